@@ -35,6 +35,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -73,7 +74,7 @@ ROCPROF_STATS_8CLIPS_ALONE = "r05_kernel_stats_bf16x3_8clips_singlestream.csv"  
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5, help="timed sample() calls")
+    ap.add_argument("--steps", type=_positive_int, default=5, help="timed sample() calls")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--clips-per-gpu", type=int, default=0, help="0 = 1 clip at --gpus 1 (configs[1]), 8 clips per GPU at --gpus N > 1 (configs[2])")
     ap.add_argument("--cfm-steps", type=int, default=32)
@@ -124,6 +125,8 @@ def main():
                          "stand-in that returns each clip's global index, the collectives run over gloo.  Everything around it -- sharding, warm-up, "
                          "barriers, the timed loop, the MAX over ranks, the all-gather, `scaling_reference` -- is this script's real code.  The line "
                          "says so in `data`; its numbers measure nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one returned (the gathered mel latents) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -285,6 +288,8 @@ def main():
         el = float(t.item())
     assert out.shape == (n_clips, T, cfg.num_channels) and bool(torch.isfinite(out).all())
     log("timed %d steps: %.1f ms/step" % (args.steps, el / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:        # now: the legs below run the sampler again and may reuse its output buffers
+        log("outputs written: %s" % dump_outputs(args.dump_outputs, {"mel": out}))
 
     ms_per_step = el / args.steps * 1e3
     ph = model.phase_ms()
@@ -374,7 +379,8 @@ def standin_main(args, v2a_amd, dist, rank, world):
     """--stand-in-sampler: the N-rank control path of main() on CPU tensors over gloo (no GPU, no HIP library).  The sampler is replaced by
     a function that returns, for every clip of the rank's shard, a (T, C) tensor filled with the clip's GLOBAL index; the all-gather must
     then hand every rank the tensor whose clip i is filled with i, whatever the partition (a batch that does not divide by the world size
-    is padded and the padding dropped).  Sharding follows v2a_amd.shard_range exactly as cli.py does for a real batch."""
+    is padded and the padding dropped).  Sharding follows v2a_amd.shard_range exactly as cli.py does for a real batch.
+    Barriers are gloo's monitored_barrier(): dist.barrier() first probes for an accelerator, which opens the GPU in every rank."""
     T, C = 6, 4
     B = args.clips_per_gpu if args.clips_per_gpu > 0 else (1 if world == 1 else 8)
     n_clips = int(os.environ.get("V2A_STANDIN_CLIPS", B * world))        # a batch size that need not divide by the world size
@@ -387,18 +393,20 @@ def standin_main(args, v2a_amd, dist, rank, world):
     for _ in range(args.warmup):
         one_step()
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = one_step()
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
     el = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     ok = out.shape == (n_clips, T, C) and all(bool((out[i] == float(i)).all()) for i in range(n_clips))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mel": out})
     frames_per_s = n_clips * T / (el / args.steps)
     res = {"metric": "stand-in (control-path rehearsal, measures nothing)", "value": round(frames_per_s, 2), "unit": "mel-frames/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -412,7 +420,7 @@ def standin_main(args, v2a_amd, dist, rank, world):
             for _ in range(args.steps):
                 sample()
             same = max(hi - lo, 1) * T / ((time.perf_counter() - ts) / args.steps)
-        dist.barrier()
+        dist.monitored_barrier()
         if rank == 0:
             res["scaling_reference"] = scaling_reference(per, same, frames_per_s, world)
     oks = [None] * world
@@ -422,8 +430,38 @@ def standin_main(args, v2a_amd, dist, rank, world):
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
         dist.destroy_process_group()
+
+
+def _positive_int(v):
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return n
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: each tensor as dirname/<name>.npy in float32 (float64 stays float64), so that two builds can be compared output
+    for output on the same seeded inputs.  An array over its share of `cap_bytes` is replaced by a fixed sample of its flattened
+    elements (seed 0, ascending index order): the same shape always gives the same positions.  Returns the paths written."""
+    os.makedirs(dirname, exist_ok=True)
+    share = cap_bytes // max(1, len(arrays))
+    paths = []
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        if a.nbytes > share:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, share // flat.itemsize, replace=False))
+            a = flat[idx]
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        paths.append(path)
+    return paths
 
 
 def summary_fields(res):

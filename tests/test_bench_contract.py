@@ -50,8 +50,30 @@ def test_traffic_block_reports_algorithmic_bytes_and_ratio(bench):
 def test_bench_help_lists_the_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-500:]
-    for flag in ("--gpus", "--steps", "--warmup", "--dtype", "--clips-per-gpu", "--no-cpu-baseline"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dtype", "--clips-per-gpu", "--no-cpu-baseline", "--dump-outputs"):
         assert flag in out.stdout, flag
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr, out.stderr[-500:]
+
+
+def test_dump_outputs_float_and_capped(bench, tmp_path):
+    """--dump-outputs: float32 (float64 kept), whole arrays under the cap, a fixed seeded sample of the elements over it."""
+    import numpy as np
+    import torch
+    small, big = torch.randn(3, 5, dtype=torch.float64), torch.randn(2, 1000)
+    paths = bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big.to(torch.bfloat16)}, cap_bytes=2048)
+    assert [os.path.basename(p) for p in paths] == ["small.npy", "big.npy"]
+    s, b = np.load(paths[0]), np.load(paths[1])
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    assert b.dtype == np.float32 and b.nbytes <= 1024 and b.size == 256
+    assert set(b.tolist()) <= set(big.to(torch.bfloat16).float().reshape(-1).tolist())
+    again = bench.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big.to(torch.bfloat16)}, cap_bytes=2048)
+    assert np.array_equal(np.load(again[1]), b)
+    whole = bench.dump_outputs(str(tmp_path / "c"), {"big": big})
+    assert np.array_equal(np.load(whole[0]), big.numpy())
 
 
 def test_scaling_reference_field(bench):

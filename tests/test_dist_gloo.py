@@ -31,7 +31,7 @@ def _worker(rank, world, port, n_clips, q):
     out = v2a_amd.gather_latents(local, n_clips, per)
     ok = out.shape == (n_clips, T, C) and all(torch.equal(out[i], torch.full((T, C), float(i)) + torch.arange(C)) for i in range(n_clips))
     q.put((rank, bool(ok)))
-    dist.barrier()
+    dist.monitored_barrier()          # not dist.barrier(): it probes for an accelerator, which opens the GPU in every rank
     dist.destroy_process_group()
 
 
@@ -104,6 +104,15 @@ def test_bench_two_rank_control_path_end_to_end():
     assert sr["clips_per_gpu"] == 8 and sr["n1_same_shape_mel_frames_per_s"] > 0
     assert abs(sr["efficiency"] - r["value"] / (2 * sr["n1_same_shape_mel_frames_per_s"])) < 1e-3
     assert "stand-in" in r["data"]
+
+
+def test_bench_dump_outputs_after_the_timed_steps(tmp_path):
+    """--dump-outputs writes, once (rank 0), the gathered latents of the last timed step: clip i filled with i."""
+    import numpy as np
+    r = _bench_standin(2, clips=3, extra=("--dump-outputs", str(tmp_path)))
+    assert r["standin_gather_ok_all_ranks"] and os.listdir(tmp_path) == ["mel.npy"]
+    mel = np.load(tmp_path / "mel.npy")
+    assert mel.dtype == np.float32 and mel.shape[0] == 3 and all((mel[i] == i).all() for i in range(3))
 
 
 def test_bench_eight_rank_control_path_ragged_batch():
