@@ -108,7 +108,13 @@ typedef struct v2a_gemm_args {
    * zero border, a_row_offset = top-left tap of output pixel m and a_ktile_offset[kt] = (ky*Wp + kx)*C + c0, so the patch
    * matrix of nn.Conv2d (Video2RollNet.py:9-12) is never materialised; lda is ignored.  With out_row_offset, row m of out,
    * resid and out_bf16 starts at base + out_row_offset[m] (the interior of the next layer's bordered map) instead of m * ld.
-   * All offsets in elements, multiples of 8; NULL = dense rows. */
+   * All offsets in elements, multiples of 8; NULL = dense rows.
+   * Split operands (a_dtype V2A_BF16_SPLIT, the bf16x3 mode) take the tables too, on the 64-wide K stage shapes only (tile_hint 0 or
+   * 1..4): the hi plane of row m / K tile kt starts at a[0] + a_row_offset[m] + a_ktile_offset[kt], its lo plane a_lo_offset[0]
+   * elements further (required, > 0, a multiple of 8; lda is not checked).  The CALLER guarantees that every hi-plane read --
+   * a_row_offset[m] + a_ktile_offset[kt] + 64 -- stays within a_lo_offset[0] (the zero-bordered NHWC hi map), the library cannot
+   * see the device tables.  A split shadow (out_bf16_split) with out_row_offset puts the lo plane of row m at out_bf16 +
+   * out_row_offset[m] + out_bf16_lo_offset (required, > 0: the hi map's size). */
   const int32_t* a_row_offset;
   const int32_t* a_ktile_offset;
   const int32_t* out_row_offset;
@@ -349,6 +355,12 @@ int v2a_im2col(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32
  * v2a_gemm computes conv1 (v2r:138, 11x11 / stride 2 / pad 4) without the patch matrix of v2a_im2col. */
 int v2a_frames_pack(const float* frames, void* out, int32_t T, int32_t H, int32_t W, int32_t kw, int32_t stride, int32_t pad,
                     int32_t Wo, v2a_stream_t stream);
+/* The same column patches in the V2A_BF16_SPLIT planes of the bf16x3 mode (conv1, v2r:138): out[i] = hi = bf16(v) for the
+ * (T+4)*Wo*(H+2*pad)*16 elements i of v2a_frames_pack, and out[lo_offset + i] = lo = bf16(v - hi) -- the grey frames are fp32
+ * intensities that one bf16 does not hold.  lo_offset >= (T+4)*Wo*(H+2*pad)*16, a multiple of 8; out holds lo_offset + that many.
+ * v2a_gemm reads both planes through the same offset tables (a_dtype V2A_BF16_SPLIT, a_lo_offset[0] = lo_offset). */
+int v2a_frames_pack_split(const float* frames, void* out, int64_t lo_offset, int32_t T, int32_t H, int32_t W, int32_t kw,
+                          int32_t stride, int32_t pad, int32_t Wo, v2a_stream_t stream);
 
 /* NHWC fp32 pooling: mode 0 = max (padding acts as -inf; nn.MaxPool2d(3, 2, 1) v2r:141), mode 1 = average over the full
  * k*k window (nn.AvgPool2d(2, 2) / (3, 1), pad 0, v2r:22-23).  C % 4 == 0.  The input / output maps may be stored with a
@@ -357,6 +369,13 @@ int v2a_frames_pack(const float* frames, void* out, int32_t T, int32_t H, int32_
 int v2a_pool2d(const float* x, float* out, void* out_bf16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
                int32_t stride, int32_t pad, int32_t mode, int32_t Ho, int32_t Wo, int32_t in_border, int32_t out_border,
                v2a_stream_t stream);
+/* v2a_pool2d with its bf16 copy in the V2A_BF16_SPLIT planes of the bf16x3 mode, written by the pooling kernel itself: out_split
+ * (required) has out's geometry twice -- hi = bf16(out) at the position of out, lo = bf16(out - hi) lo_offset elements further
+ * (>= B*(Ho+2*out_border)*(Wo+2*out_border)*C, a multiple of 4).  Only interiors are written: the caller zeroes the borders once.
+ * The maps that feed a convolution: the max pool after conv1 (v2r:141) and FTB2_1's average pool into FTB2_2 (v2r:22-23, 214). */
+int v2a_pool2d_split(const float* x, float* out, void* out_split, int64_t lo_offset, int32_t B, int32_t H, int32_t W, int32_t C,
+                     int32_t k, int32_t stride, int32_t pad, int32_t mode, int32_t Ho, int32_t Wo, int32_t in_border,
+                     int32_t out_border, v2a_stream_t stream);
 
 /* Fused top of the network (v2r:224-249 + the sigmoid of x3:1541), one workgroup per window:
  *   FRB4/3/2 channel gates (global average pool -> fc1 -> ReLU -> fc2 -> sigmoid, v2r:44-57), out1 = p2*p3, softmax over

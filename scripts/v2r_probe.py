@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Time Video2RollEngine.encode_frames for a list of chunk sizes (tuning aid).  usage: python scripts/v2r_probe.py 25 50 126 251"""
+"""Time Video2RollEngine.encode_frames on one 251-frame clip for a list of chunk sizes (tuning aid).
+usage: python scripts/v2r_probe.py [--compute bf16|bf16x3|fp32 ...] 25 50 126 251
+Several --compute values are timed side by side; no chunk size = the engine's default for that mode."""
+import argparse
 import os
 import sys
 import time
@@ -10,16 +13,23 @@ import v2a_amd  # noqa: E402,F401
 from v2a_amd.synth import random_video2roll_state_dict, synthetic_piano_frames  # noqa: E402
 from v2a_amd.video2roll import Video2RollEngine  # noqa: E402
 
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--compute", action="append", choices=["bf16", "bf16x3", "fp32"], help="engine mode (repeatable; default bf16)")
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("chunks", type=int, nargs="*")
+a = ap.parse_args()
+
 sd = random_video2roll_state_dict(0)
 x = synthetic_piano_frames(1, 251, seed=0).to("cuda")
-for ch in [int(a) for a in sys.argv[1:]]:
-    eng = Video2RollEngine(sd, "cuda", compute="bf16", chunk=ch)
-    eng.encode_frames(x, 750)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(3):
+for mode in a.compute or ["bf16"]:
+    for ch in a.chunks or [None]:
+        eng = Video2RollEngine(sd, "cuda", compute=mode, chunk=ch)
         eng.encode_frames(x, 750)
-    torch.cuda.synchronize()
-    print(f"chunk {ch:4d}: {(time.perf_counter() - t0) / 3 * 1e3:7.2f} ms per 251-frame clip", flush=True)
-    del eng
-    torch.cuda.empty_cache()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            eng.encode_frames(x, 750)
+        torch.cuda.synchronize()
+        print(f"{mode:6s} chunk {eng.chunk:4d}: {(time.perf_counter() - t0) / a.reps * 1e3:7.2f} ms per 251-frame clip", flush=True)
+        del eng
+        torch.cuda.empty_cache()

@@ -88,7 +88,7 @@ EXPORTS = [
     "v2a_abi_version", "v2a_last_error", "v2a_gemm", "v2a_gemm_args_size", "v2a_set_tuning", "v2a_rmsnorm", "v2a_dwconv_silu_residual", "v2a_dwconv_silu_residual_norm",
     "v2a_rope_inplace", "v2a_attention", "v2a_qproj_xattn", "v2a_linear_small", "v2a_fill_registers", "v2a_time_cond",
     "v2a_apg_reduce", "v2a_cfg_euler", "v2a_step_advance", "v2a_cast_bf16", "v2a_split_bf16",
-    "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand",
+    "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand", "v2a_frames_pack_split", "v2a_pool2d_split",
     "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2",
 ]
 
@@ -134,6 +134,8 @@ def _declare(lib):
     lib.v2a_im2col.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, i32, i32, vp]
     lib.v2a_frames_pack.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.v2a_pool2d.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.v2a_frames_pack_split.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.v2a_pool2d_split.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.v2a_roll_head.argtypes = [C.POINTER(RollHeadArgs), vp]
     lib.v2a_roll_expand.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.v2a_elu_pad.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
@@ -505,10 +507,23 @@ def frames_pack(frames, out, *, T, H, W, kw, stride, pad, Wo):
             lambda: lib().v2a_frames_pack(frames.data_ptr(), out.data_ptr(), T, H, W, kw, stride, pad, Wo, stream_ptr()))
 
 
+def frames_pack_split(frames, out, *, lo_offset, T, H, W, kw, stride, pad, Wo):
+    """bf16x3 mode: the column patches of frames_pack as hi | lo planes, the lo plane lo_offset elements after the hi one."""
+    _launch("frames_pack_split", 0.0, 4.0 * T * H * W + 64.0 * (T + 4) * Wo * (H + 2 * pad),
+            lambda: lib().v2a_frames_pack_split(frames.data_ptr(), out.data_ptr(), lo_offset, T, H, W, kw, stride, pad, Wo, stream_ptr()))
+
+
 def pool2d(x, out, *, B, H, W, C_, k, stride, pad, mode, Ho, Wo, out_bf16=None, in_border=0, out_border=0):
     _launch("pool2d", 0.0, 4.0 * B * C_ * (H * W + Ho * Wo),
             lambda: lib().v2a_pool2d(x.data_ptr(), out.data_ptr(), _p(out_bf16), B, H, W, C_, k, stride, pad, mode, Ho, Wo,
                                      in_border, out_border, stream_ptr()))
+
+
+def pool2d_split(x, out, out_split, *, lo_offset, B, H, W, C_, k, stride, pad, mode, Ho, Wo, in_border=0, out_border=0):
+    """bf16x3 mode: pool2d whose bf16 copy is written as hi | lo planes (out_split, the lo plane lo_offset elements further)."""
+    _launch("pool2d_split", 0.0, 4.0 * B * C_ * (H * W + 2 * Ho * Wo),
+            lambda: lib().v2a_pool2d_split(x.data_ptr(), out.data_ptr(), out_split.data_ptr(), lo_offset, B, H, W, C_, k, stride, pad,
+                                           mode, Ho, Wo, in_border, out_border, stream_ptr()))
 
 
 def roll_head(args: "RollHeadArgs"):

@@ -82,6 +82,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the cached piano frames through the Video2Roll encoder")
+    ap.add_argument("--frames-dtype", default=None, choices=["fp32", "bf16", "bf16x3"],
+                    help="compute mode of the Video2Roll encoder behind --piano (default: bf16 under --dtype bf16, else fp32); bf16x3: "
+                         "split-bf16 implicit GEMM inside 1e-4 of the reference probabilities")
     ap.add_argument("--encodec", default=None, help="state dict (.pt) of the Encodec model / decoder: also write <name>.wav")
     a = ap.parse_args(argv)
 
@@ -98,7 +101,8 @@ def main(argv=None):
     channels = tk.pop("num_channels", 128)
     model = E2TTS(transformer=dict(if_text_modules=True, if_cross_attn=True, if_audio_conv=True, if_text_conv=True, **tk),
                   num_channels=channels, sampling_rate=24000, if_cond_proj_in=False, tokenizer="phoneme_zh",
-                  compute_dtype=a.dtype, device=torch.device("cuda", local), bucket_frames=a.bucket_frames, bucket_ctx=a.bucket_ctx)
+                  compute_dtype=a.dtype, device=torch.device("cuda", local), bucket_frames=a.bucket_frames, bucket_ctx=a.bucket_ctx,
+                  frames_compute_dtype=a.frames_dtype)
     ck = torch.load(a.ckpt, map_location="cpu")
     res = model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # predict.py:161-168
     if res.missing_keys:

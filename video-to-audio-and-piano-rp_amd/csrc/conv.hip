@@ -81,8 +81,10 @@ __global__ __launch_bounds__(256) void im2col_window_kernel(const float* __restr
 // For output pixel (window i, yo, xo) and input channel c the kh x kw taps are then the kh consecutive 16-element rows
 // starting at out[i + c][xo][stride*yo]: K tiles of 64 elements are contiguous, so the LDS-DMA GEMM reads them through its
 // row / K-tile offset tables and the 28 MB-per-window patch matrix of v2a_im2col is never written.
+// SPLIT (bf16x3 mode, v2a_frames_pack_split): the same patches as hi = bf16(v) and, lo_off elements further, lo = bf16(v - hi).
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void frames_pack_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int64_t total, int T,
-                                                          int H, int W, int Wo, int Hp, int kw, int stride, int pad) {
+                                                          int H, int W, int Wo, int Hp, int kw, int stride, int pad, int64_t lo_off) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;      // one thread per (j, xo, y)
   if (gid >= total) return;
   const int y = (int)(gid % Hp);
@@ -92,24 +94,35 @@ __global__ __launch_bounds__(256) void frames_pack_kernel(const float* __restric
   int f = j - 2;
   f = f < 0 ? 0 : (f > T - 1 ? T - 1 : f);
   const int yi = y - pad;
-  bf16x8 lo, hi;
+  bf16x8 lo, hi, lo2, hi2;       // elements 0..7 / 8..15 of the row; lo2 / hi2: the same of the split's lo plane
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int xi = xo * stride - pad + e;
     float v = 0.f;
     if (e < kw && yi >= 0 && yi < H && xi >= 0 && xi < W) v = x[((int64_t)f * H + yi) * W + xi];
-    if (e < 8) lo[e] = (bf16_t)v; else hi[e - 8] = (bf16_t)v;
+    const bf16_t b = (bf16_t)v;
+    if (e < 8) lo[e] = b; else hi[e - 8] = b;
+    if constexpr (SPLIT) {
+      const bf16_t r = (bf16_t)(v - (float)b);
+      if (e < 8) lo2[e] = r; else hi2[e - 8] = r;
+    }
   }
   bf16x8* dst = reinterpret_cast<bf16x8*>(out + gid * 16);
   dst[0] = lo;
   dst[1] = hi;
+  if constexpr (SPLIT) {
+    bf16x8* dst2 = reinterpret_cast<bf16x8*>(out + lo_off + gid * 16);
+    dst2[0] = lo2;
+    dst2[1] = hi2;
+  }
 }
 
 // ---- pooling, NHWC fp32, one thread per (n, yo, xo, 4 channels) ---------------------------------------------------------
-template <bool MAX>
+// SPLIT (bf16x3 mode, v2a_pool2d_split): out2 receives hi = bf16(out) and, lo_off elements further, lo = bf16(out - hi)
+template <bool MAX, bool SPLIT = false>
 __global__ __launch_bounds__(256) void pool2d_kernel(const float* __restrict__ x, float* __restrict__ out, bf16_t* __restrict__ out2,
                                                      int64_t total, int H, int W, int C4, int k, int stride, int pad, int Ho, int Wo,
-                                                     int ib, int ob) {
+                                                     int ib, int ob, int64_t lo_off = 0) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= total) return;
   const int c4 = (int)(gid % C4);
@@ -138,7 +151,22 @@ __global__ __launch_bounds__(256) void pool2d_kernel(const float* __restrict__ x
   }
   const int64_t o = (((n * (Ho + 2 * ob) + yo + ob) * (Wo + 2 * ob) + xo + ob) * C4 + c4) * 4;
   *reinterpret_cast<f32x4*>(out + o) = acc;
-  if (out2) store4<bf16_t>(out2 + o, acc);
+  if constexpr (SPLIT) {
+    bf16x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      // the split of the STORED fp32 value: without the barrier -ffp-contract=fast fuses the average's 1/k^2 scaling into the
+      // subtraction, and lo then splits the unrounded mean (found by the bit-exact test of the 3x3 average pool)
+      float a = acc[e];
+      asm volatile("" : "+v"(a));
+      hi[e] = (bf16_t)a;
+      lo[e] = (bf16_t)(a - (float)hi[e]);
+    }
+    *reinterpret_cast<bf16x4*>(out2 + o) = hi;
+    *reinterpret_cast<bf16x4*>(out2 + lo_off + o) = lo;
+  } else {
+    if (out2) store4<bf16_t>(out2 + o, acc);
+  }
 }
 
 // ---- fused head: one workgroup of 128 threads (thread = channel) per window ---------------------------------------------
@@ -283,9 +311,25 @@ extern "C" int v2a_frames_pack(const float* frames, void* out, int32_t T, int32_
   V2A_REQUIRE(((uintptr_t)out & 15) == 0, "v2a_frames_pack: 16-byte alignment");
   const int Hp = H + 2 * pad;
   const int64_t total = (int64_t)(T + 4) * Wo * Hp;
-  hipLaunchKernelGGL(frames_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames, (bf16_t*)out,
-                     total, T, H, W, Wo, Hp, kw, stride, pad);
+  hipLaunchKernelGGL(frames_pack_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames,
+                     (bf16_t*)out, total, T, H, W, Wo, Hp, kw, stride, pad, (int64_t)0);
   return v2a_check_launch("v2a_frames_pack");
+}
+
+extern "C" int v2a_frames_pack_split(const float* frames, void* out, int64_t lo_offset, int32_t T, int32_t H, int32_t W, int32_t kw,
+                                     int32_t stride, int32_t pad, int32_t Wo, v2a_stream_t stream) {
+  V2A_REQUIRE(frames && out, "v2a_frames_pack_split: null pointer");
+  V2A_REQUIRE(T > 0 && H > 0 && W > 0 && kw > 0 && kw <= 16 && stride > 0 && pad >= 0, "v2a_frames_pack_split: bad geometry (kw=%d)", kw);
+  V2A_REQUIRE(Wo == (W + 2 * pad - kw) / stride + 1, "v2a_frames_pack_split: Wo=%d does not match the convolution geometry", Wo);
+  V2A_REQUIRE(((uintptr_t)out & 15) == 0, "v2a_frames_pack_split: 16-byte alignment");
+  const int Hp = H + 2 * pad;
+  const int64_t total = (int64_t)(T + 4) * Wo * Hp;
+  V2A_REQUIRE(lo_offset >= total * 16 && lo_offset % 8 == 0,
+              "v2a_frames_pack_split: lo_offset %lld must be >= the hi plane (%lld elements) and a multiple of 8", (long long)lo_offset,
+              (long long)(total * 16));
+  hipLaunchKernelGGL(frames_pack_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames,
+                     (bf16_t*)out, total, T, H, W, Wo, Hp, kw, stride, pad, lo_offset);
+  return v2a_check_launch("v2a_frames_pack_split");
 }
 
 extern "C" int v2a_pool2d(const float* x, float* out, void* out_bf16, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
@@ -305,6 +349,29 @@ extern "C" int v2a_pool2d(const float* x, float* out, void* out_bf16, int32_t B,
     hipLaunchKernelGGL((pool2d_kernel<false>), grid, block, 0, (hipStream_t)stream, x, out, (bf16_t*)out_bf16, total, H, W, C / 4, k,
                        stride, pad, Ho, Wo, in_border, out_border);
   return v2a_check_launch("v2a_pool2d");
+}
+
+extern "C" int v2a_pool2d_split(const float* x, float* out, void* out_split, int64_t lo_offset, int32_t B, int32_t H, int32_t W, int32_t C,
+                                int32_t k, int32_t stride, int32_t pad, int32_t mode, int32_t Ho, int32_t Wo, int32_t in_border,
+                                int32_t out_border, v2a_stream_t stream) {
+  V2A_REQUIRE(x && out && out_split && x != out, "v2a_pool2d_split: null / aliased pointer");
+  V2A_REQUIRE(B > 0 && C > 0 && C % 4 == 0 && k > 0 && stride > 0 && pad >= 0 && pad < k, "v2a_pool2d_split: bad geometry (C=%d k=%d)", C, k);
+  V2A_REQUIRE(Ho == (H + 2 * pad - k) / stride + 1 && Wo == (W + 2 * pad - k) / stride + 1, "v2a_pool2d_split: Ho/Wo mismatch");
+  V2A_REQUIRE(mode == 0 || (mode == 1 && pad == 0), "v2a_pool2d_split: mode %d (average pooling is built for pad 0)", mode);
+  V2A_REQUIRE(in_border >= 0 && out_border >= 0 && ((uintptr_t)out_split & 7) == 0, "v2a_pool2d_split: borders / bf16 alignment");
+  const int64_t plane = (int64_t)B * (Ho + 2 * out_border) * (Wo + 2 * out_border) * C;
+  V2A_REQUIRE(lo_offset >= plane && lo_offset % 4 == 0,
+              "v2a_pool2d_split: lo_offset %lld must be >= the hi plane (%lld elements) and a multiple of 4", (long long)lo_offset,
+              (long long)plane);
+  const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
+  dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (mode == 0)
+    hipLaunchKernelGGL((pool2d_kernel<true, true>), grid, block, 0, (hipStream_t)stream, x, out, (bf16_t*)out_split, total, H, W, C / 4,
+                       k, stride, pad, Ho, Wo, in_border, out_border, lo_offset);
+  else
+    hipLaunchKernelGGL((pool2d_kernel<false, true>), grid, block, 0, (hipStream_t)stream, x, out, (bf16_t*)out_split, total, H, W, C / 4,
+                       k, stride, pad, Ho, Wo, in_border, out_border, lo_offset);
+  return v2a_check_launch("v2a_pool2d_split");
 }
 
 extern "C" int v2a_roll_head(const v2a_roll_head_args* a, v2a_stream_t stream) {

@@ -589,7 +589,8 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
     V2A_REQUIRE(a->a[s] != nullptr, "v2a_gemm: segment %d null", s);
     V2A_REQUIRE(a->ka[s] > 0 && a->ka[s] % bk == 0, "v2a_gemm: segment %d K=%d not a multiple of %d", s, a->ka[s], bk);
     V2A_REQUIRE(a->lda[s] % a_vec == 0 && ((uintptr_t)a->a[s] & 15) == 0, "v2a_gemm: segment %d not 16-byte aligned", s);
-    if (split_in) V2A_REQUIRE(a->lda[s] >= 2 * (int64_t)a->ka[s], "v2a_gemm: split segment %d needs lda >= 2 * K (hi | lo planes)", s);
+    // with offset tables (implicit-GEMM convolution) lda is ignored: the planes are a_lo_offset apart, checked below
+    if (split_in && !a->a_row_offset) V2A_REQUIRE(a->lda[s] >= 2 * (int64_t)a->ka[s], "v2a_gemm: split segment %d needs lda >= 2 * K (hi | lo planes)", s);
     p.a[s] = a->a[s];
     p.lda[s] = a->lda[s];
     K += a->ka[s];
@@ -612,14 +613,22 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   if (a->out_bf16) V2A_REQUIRE(a->out_dtype == V2A_F32 && a->epilogue != V2A_EPI_GEGLU, "v2a_gemm: out_bf16 shadows an fp32 output only");
   p.out2_split = a->out_bf16 && a->out_bf16_split ? 1 : 0;
   p.out2_lo = a->out_bf16_lo_offset > 0 ? a->out_bf16_lo_offset : a->N;
-  if (p.out2_split)
+  if (p.out2_split && a->out_row_offset)      // scattered rows (a bordered map): the lo plane is a whole map further, not a row part
+    V2A_REQUIRE(a->out_bf16_lo_offset > 0 && a->out_bf16_lo_offset % 4 == 0,
+                "v2a_gemm: a split shadow with out_row_offset needs an explicit out_bf16_lo_offset (%lld) > 0, a multiple of 4",
+                (long long)a->out_bf16_lo_offset);
+  else if (p.out2_split)
     V2A_REQUIRE(p.out2_lo >= a->N && p.out2_lo % 4 == 0 && a->ld_out_bf16 >= p.out2_lo + (int64_t)a->N,
                 "v2a_gemm: a split shadow needs out_bf16_lo_offset (%lld) >= N, a multiple of 4, and ld_out_bf16 >= lo offset + N", (long long)p.out2_lo);
   else
     V2A_REQUIRE(a->out_bf16_lo_offset == 0, "v2a_gemm: out_bf16_lo_offset goes with out_bf16_split");
   for (int sg = 0; sg < a->nseg; ++sg) {
     p.alo[sg] = a->a_lo_offset[sg] > 0 ? a->a_lo_offset[sg] : a->ka[sg];
-    if (split_in)
+    if (split_in && a->a_row_offset)     // the caller guarantees that every hi-plane row / K-tile offset stays below a_lo_offset
+      V2A_REQUIRE(a->a_lo_offset[sg] > 0 && a->a_lo_offset[sg] % 8 == 0,
+                  "v2a_gemm: split operands with offset tables need an explicit a_lo_offset (%lld) > 0, a multiple of 8",
+                  (long long)a->a_lo_offset[sg]);
+    else if (split_in)
       V2A_REQUIRE(p.alo[sg] >= a->ka[sg] && p.alo[sg] % 8 == 0 && a->lda[sg] >= p.alo[sg] + (int64_t)a->ka[sg],
                   "v2a_gemm: split segment %d: a_lo_offset (%lld) must be >= K, a multiple of 8, and lda >= lo offset + K", sg, (long long)p.alo[sg]);
     else
@@ -673,9 +682,9 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   p.o_rowoff = a->out_row_offset;
   if (a->a_row_offset || a->a_ktile_offset || a->out_row_offset) {
     V2A_REQUIRE((a->a_row_offset != nullptr) == (a->a_ktile_offset != nullptr), "v2a_gemm: a_row_offset and a_ktile_offset go together");
-    V2A_REQUIRE(a->nseg == 1 && a->compute_dtype == V2A_BF16 && a->a_dtype == V2A_BF16 && p.vec_epi &&
+    V2A_REQUIRE(a->nseg == 1 && a->compute_dtype == V2A_BF16 && (a->a_dtype == V2A_BF16 || split_in) && p.vec_epi &&
                     (a->epilogue == V2A_EPI_STORE || a->epilogue == V2A_EPI_RESID) && !a->rope_table,
-                "v2a_gemm: row/K-tile offset tables need one bf16 segment, bf16 compute, STORE/RESID and 16-byte aligned rows");
+                "v2a_gemm: row/K-tile offset tables need one bf16 (or split bf16) segment, bf16 compute, STORE/RESID and 16-byte aligned rows");
   }
   V2A_REQUIRE(!a->relu || a->epilogue != V2A_EPI_GEGLU, "v2a_gemm: relu with GEGLU");
   p.ngam = a->norm_gamma;
@@ -734,8 +743,13 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
     return dispatch_epi<float, false, 128, 128>(a, p, s);
   }
   if (split_in) {
-    V2A_REQUIRE(p.vec_epi && !a->a_row_offset && !a->out_row_offset, "v2a_gemm: split operands need dense rows and 16-byte aligned epilogue operands");
+    V2A_REQUIRE(p.vec_epi, "v2a_gemm: split operands need 16-byte aligned epilogue operands");
     V2A_REQUIRE(a->tile_hint >= 0 && a->tile_hint <= 7, "v2a_gemm: tile_hint %d with split operands (0 = by shape, 1..7)", a->tile_hint);
+    // implicit-GEMM convolution (the bf16x3 Video2Roll encoder): offset tables run on the BK = 64 split ring shapes 1..4 only -- the
+    // 8-phase kernel knows dense rows only, and the K-tile tables are laid out for 64-wide K tiles (shapes 6 / 7 stage 32)
+    const bool scattered = a->a_row_offset || a->out_row_offset;
+    V2A_REQUIRE(!scattered || a->tile_hint <= 4,
+                "v2a_gemm: tile_hint %d with split operands and offset tables (0 = by shape, 1..4: the 64-wide K stage ring shapes)", a->tile_hint);
     auto nt = [&](int bm, int bn) { return (int64_t)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
     // split-operand tile shapes (hi + lo planes double a stage): 1 = 64x64 (96 KB), 2 = 128x64 (144 KB), 3 = 128x128 with 8 waves and a
     // 2-deep ring (128 KB), 4 = 64x128 with 8 waves (144 KB), 5 = the 8-phase kernel; with 32-wide K stages (round 5): 6 = 128x256 with
@@ -747,7 +761,7 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
     // 102 us on the best split ring tile) and -- round 5 -- narrow ones (512 < N < 2048, any number of logical segments) from 150 tiles,
     // i.e. from ~6 clips per GPU: at 8 clips the 64x128 split ring ran them at 28 % of the MFMA peak (issued products) against 46 % here.
     // tile_hint 5 asks for it, 0 picks by shape.
-    const bool wide8 = tune.use_8phase && (cfg == 5 || (cfg == 0 && a->N > 512 && nt(256, 256) >= 150));
+    const bool wide8 = !scattered && tune.use_8phase && (cfg == 5 || (cfg == 0 && a->N > 512 && nt(256, 256) >= 150));
     if (wide8) {
       GemmParams q = p;
       split_as_three_passes(q);
@@ -759,7 +773,14 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
     // (a 128x128 tile whose two wave groups alternate along K -- one multiplies a stage while the other reads and stages the next -- was built
     // and measured in round 5: 20-25 % slower than shape 7, bound by the DMA issue of its loading waves; profiles/r05_pingpong_probe.txt, source
     // kept as scripts/probes/gemm_pingpong.hip.txt)
-    if (cfg == 0) {
+    if (cfg == 0 && scattered) {
+      // Video2Roll convolutions (scripts/v2r_split_tiles.py, one 251-frame clip per launch, RESID + ReLU + split shadow; us for
+      // shapes 1 / 2 / 3 / 4):  N = 64,  M 1.41e6, K 576:  899 / 740 / 846 / 984;   N = 128, M 3.7e5, K 1152: 677 / 584 / 406 / 450;
+      // N = 256, M 1.0e5, K 2304: 590 / 534 / 396 / 416;  N = 512, M 2.9e4, K 4608: 632 / 620 / 401 / 450;  N = 128, M 4.7e4, K 512
+      // (FTB4 conv0): 61 / 57 / 42 / 40.  128x64 for the 64-channel layers, the 8-wave 128x128 tile from N = 128 on; 64x128 only
+      // below 256 tiles of 128x128 (unmeasured for the encoder: its smallest launch has 365)
+      cfg = a->N <= 64 ? 2 : (nt(128, 128) >= 256 ? 3 : 4);
+    } else if (cfg == 0) {
       // (stand-alone, scripts/split_probe.py, profiles/r05_split_probe.txt)
       if (a->epilogue == V2A_EPI_GEGLU || a->N >= 2048) cfg = nt(128, 128) >= 200 ? 3 : 4;
       // N <= 512 with many rows (the frames stream at 8 clips per GPU: 98 tiles of 256x256 cannot fill the chip on the 8-phase kernel):

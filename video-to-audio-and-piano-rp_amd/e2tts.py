@@ -161,6 +161,7 @@ class E2TTS:
         video_encoder_fn: Callable | None = None,   # (video_paths, n) -> (b, n, dim_text)
         text_encoder_fn: Callable | None = None,    # (prompts) -> ((b, nc, ctx) float, (b, nc) bool)
         frames_encoder_fn: Callable | None = None,  # (frames, n) -> (b, n, NOTES)
+        frames_compute_dtype: str | None = None,    # Video2Roll encoder mode: None = "bf16" under compute_dtype "bf16", else "fp32"; or "fp32" | "bf16" | "bf16x3"
     ):
         if not isinstance(transformer, dict):
             raise TypeError("transformer must be the keyword dict of the reference (predict.py:120-134)")
@@ -192,6 +193,9 @@ class E2TTS:
         if compute_dtype not in ("bf16", "fp32", "bf16x3"):
             raise ValueError(f"compute_dtype must be 'bf16', 'fp32' or 'bf16x3', got {compute_dtype!r}")
         self._compute = compute_dtype
+        if frames_compute_dtype is not None and frames_compute_dtype not in ("bf16", "fp32", "bf16x3"):
+            raise ValueError(f"frames_compute_dtype must be None, 'bf16', 'fp32' or 'bf16x3', got {frames_compute_dtype!r}")
+        self._frames_compute = frames_compute_dtype or ("bf16" if compute_dtype == "bf16" else "fp32")
         self._rope = (rope_layout, rope_cross)
         self._use_graph = use_graph
         # Shape buckets: captions and durations vary per clip (predict.py:210-237), and every new (frames, context) shape costs a
@@ -286,7 +290,7 @@ class E2TTS:
                                "frames_embed= or frames_encoder_fn= instead")
         if self._v2r is None:
             from .video2roll import Video2RollEngine
-            self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute="bf16" if self._compute == "bf16" else "fp32")
+            self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute)
         return self._v2r.encode_frames(x, l)
 
     def _get_context(self, prompt, context, context_mask, b):

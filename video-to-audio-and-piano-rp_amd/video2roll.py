@@ -69,11 +69,18 @@ def expected_state_dict_shapes(num_classes: int = NOTES) -> dict[str, tuple]:
     return s
 
 
+def _split_rows(w):
+    """fp32 rows -> [W_hi | W_lo] bf16 rows (V2A_BF16_SPLIT): hi = bf16(w), lo = bf16(w - hi)."""
+    hi = w.to(torch.bfloat16)
+    return torch.cat([hi, (w - hi.float()).to(torch.bfloat16)], 1)
+
+
 class _Conv:
     """One convolution as a GEMM operand: weight [Cout][Kpad] in the compute dtype (BatchNorm scale folded in),
-    fp32 bias (folded BatchNorm shift, plus the conv's own bias where it has one)."""
+    fp32 bias (folded BatchNorm shift, plus the conv's own bias where it has one).  split (bf16x3 mode): weight rows
+    [W_hi | W_lo] (ldw = 2*Kpad), split from the FOLDED fp32 weight."""
 
-    def __init__(self, sd, wkey, bnkey, dev, cd, *, stride, pad, window=False, conv_bias=None):
+    def __init__(self, sd, wkey, bnkey, dev, cd, *, stride, pad, window=False, conv_bias=None, split=False):
         w = sd[wkey].float()
         co, ci, kh, kw = w.shape
         bias = sd[conv_bias].float() if conv_bias else None
@@ -89,14 +96,15 @@ class _Conv:
         self.Kpad = (K + kq - 1) // kq * kq
         wp = torch.zeros(co, self.Kpad)
         wp[:, :K] = wk
-        self.w = wp.to(dev, cd).contiguous()
+        self.w = (_split_rows(wp) if split else wp.to(cd)).to(dev).contiguous()
         self.w_pack = None
         if window and cd == torch.bfloat16:
             # implicit first layer (v2a_frames_pack): per input channel kh rows of 16 columns, padded to whole 64-element K tiles
             g = (kh + 3) // 4
             wq = torch.zeros(co, ci, g * 4, 16)
             wq[:, :, :kh, :kw] = w
-            self.w_pack = wq.reshape(co, ci * g * 64).to(dev, cd).contiguous()
+            wq = wq.reshape(co, ci * g * 64)
+            self.w_pack = (_split_rows(wq) if split else wq.to(cd)).to(dev).contiguous()
             self.g = g
         self.bias = None if bias is None else bias.to(dev).contiguous()
         self.co, self.ci, self.kh, self.kw, self.stride, self.pad, self.window = co, ci, kh, kw, stride, pad, window
@@ -109,19 +117,23 @@ class Video2RollEngine:
     """`video2roll_net` + `encode_frames` of the reference E2TTS on HIP kernels.
 
     sd: state dict of the reference module (`video2roll_net.` prefix already stripped, or pass prefix=).
-    compute: "bf16" (bf16 MFMA operands, fp32 accumulate / activations) or "fp32" (parity mode, exact-fp32 MFMA).
-    chunk: windows per pass.  Default 256 in bf16 mode (implicit GEMM: no patch matrix; ~22 MB of activation maps per window,
-    and one pass per clip measured fastest: 8.8 ms per 251-frame clip vs 13.3 ms at 25) and 16 in fp32 mode (the explicit
-    fp32 patch matrix of the first layer is 53 MB per window)."""
+    compute: "bf16" (bf16 MFMA operands, fp32 accumulate / activations), "bf16x3" (split-bf16 hi | lo operand planes on both
+    sides, three MFMA products per fp32 product, fp32 accumulate / activations: the parity mode at implicit-GEMM speed) or
+    "fp32" (exact-fp32 MFMA over explicit patch matrices).
+    chunk: windows per pass.  Default 256 in the bf16 and bf16x3 modes (implicit GEMM: no patch matrix; ~22 MB of activation maps
+    per window in bf16, ~29 MB in bf16x3, and one pass per clip measured fastest: 8.8 ms per 251-frame clip vs 13.3 ms at 25 in
+    bf16) and 16 in fp32 mode (the explicit fp32 patch matrix of the first layer is 53 MB per window)."""
 
     def __init__(self, sd, device="cuda:0", compute="bf16", prefix="", chunk=None):
         L.lib()                                                   # fail loudly without the HIP library
         self.dev = torch.device(device)
-        if compute not in ("bf16", "fp32"):
-            raise ValueError(f"compute must be 'bf16' or 'fp32', got {compute!r}")
-        self.cd = torch.bfloat16 if compute == "bf16" else torch.float32
-        self.code = L.BF16 if compute == "bf16" else L.F32
-        self.chunk = int(chunk) if chunk else (256 if compute == "bf16" else 16)
+        if compute not in ("bf16", "bf16x3", "fp32"):
+            raise ValueError(f"compute must be 'bf16', 'bf16x3' or 'fp32', got {compute!r}")
+        self.compute = compute
+        self.split = compute == "bf16x3"
+        self.cd = torch.float32 if compute == "fp32" else torch.bfloat16
+        self.code = L.F32 if compute == "fp32" else L.BF16
+        self.chunk = int(chunk) if chunk else (16 if compute == "fp32" else 256)
         sd = {k[len(prefix):]: v.detach().cpu() for k, v in sd.items() if k.startswith(prefix)}
         want = expected_state_dict_shapes(sd["fc.weight"].shape[0] if "fc.weight" in sd else NOTES)
         missing = [k for k in want if k not in sd and not k.endswith("num_batches_tracked")]
@@ -132,21 +144,22 @@ class Video2RollEngine:
             raise ValueError(f"Video2RollEngine: shape mismatch for {bad[:4]}")
         self.notes = sd["fc.weight"].shape[0]
         dev, cd = self.dev, self.cd
+        _Cv = lambda *a, **k: _Conv(*a, split=self.split, **k)
         c = {}
-        c["conv1"] = _Conv(sd, "conv1.weight", "bn1", dev, cd, stride=2, pad=4, window=True)
+        c["conv1"] = _Cv(sd, "conv1.weight", "bn1", dev, cd, stride=2, pad=4, window=True)
         for name, planes, stride in _LAYERS:
             for b in range(2):
                 p = f"{name}.{b}"
                 st = stride if b == 0 else 1
-                c[f"{p}.conv1"] = _Conv(sd, f"{p}.conv1.weight", f"{p}.bn1", dev, cd, stride=st, pad=1)
-                c[f"{p}.conv2"] = _Conv(sd, f"{p}.conv2.weight", f"{p}.bn2", dev, cd, stride=1, pad=1)
+                c[f"{p}.conv1"] = _Cv(sd, f"{p}.conv1.weight", f"{p}.bn1", dev, cd, stride=st, pad=1)
+                c[f"{p}.conv2"] = _Cv(sd, f"{p}.conv2.weight", f"{p}.bn2", dev, cd, stride=1, pad=1)
                 if f"{p}.downsample.0.weight" in sd:
-                    c[f"{p}.down"] = _Conv(sd, f"{p}.downsample.0.weight", f"{p}.downsample.1", dev, cd, stride=st, pad=0)
+                    c[f"{p}.down"] = _Cv(sd, f"{p}.downsample.0.weight", f"{p}.downsample.1", dev, cd, stride=st, pad=0)
         for name in ("FTB2_1", "FTB2_2", "FTB3", "FTB4"):
-            c[f"{name}.conv0"] = _Conv(sd, f"{name}.conv0.weight", None, dev, cd, stride=1, pad=1)
-            c[f"{name}.conv1"] = _Conv(sd, f"{name}.conv1.weight", f"{name}.bn1", dev, cd, stride=1, pad=1)
-            c[f"{name}.conv2"] = _Conv(sd, f"{name}.conv2.weight", None, dev, cd, stride=1, pad=1)
-        c["toplayer"] = _Conv(sd, "toplayer.weight", "toplayer_bn", dev, cd, stride=1, pad=0, conv_bias="toplayer.bias")
+            c[f"{name}.conv0"] = _Cv(sd, f"{name}.conv0.weight", None, dev, cd, stride=1, pad=1)
+            c[f"{name}.conv1"] = _Cv(sd, f"{name}.conv1.weight", f"{name}.bn1", dev, cd, stride=1, pad=1)
+            c[f"{name}.conv2"] = _Cv(sd, f"{name}.conv2.weight", None, dev, cd, stride=1, pad=1)
+        c["toplayer"] = _Cv(sd, "toplayer.weight", "toplayer_bn", dev, cd, stride=1, pad=0, conv_bias="toplayer.bias")
         self.convs = c
         t32 = lambda k: sd[k].float().t().contiguous().to(dev)    # [in][out]
         f32 = lambda k: sd[k].float().contiguous().to(dev)
@@ -164,13 +177,15 @@ class Video2RollEngine:
         self._tabs: dict = {}
         self._col = None
         # bf16: implicit GEMM (the MFMA kernel gathers patch rows from zero-bordered NHWC bf16 maps through offset tables);
-        # fp32 parity mode: explicit patch matrix + the exact-fp32 GEMM.  The windowed first layer uses im2col in both.
-        self.implicit = compute == "bf16"
+        # bf16x3: the same over hi | lo planes of the maps (split shadows) and of the weights, the first layer included;
+        # fp32 parity mode: explicit patch matrix + the exact-fp32 GEMM, the windowed first layer through im2col.
+        self.implicit = compute != "fp32"
 
     # ---- activation maps --------------------------------------------------------------------------
     class _Map:
         """NHWC fp32 activation (n, H + 2b, W + 2b, C) with a zero border of b pixels, plus its bf16 copy when a
-        convolution reads it (the DMA GEMM moves raw bf16 bytes)."""
+        convolution reads it (the DMA GEMM moves raw bf16 bytes).  bf16x3 mode: the copy is a split shadow
+        (2, n, H + 2b, W + 2b, C) -- plane 0 hi, plane 1 lo, both zero-bordered."""
         __slots__ = ("f32", "b16", "n", "H", "W", "C", "border")
 
         def __init__(self, f32, b16, n, H, W, C, border):
@@ -181,13 +196,15 @@ class Video2RollEngine:
             return self.f32 if b == 0 else self.f32[:, b:-b, b:-b, :]
 
     def _map(self, name, n, H, W, C, border=0, shadow=False):
-        """Cached by full geometry: a bordered map relies on its border staying zero, so two geometries never share memory."""
-        key = (name, n, H, W, C, border, shadow)
+        """Cached by full geometry: a bordered map relies on its border staying zero, so two geometries never share memory
+        (nor does a split shadow share memory with a plain one)."""
+        split = shadow and self.split
+        key = (name, n, H, W, C, border, shadow, split)
         m = self._maps.get(key)
         if m is None:
             shp = (n, H + 2 * border, W + 2 * border, C)
             f32 = torch.zeros(shp, device=self.dev, dtype=torch.float32)
-            b16 = torch.zeros(shp, device=self.dev, dtype=torch.bfloat16) if shadow else None
+            b16 = torch.zeros(((2,) if split else ()) + shp, device=self.dev, dtype=torch.bfloat16) if shadow else None
             m = self._maps[key] = self._Map(f32, b16, n, H, W, C, border)
         return m
 
@@ -241,6 +258,10 @@ class Video2RollEngine:
             assert (resid.n, resid.H, resid.W, resid.C, resid.border) == (dst.n, dst.H, dst.W, dst.C, dst.border)
         epi = L.EPI_RESID if resid is not None else L.EPI_STORE
         rs = None if resid is None else resid.f32
+        # bf16x3: the A operand's lo plane is a whole map (plane) after its hi plane; weight rows are [W_hi | W_lo]
+        sp = dict(a_split=True) if self.split else {}
+        if self.split and dst.b16 is not None:
+            sp.update(out_bf16_split=True, out_bf16_lo_offset=dst.b16[0].numel())
         if cv.window and patches is not None:
             # first layer over the packed column patches of this clip (v2a_frames_pack): windows [first, first + n) of the clip
             key = ("c1", T, first, n, H, W)
@@ -254,18 +275,21 @@ class Video2RollEngine:
                 a_row = ((ni * Wo + xo) * Hp + yo * cv.stride) * 16
                 kt = torch.arange(cv.ci * cv.g, device=dev, dtype=torch.int64)
                 a_k = (kt // cv.g) * (Wo * Hp * 16) + (kt % cv.g) * 64
-                assert int(a_row.max()) + int(a_k.max()) + 64 <= patches.numel() < 2 ** 31
+                assert int(a_row.max()) + int(a_k.max()) + 64 <= patches.numel() // (2 if self.split else 1) < 2 ** 31
                 t = self._tabs[key] = (a_row.reshape(-1).to(torch.int32).contiguous(), a_k.to(torch.int32).contiguous())
             K = cv.ci * cv.g * 64
-            L.gemm([(patches, K, K)], cv.w_pack, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
-                   relu=relu, ldo=cv.co, ldr=cv.co, a_row_offset=t[0], a_ktile_offset=t[1])
+            seg = (patches, K, K, patches.numel() // 2) if self.split else (patches, K, K)
+            L.gemm([seg], cv.w_pack, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
+                   relu=relu, ldo=cv.co, ldr=cv.co, a_row_offset=t[0], a_ktile_offset=t[1], **sp)
             return dst
         if self.implicit and not cv.window:
             a_row, a_k, o_row = self._tables(cv, src, Ho, Wo, dst.border)
             K = cv.kh * cv.kw * cv.ci
-            L.gemm([(src.b16, K, K)], cv.w, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
+            assert K == cv.Kpad, "NHWC convolutions have whole 64-element K tiles (C % 64 == 0)"
+            seg = (src.b16, K, K, src.b16[0].numel()) if self.split else (src.b16, K, K)
+            L.gemm([seg], cv.w, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
                    relu=relu, ldo=cv.co, ldr=cv.co, out_bf16=dst.b16, ld_out_bf16=cv.co,
-                   a_row_offset=a_row, a_ktile_offset=a_k, out_row_offset=o_row)
+                   a_row_offset=a_row, a_ktile_offset=a_k, out_row_offset=o_row, **sp)
             return dst
         # explicit patch matrix
         assert dst.border == 0 or cv.window is False
@@ -285,6 +309,10 @@ class Video2RollEngine:
         Ho, Wo = (src.H + 2 * pad - k) // stride + 1, (src.W + 2 * pad - k) // stride + 1
         if dst is None:
             dst = self._map(dst_name, src.n, Ho, Wo, src.C, border, shadow)
+        if self.split and dst.b16 is not None:
+            L.pool2d_split(src.f32, dst.f32, dst.b16, lo_offset=dst.b16[0].numel(), B=src.n, H=src.H, W=src.W, C_=src.C, k=k,
+                           stride=stride, pad=pad, mode=mode, Ho=Ho, Wo=Wo, in_border=src.border, out_border=dst.border)
+            return dst
         L.pool2d(src.f32, dst.f32, B=src.n, H=src.H, W=src.W, C_=src.C, k=k, stride=stride, pad=pad, mode=mode, Ho=Ho, Wo=Wo,
                  out_bf16=dst.b16, in_border=src.border, out_border=dst.border)
         return dst
@@ -353,14 +381,19 @@ class Video2RollEngine:
         return hb, P
 
     def _pack(self, clip_frames, T, H, W):
-        """bf16 column patches of one clip for the implicit first layer (v2a_frames_pack)."""
+        """bf16 column patches of one clip for the implicit first layer (v2a_frames_pack); bf16x3: hi | lo planes, one after
+        the other (v2a_frames_pack_split)."""
         cv = self.convs["conv1"]
         _, Wo = cv.out_hw(H, W)
-        key = ("patches", T, H, W)
+        key = ("patches", T, H, W, self.split)
+        plane = (T + 4) * Wo * (H + 2 * cv.pad) * 16
         buf = self._maps.get(key)
         if buf is None:
-            buf = self._maps[key] = torch.empty((T + 4) * Wo * (H + 2 * cv.pad) * 16, device=self.dev, dtype=torch.bfloat16)
-        L.frames_pack(clip_frames, buf, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
+            buf = self._maps[key] = torch.empty(plane * (2 if self.split else 1), device=self.dev, dtype=torch.bfloat16)
+        if self.split:
+            L.frames_pack_split(clip_frames, buf, lo_offset=plane, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
+        else:
+            L.frames_pack(clip_frames, buf, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
         return buf
 
     def _run(self, frames, T, sigmoid, windows=None, taps=None):
