@@ -70,7 +70,9 @@ enum {
   V2A_EPI_GEGLU = 2,      /* W rows packed [16 value | 16 gate] per 16 outputs:
                              out[m][j] = (acc_v + b_v) * gelu_erf(acc_g + b_g); out has N/2 cols */
   V2A_EPI_RESID = 3,      /* out = resid + acc + bias             (text/frames streams, cross-condition) */
-  V2A_EPI_GATE_RESID = 4  /* out = resid + gate[n] * (acc + bias) (AdaLNZero x3:546-551 + residual x3:1128) */
+  V2A_EPI_GATE_RESID = 4, /* out = resid + gate[n] * (acc + bias) (AdaLNZero x3:546-551 + residual x3:1128) */
+  V2A_EPI_GEGLU_TANH = 5  /* v2a_gemm_skinny_f32 only (v2a_gemm rejects it): the GEGLU row packing with value = wi_1, gate = wi_0,
+                             out[m][j] = (acc_v + b_v) * gelu_new(acc_g + b_g), gelu_new(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) */
 };
 
 typedef struct v2a_gemm_args {
@@ -431,6 +433,45 @@ int v2a_lstm_layer(const float* gates_x, const float* w_hh, float* h, const floa
  * workspace = 8*H + 2 int32, 8-byte aligned (zeroed by the call; workspace[8*H] != 0 afterwards = a workgroup timed out). */
 int v2a_lstm2(const float* gates_x0, const float* w_hh0, const float* w_ih1, const float* bias1, const float* w_hh1,
               const float* resid, float* y, int32_t T, int32_t H, int32_t* workspace, v2a_stream_t stream);
+
+/* =======================================================================================
+ * FLAN-T5 prompt encoder: `E2TTS.encode_text` x3:1648-1657 running transformers `T5EncoderModel` (x3:1413, 1654), fp32.
+ * Per block: h += o(Attn(LN1(h))); h += wo(gelu_new(wi_0 LN2(h)) * wi_1 LN2(h)); then final_layer_norm.
+ * ===================================================================================== */
+
+/* T5LayerNorm: y[m] = w * x[m] * rsqrt(mean(x[m]^2) + eps), fp32, d % 4 == 0, 16-byte aligned rows.
+ * With ids != NULL row m of x is the embedding row ids[m] of the table x (vocab rows, row stride ldx) and is also written to
+ * resid[m] (the residual stream): the embedding gather of T5Stack fused into the first LN.  The caller validates the ids.
+ * Replaces: transformers T5LayerNorm (LN1, LN2, final_layer_norm) and the embed_tokens lookup, reached from x3:1413,1654. */
+int v2a_t5_rmsnorm(const float* x, int64_t ldx, const int32_t* ids, int32_t vocab, float* resid, int64_t ldr, float* y, int64_t ldy,
+                   int64_t rows, int32_t d, const float* w, float eps, v2a_stream_t stream);
+
+/* T5Attention core (d_kv = 64, N <= 512), fp32 VALU with an online softmax over 64-key blocks:
+ *   s[b,h,i,j] = q[b,i,h,:] . k[b,j,h,:] + bias[h][j - i + N - 1]      (no 1/sqrt(d) scale)
+ *   o[b,i,h,:] = softmax_j(s | key_mask[b][j] != 0) v[b,j,h,:]          for every row i, padded rows included
+ * q/k/v/out are addressed as base + b*batch_stride + token*row_stride + h*64 (+c), so q, k, v are read in place from the fused
+ * [q | k | v] GEMM output.  bias is the relative-position bias gathered per call from the bucket table and the
+ * relative_attention_bias embedding (num_buckets x H) of block 0.  A batch row with no valid key is the caller's error (it gets 0).
+ * Replaces: transformers T5Attention minus its Linears (T5LayerSelfAttention), reached from x3:1413,1654. */
+typedef struct v2a_t5_attn_args {
+  const float *q, *k, *v;
+  float* out;
+  int64_t q_row_stride, k_row_stride, v_row_stride, out_row_stride;
+  int64_t q_batch_stride, k_batch_stride, v_batch_stride, out_batch_stride;
+  int32_t B, H, N, d_kv;
+  const float* bias;        /* [H][2N - 1] */
+  const int32_t* key_mask;  /* [B][N], 0 / 1 */
+} v2a_t5_attn_args;
+int v2a_t5_attention(const v2a_t5_attn_args* args, v2a_stream_t stream);
+
+/* Exact-fp32 GEMM for few rows (the encoder at B*N <= 128 rows streams 51 MB of fp32 weights per block): a subset of
+ * v2a_gemm_args -- nseg 1, a_dtype / compute_dtype / out_dtype V2A_F32, K % 32 == 0, 16-byte aligned A / W rows, M <= 8192 --
+ * and the epilogues STORE (N % 16 == 0), RESID (resid may alias out) and GEGLU_TANH (N % 32 == 0, out has N/2 columns).  Each
+ * workgroup owns 16 output columns (32 packed rows for GEGLU_TANH) and its 8 waves split K; the partial sums are added in a fixed
+ * order, so the result is the same bits on every run and for every M.  v2a_gemm's dispatch is unaffected.
+ * Replaces: the Linears of transformers T5Attention (fused q|k|v, o) and T5DenseGatedActDense (wi_0 | wi_1, wo) with the
+ * residual add of T5LayerSelfAttention / T5LayerFF, reached from x3:1413,1654. */
+int v2a_gemm_skinny_f32(const v2a_gemm_args* args, v2a_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 F32, BF16, BF16_SPLIT = 0, 1, 2
 EPI_STORE, EPI_SIGMOID, EPI_GEGLU, EPI_RESID, EPI_GATE_RESID = 0, 1, 2, 3, 4
+EPI_GEGLU_TANH = 5           # v2a_gemm_skinny_f32 only
 
 _lib = None
 
@@ -77,6 +78,17 @@ class AttnArgs(C.Structure):
     ]
 
 
+class T5AttnArgs(C.Structure):
+    """Mirror of `v2a_t5_attn_args`."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+        ("q_row_stride", C.c_int64), ("k_row_stride", C.c_int64), ("v_row_stride", C.c_int64), ("out_row_stride", C.c_int64),
+        ("q_batch_stride", C.c_int64), ("k_batch_stride", C.c_int64), ("v_batch_stride", C.c_int64), ("out_batch_stride", C.c_int64),
+        ("B", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("d_kv", C.c_int32),
+        ("bias", C.c_void_p), ("key_mask", C.c_void_p),
+    ]
+
+
 class RollHeadArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x2", "x3", "x4", "x5")] + [("B", C.c_int32), ("P", C.c_int32)] +
                 [(f"frb{i}_{n}", C.c_void_p) for i in (4, 3, 2) for n in ("w1t", "b1", "w2t", "b2")] +
@@ -89,7 +101,7 @@ EXPORTS = [
     "v2a_rope_inplace", "v2a_attention", "v2a_qproj_xattn", "v2a_linear_small", "v2a_fill_registers", "v2a_time_cond",
     "v2a_apg_reduce", "v2a_cfg_euler", "v2a_step_advance", "v2a_cast_bf16", "v2a_split_bf16",
     "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand", "v2a_frames_pack_split", "v2a_pool2d_split",
-    "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2",
+    "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2", "v2a_t5_rmsnorm", "v2a_t5_attention", "v2a_gemm_skinny_f32",
 ]
 
 
@@ -141,6 +153,9 @@ def _declare(lib):
     lib.v2a_elu_pad.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
     lib.v2a_lstm_layer.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp]
     lib.v2a_lstm2.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.v2a_t5_rmsnorm.argtypes = [vp, i64, vp, i32, vp, i64, vp, i64, i64, i32, vp, f32, vp]
+    lib.v2a_t5_attention.argtypes = [C.POINTER(T5AttnArgs), vp]
+    lib.v2a_gemm_skinny_f32.argtypes = [C.POINTER(GemmArgs), vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -275,7 +290,7 @@ def _launch(key, flops, nbytes, call):
         _prof.launch(key, flops, nbytes, lambda: check(call()))
 
 
-_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid"}
+_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh"}
 
 
 # ------------------------------------------------------------------------------------------
@@ -550,3 +565,43 @@ def lstm2(gates_x0, w_hh0, w_ih1, bias1, w_hh1, y, workspace, *, T, H, resid=Non
     _launch("lstm2", 2.0 * T * 4 * H * H * 3, 4.0 * T * 6 * H,
             lambda: lib().v2a_lstm2(gates_x0.data_ptr(), w_hh0.data_ptr(), w_ih1.data_ptr(), bias1.data_ptr(), w_hh1.data_ptr(),
                                     _p(resid), y.data_ptr(), T, H, workspace.data_ptr(), stream_ptr()))
+
+
+# ---- FLAN-T5 prompt encoder (t5.py) ------------------------------------------------------------
+def t5_rmsnorm(x, y, w, *, rows, d, eps, ids=None, vocab=0, resid=None, ldx=None, ldy=None):
+    """T5LayerNorm of `rows` rows; with ids, x is the embedding table and the gathered rows also go to resid."""
+    _launch("t5_rmsnorm%s" % ("+gather" if ids is not None else ""), 0.0, rows * d * (12 if ids is not None else 8),
+            lambda: lib().v2a_t5_rmsnorm(x.data_ptr(), ldx or d, _p(ids), vocab, _p(resid), d, y.data_ptr(), ldy or d, rows, d,
+                                         w.data_ptr(), float(eps), stream_ptr()))
+
+
+def t5_attention(qkv, out, bias, key_mask, *, B, H, N, inner):
+    """q | k | v read in place from the fused (B*N, 3*inner) GEMM output; out (B*N, inner)."""
+    a = T5AttnArgs()
+    base, ld = qkv.data_ptr(), qkv.stride(0)
+    a.q, a.k, a.v, a.out = base, base + 4 * inner, base + 8 * inner, out.data_ptr()
+    a.q_row_stride = a.k_row_stride = a.v_row_stride = ld
+    a.out_row_stride = out.stride(0)
+    a.q_batch_stride = a.k_batch_stride = a.v_batch_stride = N * ld
+    a.out_batch_stride = N * out.stride(0)
+    a.B, a.H, a.N, a.d_kv = B, H, N, 64
+    a.bias, a.key_mask = bias.data_ptr(), key_mask.data_ptr()
+    _launch("t5_attention", 4.0 * B * H * N * N * 64, 4.0 * B * N * (4 * inner),
+            lambda: lib().v2a_t5_attention(C.byref(a), stream_ptr()))
+
+
+def gemm_skinny(a, w, out, *, M, N, K, epilogue=EPI_STORE, resid=None, bias=None):
+    """One v2a_gemm_skinny_f32 launch: a (M, K) fp32 rows, w [N][K] fp32, out (M, N) (GEGLU_TANH: (M, N/2))."""
+    g = GemmArgs()
+    g.a[0], g.lda[0], g.ka[0], g.nseg = a.data_ptr(), a.stride(0), K, 1
+    g.a_dtype = g.compute_dtype = g.out_dtype = F32
+    g.w, g.ldw = w.data_ptr(), w.stride(0)
+    g.bias = _p(bias)
+    g.M, g.N, g.epilogue = M, N, epilogue
+    g.out, g.ldo = out.data_ptr(), out.stride(0)
+    g.resid, g.ldr = _p(resid), (resid.stride(0) if resid is not None else 0)
+    key = "gemm_skinny<f32,%s>" % _EPI_NAMES[epilogue]
+    if _prof is not None and _prof.shapes:
+        key += " %dx%dx%d" % (M, N, K)
+    nbytes = 4.0 * (M * K + N * K + M * (N // 2 if epilogue == EPI_GEGLU_TANH else N) * (2 if resid is not None else 1))
+    _launch(key, 2.0 * M * N * K, nbytes, lambda: lib().v2a_gemm_skinny_f32(C.byref(g), stream_ptr()))

@@ -11,6 +11,7 @@ FLAN-T5 context `<video>.t5.npz` (arr_0 = (nc, 1024) hidden states) unless `--t5
 local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec latent that the reference feeds to
 `vocos.decode` (src/inference_v2a.py / predict.py:277-278).
 
+  --t5-engine hip    run --t5 on the HIP FLAN-T5 encoder (t5.py) of this rank's GPU instead of transformers on the CPU
   --piano            V2P (src/inference_v2p.py): the cached grey frames `<video>.generated_frames_raw.2.npz` (features.py) go
                      through the HIP Video2Roll encoder; the checkpoint must hold `video2roll_net.*`
   --encodec STATE    torch-saved state dict of `EncodecModel.from_pretrained("facebook/encodec_24khz")` (or of its decoder):
@@ -60,7 +61,7 @@ def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None):
     return reqs
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("ckpt")
     ap.add_argument("drop_prompt", type=int)
@@ -79,6 +80,8 @@ def main(argv=None):
                     "durations vary per clip, and every new shape costs a plan and a hipGraph capture")
     ap.add_argument("--bucket-ctx", type=int, default=16, help="pad the T5 context to a multiple of this many tokens (0 = exact)")
     ap.add_argument("--t5", default=None, help="local FLAN-T5 directory (reference: ./ckpts/flan-t5-large)")
+    ap.add_argument("--t5-engine", default="torch", choices=["torch", "hip"],
+                    help="what runs --t5: stock transformers on the CPU (torch) or the HIP T5Encoder on this rank's GPU (hip)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the cached piano frames through the Video2Roll encoder")
@@ -86,7 +89,11 @@ def main(argv=None):
                     help="compute mode of the Video2Roll encoder behind --piano (default: bf16 under --dtype bf16, else fp32); bf16x3: "
                          "split-bf16 implicit GEMM inside 1e-4 of the reference probabilities")
     ap.add_argument("--encodec", default=None, help="state dict (.pt) of the Encodec model / decoder: also write <name>.wav")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
 
     import torch.distributed as dist
     from . import E2TTS, collate_clips, gather_latents, shard_range
@@ -108,7 +115,12 @@ def main(argv=None):
     if res.missing_keys:
         raise RuntimeError(f"checkpoint lacks {len(res.missing_keys)} parameters of the sampled path, e.g. {res.missing_keys[0]}")
     t5_encode = None
-    if a.t5:
+    if a.t5 and a.t5_engine == "hip":
+        from .t5 import T5Encoder
+        enc = T5Encoder.from_pretrained(a.t5, torch.device("cuda", local))
+        def t5_encode(prompt):
+            return enc([prompt])[0][0].cpu()
+    elif a.t5:
         from transformers import AutoTokenizer, T5EncoderModel
         tok, enc = AutoTokenizer.from_pretrained(a.t5), T5EncoderModel.from_pretrained(a.t5).eval()
         def t5_encode(prompt):

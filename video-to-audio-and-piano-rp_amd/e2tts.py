@@ -209,6 +209,7 @@ class E2TTS:
         self._sd: dict[str, torch.Tensor] = {}
         self._engine: DiTEngine | None = None
         self._v2r_sd, self._v2r = None, None      # optional Video2Roll frame encoder (video2roll_net.*, x3:1523)
+        self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
         L.lib()  # no library -> no sampler
 
     # ---- nn.Module-like surface used by the callers (predict.py:156-170) -------------------
@@ -293,14 +294,40 @@ class E2TTS:
             self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute)
         return self._v2r.encode_frames(x, l)
 
-    def _get_context(self, prompt, context, context_mask, b):
+    def load_text_encoder(self, src, tokenizer=None):
+        """The FLAN-T5 prompt encoder behind `prompt=` (x3:1412-1413): a `T5Encoder`, a local HF directory
+        (./ckpts/flan-t5-large) or a state dict (T5EncoderModel keys, or a reference checkpoint with `text_encoder2.*`).
+        A `text_encoder_fn` given to the constructor still takes precedence."""
+        from .t5 import T5Encoder
+        if isinstance(src, T5Encoder):
+            enc = src
+            if tokenizer is not None:
+                enc.tokenizer = tokenizer
+        elif isinstance(src, (str, Path)):
+            enc = T5Encoder.from_pretrained(str(src), self._device)
+            if tokenizer is not None:
+                enc.tokenizer = tokenizer
+        elif isinstance(src, dict):
+            enc = T5Encoder(src, self._device, tokenizer=tokenizer)
+        else:
+            raise TypeError(f"load_text_encoder: a T5Encoder, a directory or a state dict, got {type(src).__name__}")
+        self._t5 = enc
+        return enc
+
+    def _get_context(self, prompt, context, context_mask, b, video_drop_prompt=None):
         if context is None:
             if prompt is None:
                 raise ValueError("pass `prompt` (with text_encoder_fn) or precomputed `context`/`context_mask`")
-            if self.text_encoder_fn is None:
+            if self.text_encoder_fn is not None:
+                context, context_mask = self.text_encoder_fn(list(prompt))     # encode_text x3:1648-1657
+            elif getattr(self, "_t5", None) is not None:
+                prompts = list(prompt)
+                if video_drop_prompt is not None:              # x3:2053-2057 (the reference rewrites the caller's list in place)
+                    prompts = ["the sound of X X" if video_drop_prompt[i] else p for i, p in enumerate(prompts)]
+                context, context_mask = self._t5(prompts)      # encode_text x3:1648-1657, once per call
+            else:
                 raise NotImplementedError("FLAN-T5 encoding is outside the accelerated path (SURVEY 8): supply "
                                           "`context`/`context_mask` or construct with text_encoder_fn=")
-            context, context_mask = self.text_encoder_fn(list(prompt))     # encode_text x3:1648-1657
         if context_mask is None:
             context_mask = torch.ones(context.shape[:2], dtype=torch.bool)
         assert context.shape[0] == b
@@ -323,7 +350,7 @@ class E2TTS:
         b, n, _ = x.shape
         dtc, dtp = bool(drop_text_cond), bool(drop_text_prompt)
         eng = self.engine()
-        context, context_mask = self._get_context(prompt, context, context_mask, b)
+        context, context_mask = self._get_context(prompt, context, context_mask, b, video_drop_prompt)
         times = torch.as_tensor(times, dtype=torch.float32)
         if times.ndim == 0:
             times = times.repeat(b)
@@ -450,7 +477,7 @@ class E2TTS:
                     step_cond[i] = 0
         elif n != cond_seq_len:
             raise ValueError(f"cond has {cond_seq_len} frames but the longest duration is {n}")
-        context, context_mask = self._get_context(prompt, context, context_mask, batch)
+        context, context_mask = self._get_context(prompt, context, context_mask, batch, video_drop_prompt)
         drop_ctx = [bool(video_drop_prompt is not None and video_drop_prompt[i]) for i in range(batch)]
         # -- grid (x3:2250-2252) and noise (x3:2248)
         t = sway_grid(steps, sway_sampling)

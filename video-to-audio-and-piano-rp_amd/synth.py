@@ -139,3 +139,40 @@ def random_encodec_decoder_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
             v = 0.05 * rs.standard_normal(shp)
         sd[k] = torch.from_numpy(v.astype(np.float32))
     return sd
+
+
+FLAN_T5_LARGE = dict(vocab_size=32128, d_model=1024, d_kv=64, num_heads=16, d_ff=2816, num_layers=24, relative_attention_num_buckets=32,
+                     relative_attention_max_distance=128, layer_norm_epsilon=1e-6)
+
+
+def random_t5_encoder_state_dict(config: dict, seed: int = 0, amplify: float = 1.0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `T5EncoderModel(T5Config(**config, feed_forward_proj="gated-gelu"))` (the flan-t5-large
+    checkpoint the reference loads from ./ckpts/flan-t5-large, x3:1412-1413, is not reachable offline).  numpy RandomState stream:
+    the same tensors on any machine.  q is scaled like T5's own init (no 1/sqrt(d_kv) in the attention) so the scores stay
+    O(1); `amplify` multiplies the o and wo projections, which makes the residual stream grow to |h| ~ 1e2 - 1e3 by the last block
+    (FLAN-T5's large residual activations) instead of staying O(1)."""
+    import numpy as np
+
+    c = dict(config)
+    d, H, dkv, dff, nl, V = c["d_model"], c["num_heads"], c["d_kv"], c["d_ff"], c["num_layers"], c["vocab_size"]
+    inner = H * dkv
+    rs = np.random.RandomState(seed)
+    t = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32))
+    nrm = lambda shp, s: t(rs.standard_normal(shp) * s)
+    sd = {"shared.weight": nrm((V, d), 1.0)}
+    sd["encoder.embed_tokens.weight"] = sd["shared.weight"]
+    for i in range(nl):
+        P = f"encoder.block.{i}.layer."
+        sd[P + "0.SelfAttention.q.weight"] = nrm((inner, d), 1.5 / math.sqrt(d * dkv))
+        sd[P + "0.SelfAttention.k.weight"] = nrm((inner, d), 1.0 / math.sqrt(d))
+        sd[P + "0.SelfAttention.v.weight"] = nrm((inner, d), 1.0 / math.sqrt(d))
+        sd[P + "0.SelfAttention.o.weight"] = nrm((d, inner), amplify / math.sqrt(inner))
+        if i == 0:
+            sd[P + "0.SelfAttention.relative_attention_bias.weight"] = nrm((c["relative_attention_num_buckets"], H), 1.0)
+        sd[P + "0.layer_norm.weight"] = t(1.0 + 0.1 * rs.standard_normal(d))
+        sd[P + "1.DenseReluDense.wi_0.weight"] = nrm((dff, d), 1.0 / math.sqrt(d))
+        sd[P + "1.DenseReluDense.wi_1.weight"] = nrm((dff, d), 1.0 / math.sqrt(d))
+        sd[P + "1.DenseReluDense.wo.weight"] = nrm((d, dff), amplify / math.sqrt(dff))
+        sd[P + "1.layer_norm.weight"] = t(1.0 + 0.1 * rs.standard_normal(d))
+    sd["encoder.final_layer_norm.weight"] = t(1.0 + 0.1 * rs.standard_normal(d))
+    return sd
