@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
 
 import torch
 
@@ -212,6 +213,23 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+class Operand(NamedTuple):
+    """A GEMM A segment, or the destination of a bf16 shadow: `t` is the view at the hi plane of row 0, `ld` the row stride in
+    elements, `k` the logical K (columns), `lo` the distance from a row's hi plane to its lo plane in the split layout (0: k,
+    as in the C ABI).  gemm() takes these wherever it takes (t, lda, k[, lo]) tuples."""
+    t: torch.Tensor
+    ld: int
+    k: int
+    lo: int = 0
+
+
+def split_planes(w):
+    """fp32 rows -> [hi | lo] bf16 rows (V2A_BF16_SPLIT): hi = bf16(w), lo = bf16(w - hi)."""
+    w = w.float()
+    hi = w.bfloat16()
+    return torch.cat([hi, (w - hi.float()).bfloat16()], 1)
+
+
 # ---- optional per-launch timing (bench.py roofline leg): HIP events on the launch stream ----
 _prof = None
 
@@ -309,22 +327,18 @@ def gemm_args(a_segs, w, out, *, M, N, compute, epilogue=EPI_STORE, bias=None, r
          a_row_offset=None, a_ktile_offset=None, out_row_offset=None, tile_hint=0,
          norm_gamma=None, norm_step_stride=0, norm_batch_stride=0, norm_switch_row=0, norm_switch_offset=0, norm_ssq=None,
          row_ssq=None, row_norm_dim=0, out_bf16_split=False, a_split=False, out_split=False, out_bf16_lo_offset=0):
-    """a_segs: list of (tensor_or_ptr_view, lda, k).  w: [N][K] tensor in the compute dtype.
-    a_split: the segments are V2A_BF16_SPLIT rows ([hi k | lo k], lda >= 2k; a segment may be a 4-tuple whose last element is the offset of its
-    lo plane when that is not k: v2a_gemm_args.a_lo_offset) and w is [N][2K] = [W_hi | W_lo] (the bf16x3 mode's native
+    """a_segs: list of Operand records or (tensor, lda, k[, lo]) tuples.  w: [N][K] tensor in the compute dtype.
+    a_split: the segments are V2A_BF16_SPLIT rows ([hi k | lo k], lda >= 2k, or the lo plane `lo` elements after the hi one:
+    v2a_gemm_args.a_lo_offset) and w is [N][2K] = [W_hi | W_lo] (the bf16x3 mode's native
     GEMM: three MFMA products per fp32 product); out_split: GEGLU output as hi | lo planes; out_bf16_split: the shadow likewise.
     Folded RMSNorm (v2a_gemm_args): producer -- norm_gamma (+ strides / switch) scales the out_bf16 shadow, norm_ssq (rows, N/32)
     receives the sums of squares; consumer -- row_ssq (rows, parts) of its A rows and row_norm_dim = their width."""
     g = GemmArgs()
-    for i, seg in enumerate(a_segs):
-        t, lda, k = seg[:3]
-        g.a[i] = t.data_ptr()
-        g.lda[i] = lda
-        g.ka[i] = k
-        g.a_lo_offset[i] = seg[3] if len(seg) > 3 else 0
-    a_segs = [seg[:3] for seg in a_segs]
+    a_segs = [Operand(*seg) for seg in a_segs]
+    for i, s in enumerate(a_segs):
+        g.a[i], g.lda[i], g.ka[i], g.a_lo_offset[i] = s.t.data_ptr(), s.ld, s.k, s.lo
     g.nseg = len(a_segs)
-    g.a_dtype = BF16_SPLIT if a_split else dt_code(a_segs[0][0].dtype)
+    g.a_dtype = BF16_SPLIT if a_split else dt_code(a_segs[0].t.dtype)
     g.w = w.data_ptr()
     g.ldw = w.stride(0)
     g.bias = _p(bias)
@@ -359,7 +373,7 @@ def gemm_args(a_segs, w, out, *, M, N, compute, epilogue=EPI_STORE, bias=None, r
     g.row_norm_dim = row_norm_dim
     g.out_bf16_split = 1 if out_bf16_split else 0
     g.out_bf16_lo_offset = out_bf16_lo_offset
-    K = sum(k for _, _, k in a_segs)
+    K = sum(s.k for s in a_segs)
     key = "gemm<%s,%s,%s,%s>" % ("bf16" if compute == BF16 else "f32", "a_f32" if g.a_dtype == F32 else ("a_split" if a_split else "a_bf16"),
                                  _EPI_NAMES[epilogue], "f32" if g.out_dtype == F32 else "bf16")
     esz = 2 if compute == BF16 else 4

@@ -26,6 +26,7 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 from dataclasses import dataclass, asdict
+from typing import NamedTuple
 
 import torch
 
@@ -65,17 +66,31 @@ def _ru(x, m):
     return (x + m - 1) // m * m
 
 
-def pack_weight(w, dev, cd, split=False, ksegs=None):
+class _Stream(NamedTuple):
+    """An fp32 residual-stream buffer (Bt, N, d) and its GEMM operand copy (None in fp32 mode)."""
+    x: torch.Tensor
+    sh: L.Operand | None
+
+    @property
+    def op(self):
+        """The GEMM A operand of the stream: its copy, or the fp32 rows themselves in fp32 mode."""
+        return self.sh if self.sh is not None else L.Operand(self.x, self.x.shape[-1], self.x.shape[-1])
+
+
+class _Wide(NamedTuple):
+    """Operand records of one [x | skip] buffer (DiTEngine.setup): the whole of it, its x half and its skip half."""
+    whole: L.Operand
+    x: L.Operand
+    skip: L.Operand
+
+
+def pack_weight(w, dev, cd, split=False):
     """nn.Linear weight [N][K] -> device operand.  Plain modes: one tensor in the compute dtype.  split (bf16x3 mode): [N][2K] bf16 =
-    [W_hi | W_lo] with W_hi = bf16(W), W_lo = bf16(W - W_hi): against A rows [A_hi | A_lo] the split GEMM (v2a_gemm, a_dtype
-    V2A_BF16_SPLIT) sums A_lo W_hi + A_hi W_lo + A_hi W_hi in fp32 per K step, over all logical K segments in one launch (`ksegs` is
-    kept for the callers' documentation of the concatenated inputs; the layout does not depend on it)."""
-    w = w.float()
+    [W_hi | W_lo] (L.split_planes): against A rows [A_hi | A_lo] the split GEMM (v2a_gemm, a_dtype V2A_BF16_SPLIT) sums
+    A_lo W_hi + A_hi W_lo + A_hi W_hi in fp32 per K step, over all logical K segments in one launch."""
     if not split:
-        return w.to(dev, cd).contiguous()
-    hi = w.bfloat16()
-    lo = (w - hi.float()).bfloat16()
-    return torch.cat([hi, lo], 1).contiguous().to(dev)
+        return w.float().to(dev, cd).contiguous()
+    return L.split_planes(w).contiguous().to(dev)
 
 
 class _Attn:
@@ -129,7 +144,7 @@ class PackedWeights:
 
     def __init__(self, cfg: DiTConfig, sd: dict, dev, cd: torch.dtype, split: bool = False):
         c = cfg
-        pk = lambda w, ksegs=None: pack_weight(w, dev, cd, split, ksegs)
+        pk = lambda w: pack_weight(w, dev, cd, split)
         T = "transformer"
         f32 = lambda k: sd[k].float().to(dev).contiguous()
         self.pos_emb = f32(f"{T}.abs_pos_emb.weight")
@@ -159,7 +174,7 @@ class PackedWeights:
             P = f"{T}.layers.{i}"
             ly = {}
             if i >= c.depth // 2:
-                ly["skip"] = pk(sd[f"{P}.0.0.weight"], [c.dim, c.dim])
+                ly["skip"] = pk(sd[f"{P}.0.0.weight"])
                 if cd == torch.bfloat16:
                     # cross-condition and U-Net skip of the second half as ONE GEMM (bf16 mode, and since round 5 bf16x3: both Linears are bias-free):
                     #   skip_proj(cat(x + W1 [x; t; f], s)) = Ws_x (I + W1_a) x + Ws_s s + (Ws_x W1_t) t + (Ws_x W1_f) f
@@ -169,7 +184,7 @@ class PackedWeights:
                     w1 = sd[f"{P}.1.5.text_frames_to_audio.weight"].double()
                     wsx, wss = ws[:, :c.dim], ws[:, c.dim:]
                     fused = torch.cat([wsx @ w1[:, :c.dim] + wsx, wss, wsx @ w1[:, c.dim:c.dim + c.dim_text], wsx @ w1[:, c.dim + c.dim_text:]], 1)
-                    ly["x_skip"] = pk(fused.float(), [2 * c.dim, c.dim_text, c.dim_frames])
+                    ly["x_skip"] = pk(fused.float())
             ly["a_conv"] = _Conv(sd, f"{P}.0.1", dev)
             ly["a_attn"] = _Attn(sd, f"{P}.0.3", c.dim, c.heads, c.dim_head, cd, dev, split=split)
             ly["a_attn2"] = _Attn(sd, f"{P}.0.6", c.dim, c.heads, c.dim_head, cd, dev, cross=True, split=split)
@@ -184,10 +199,10 @@ class PackedWeights:
             ly["t_attn"] = _Attn(sd, f"{P}.1.2", c.dim_text, c.heads, c.dim_head, cd, dev, split=split)
             ly["t_g2"] = f32(f"{P}.1.3.g")
             ly["t_ff"] = _FF(sd, f"{P}.1.4", c.dim_text, cd, dev, split)
-            ly["x_tfa"] = pk(sd[f"{P}.1.5.text_frames_to_audio.weight"], [c.dim, c.dim_text, c.dim_frames])
+            ly["x_tfa"] = pk(sd[f"{P}.1.5.text_frames_to_audio.weight"])
             if i != c.depth - 1:
-                ly["x_at"] = pk(sd[f"{P}.1.5.audio_to_text.weight"], [c.dim, c.dim_text])
-                ly["x_af"] = pk(sd[f"{P}.1.5.audio_to_frames.weight"], [c.dim, c.dim_frames])
+                ly["x_at"] = pk(sd[f"{P}.1.5.audio_to_text.weight"])
+                ly["x_af"] = pk(sd[f"{P}.1.5.audio_to_frames.weight"])
             ly["f_conv"] = _Conv(sd, f"{P}.2.0", dev)
             ly["f_g1"] = f32(f"{P}.2.1.g")
             ly["f_attn"] = _Attn(sd, f"{P}.2.2", c.dim_frames, c.frames_heads, c.dim_head, cd, dev, split=split)
@@ -359,12 +374,27 @@ class DiTEngine:
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
         p = dict(key=key, B=B, Bt=Bt, T=T, N=N, nc=nc, S=S, rows=rows, cfg_mode=cfg_mode, graphs={})
         D, Dt, Df = c.dim, c.dim_text, c.dim_frames
-        p["xA"], p["xB"], p["xS"] = e(Bt, N, D), e(Bt, N, D), e(Bt, N, D)
-        p["skips"] = [e(Bt, N, D) for _ in range(c.depth // 2)]
-        p["tA"], p["tB"], p["t0"], p["tL0"] = e(Bt, N, Dt), e(Bt, N, Dt), e(Bt, N, Dt), e(Bt, N, Dt)
-        p["fA"], p["fB"], p["f0"], p["fL0"] = e(Bt, N, Df), e(Bt, N, Df), e(Bt, N, Df), e(Bt, N, Df)
-        W0 = self.W.layers[0]
         w2 = 2 if self.split else 1           # split operand buffers hold hi | lo planes
+        bf = cd == torch.bfloat16
+
+        def stream(d):
+            """A residual-stream buffer with its bf16 operand copy, written by the producing GEMM epilogues: the operand of the
+            cross-condition / skip GEMMs, so that those run on the LDS-DMA bf16 kernel too."""
+            return _Stream(e(Bt, N, d), L.Operand(e(Bt, N, w2 * d, dt=cd), w2 * d, d) if bf else None)
+
+        # [x entering layer depth-1-j | skip j] as one 2048-wide operand buffer per skip: the fused cross-condition + skip GEMM
+        # reads both halves as ONE K segment; the halves are written by the FF2 epilogue of layer depth-2-j (x's copy) and by
+        # the cross-condition epilogue of layer j (skip j's copy).  bf16x3: rows are [x_hi | s_hi | x_lo | s_lo] -- the lo plane
+        # of either half lies 2 D further, not D (v2a_gemm_args.a_lo_offset / out_bf16_lo_offset), so that the buffer is a
+        # K = 2 D split segment as a whole and a K = D one half by half
+        ld, lo = w2 * 2 * D, 2 * D if self.split else 0
+        wide = [e(Bt, N, ld, dt=cd) for _ in range(c.depth // 2)] if bf else []
+        p["wide"] = [_Wide(L.Operand(w, ld, 2 * D, lo), L.Operand(w[..., :D], ld, D, lo), L.Operand(w[..., D:2 * D], ld, D, lo)) for w in wide]
+        p["skips"] = [_Stream(e(Bt, N, D), p["wide"][j].skip if bf else None) for j in range(c.depth // 2)]
+        p["xA"], p["xB"], p["xS"] = stream(D), stream(D), e(Bt, N, D)
+        p["tA"], p["tB"], p["t0"], p["tL0"] = stream(Dt), stream(Dt), e(Bt, N, Dt), stream(Dt)
+        p["fA"], p["fB"], p["f0"], p["fL0"] = stream(Df), stream(Df), e(Bt, N, Df), stream(Df)
+        W0 = self.W.layers[0]
         for s, d, attn, ff in (("a", D, W0["a_attn"], W0["a_ff"]), ("t", Dt, W0["t_attn"], W0["t_ff"]),
                                ("f", Df, W0["f_attn"], W0["f_ff"])):
             p[f"hn_{s}"] = e(rows, w2 * d, dt=cd)
@@ -373,25 +403,6 @@ class DiTEngine:
             p[f"qkv_{s}"] = e(rows, attn.n_pad, dt=self.ad)
             p[f"ao_{s}"] = e(rows, w2 * attn.inner, dt=cd)
             p[f"ffh_{s}"] = e(rows, w2 * ff.inner, dt=cd)
-        # bf16 shadows of the fp32 residual streams (written by the producing GEMM epilogues): the
-        # operands of the cross-condition / skip GEMMs, so those run on the LDS-DMA bf16 kernel too
-        p["shadow"] = {}
-        p["lo_off"] = {}            # bf16x3: split operand views whose lo plane is NOT k elements behind the hi plane (by data pointer)
-        if cd == torch.bfloat16:
-            mk = lambda t: torch.empty(*t.shape[:-1], w2 * t.shape[-1], dtype=cd, device=dev)
-            for name in ("xA", "xB", "tA", "tB", "tL0", "fA", "fB", "fL0"):
-                p["shadow"][p[name].data_ptr()] = mk(p[name])
-            # [x entering layer depth-1-j | skip j] as one 2048-wide operand buffer per skip: the fused cross-condition +
-            # skip GEMM reads both halves as ONE K segment; the halves are written by the FF2 epilogue of layer
-            # depth-2-j (x's shadow) and by the cross-condition epilogue of layer j (skip j's shadow).  bf16x3: rows are
-            # [x_hi | s_hi | x_lo | s_lo] -- the lo plane of either half lies 2 D further, not D (`lo_off`: v2a_gemm_args.a_lo_offset /
-            # out_bf16_lo_offset), so that the buffer is a K = 2 D split segment as a whole and a K = D one half by half
-            p["wide"] = [torch.empty(Bt, N, w2 * 2 * D, dtype=cd, device=dev) for _ in p["skips"]]
-            for sk, wd in zip(p["skips"], p["wide"]):
-                p["shadow"][sk.data_ptr()] = wd[..., D:2 * D]
-                if self.split:
-                    p["lo_off"][wd.data_ptr()] = 2 * D                       # the whole buffer, or its x half
-                    p["lo_off"][wd[..., D:2 * D].data_ptr()] = 2 * D         # its skip half
         p["q2"] = e(B * N, W0["a_attn2"].n_pad, dt=self.ad)
         inner = c.heads * c.dim_head
         p["ctx_kv"] = e(B * nc, 2 * c.depth * inner, dt=self.ad)
@@ -439,29 +450,21 @@ class DiTEngine:
                 self.interleave_capture, self.rope_cross, self.zero_masked_queries)
 
     # --------------------------------------------------------------------------- primitives
-    def _sh(self, buf):
-        """bf16 shadow of an fp32 stream buffer (None in fp32 mode)."""
-        return self.plan["shadow"].get(buf.data_ptr())
+    def _rows(self, t):
+        """Operand record of a whole operand buffer: rows of k, or of hi k | lo k in bf16x3 mode."""
+        return L.Operand(t, t.stride(-2), t.shape[-1] // (2 if self.split else 1))
 
-    def _opnd(self, buf):
-        """GEMM A operand for a residual stream: its bf16 shadow, or the fp32 buffer itself in fp32 mode."""
-        s = self._sh(buf)
-        return buf if s is None else s
-
-    def _mm(self, segs, W, out, **kw):
-        """GEMM on logical K segments [(operand buffer, lda, k)].  Plain modes: one v2a_gemm.  bf16x3: the operand buffers hold
-        hi | lo planes (rows of 2k bf16) and W is [W_hi | W_lo]: one v2a_gemm with split operands (three MFMA products per fp32
-        product inside the kernel); a requested bf16 shadow of the result is written as hi | lo planes by the same epilogue."""
-        if kw.get("out_bf16") is not None and "ld_out_bf16" not in kw:
-            kw["ld_out_bf16"] = kw["out_bf16"].stride(-2)        # a shadow may be half of a wider operand buffer
-        if not self.split:
-            return L.gemm(segs, W, out, compute=self.cdc, **kw)
-        lo = self.plan["lo_off"]
-        segs = [(buf, buf.stride(-2), k, lo.get(buf.data_ptr(), 0)) for buf, _, k in segs]
-        if kw.get("out_bf16") is not None:
-            kw["out_bf16_split"] = True
-            kw["out_bf16_lo_offset"] = lo.get(kw["out_bf16"].data_ptr(), 0)
-        return L.gemm(segs, W, out, compute=L.BF16, a_split=True, **kw)
+    def _mm(self, segs, W, out, shadow=None, **kw):
+        """GEMM over operand records (the logical K segments); shadow: operand record that receives a bf16 copy of the result.
+        Plain modes: one v2a_gemm.  bf16x3: the operands hold hi | lo planes and W is [W_hi | W_lo]: one v2a_gemm with split
+        operands (three MFMA products per fp32 product inside the kernel); the copy is written as hi | lo planes by the same epilogue."""
+        if shadow is not None:
+            kw.update(out_bf16=shadow.t, ld_out_bf16=shadow.ld)
+            if self.split:
+                kw.update(out_bf16_split=True, out_bf16_lo_offset=shadow.lo)
+        if self.split:
+            return L.gemm(segs, W, out, compute=L.BF16, a_split=True, **kw)
+        return L.gemm(segs, W, out, compute=self.cdc, **kw)
 
     def _norm_plain(self, x, hn, rows, d, g):
         L.rmsnorm(x, hn, rows=rows, d=d, gamma=g, split=self.split)
@@ -504,16 +507,13 @@ class DiTEngine:
         return self._fold() and (self._regime() < 2 or self.fold_gemm_all)
 
     def _nprod_ada(self, layer, slot, switch_row=0):
-        """Producer side of a folded AdaptiveRMSNorm (audio stream): kwargs for the RESID / GATE_RESID GEMM or the conv that
-        writes the rows to be normed.  switch_row: rows from there on take the NEXT slot's gamma (the null half of a CFG
-        batch skips cross-attention, so its next norm is the feed-forward's)."""
+        """Producer side of a folded AdaptiveRMSNorm (audio stream): the norm kwargs of the GATE_RESID GEMM that writes the rows
+        to be normed (its gate kwargs pass `step` and `rows_per_batch`).  switch_row: rows from there on take the NEXT slot's
+        gamma (the null half of a CFG batch skips cross-attention, so its next norm is the feed-forward's)."""
         p, D = self.plan, self.cfg.dim
         ss = p["norm_tab"].stride(0)
-        kw = dict(norm_gamma=p["norm_tab"][0, layer, slot], norm_ssq=p["ssq_a"], rows_per_batch=p["N"])
-        if p["per_sample_t"]:
-            kw["norm_batch_stride"] = ss
-        else:
-            kw.update(step=p["step"], norm_step_stride=ss)
+        kw = dict(norm_gamma=p["norm_tab"][0, layer, slot], norm_ssq=p["ssq_a"], shadow=self._rows(p["hn_a"]))
+        kw["norm_batch_stride" if p["per_sample_t"] else "norm_step_stride"] = ss
         if switch_row:
             kw.update(norm_switch_row=switch_row, norm_switch_offset=D)
         return kw
@@ -536,10 +536,10 @@ class DiTEngine:
         N, rows = p["N"], nseq * p["N"]
         hn, qkv, ao = p[f"hn_{s}"], p[f"qkv_{s}"], p[f"ao_{s}"]
         if self._fuse_rope:       # RoPE of the q and k heads inside the QKV GEMM epilogue
-            self._mm([(hn, d, d)], A.w_in, qkv, M=rows, N=A.n_pad, bias=A.b_in, ldo=A.n_pad,
+            self._mm([self._rows(hn)], A.w_in, qkv, M=rows, N=A.n_pad, bias=A.b_in, ldo=A.n_pad,
                      rope_table=p["rope"], rope_cols=2 * A.inner, rope_pos_offset=0, rows_per_batch=N, **in_kw)
         else:
-            self._mm([(hn, d, d)], A.w_in, qkv, M=rows, N=A.n_pad, bias=A.b_in, ldo=A.n_pad, **in_kw)
+            self._mm([self._rows(hn)], A.w_in, qkv, M=rows, N=A.n_pad, bias=A.b_in, ldo=A.n_pad, **in_kw)
             L.rope(qkv, rows=rows, row_stride=A.n_pad, nheads=2 * A.heads, rows_per_batch=N, pos_offset=0,
                    table=p["rope"], layout=self.rope_layout)
         es = qkv.element_size()
@@ -554,77 +554,69 @@ class DiTEngine:
                     B=nseq, H=A.heads, Nq=N, Nk=N, kv_len=lens,
                     q_len=lens if self.zero_masked_queries else None,
                     scale=self.cfg.dim_head ** -0.5, softclamp=self.softclamp, dtype=self.adc, out_split=self.split)
-        self._mm([(ao, A.inner, A.inner)], A.w_out, x, M=rows, N=d, resid=x, ldo=d, ldr=d, **out_kw)
+        self._mm([self._rows(ao)], A.w_out, x, M=rows, N=d, resid=x, ldo=d, ldr=d, **out_kw)
 
     def _ff(self, Fw: _FF, x, s, nseq, d, out_kw, in_kw={}):
+        """x += epilogue(W2 geglu(W1 hn_s)); out_kw may name the `shadow` that receives the bf16 copy of x."""
         p = self.plan
         rows = nseq * p["N"]
         hn, ffh = p[f"hn_{s}"], p[f"ffh_{s}"]
         # (A row split -- whole 256-row bands on the phase-interleaved kernel in one round, the 28-row tail as its own launch -- takes
         # the text stream's GEMM from 66.9 to 51 us alone and LOSES 2 % in the sampler, profiles/r03_rowsplit_probe.txt: not done.)
-        self._mm([(hn, d, d)], Fw.w1, ffh, M=rows, N=2 * Fw.inner, epilogue=L.EPI_GEGLU, bias=Fw.b1, ldo=ffh.stride(-2),
+        self._mm([self._rows(hn)], Fw.w1, ffh, M=rows, N=2 * Fw.inner, epilogue=L.EPI_GEGLU, bias=Fw.b1, ldo=ffh.stride(-2),
                  **(dict(out_split=True) if self.split else {}), **in_kw)
-        out_kw = dict(out_kw)
-        shadow = out_kw.pop("out_bf16", self._sh(x))         # the audio stream redirects it into a wide operand buffer (forward)
-        self._mm([(ffh, Fw.inner, Fw.inner)], Fw.w2, x, M=rows, N=d, bias=Fw.b2, resid=x, ldo=d, ldr=d, out_bf16=shadow, **out_kw)
+        self._mm([self._rows(ffh)], Fw.w2, x, M=rows, N=d, bias=Fw.b2, resid=x, ldo=d, ldr=d, **out_kw)
 
-    def _side_hint(self, stream="t", op="qkv"):
-        """tile_hint of a text / frames GEMM (op: cross, qkv, out, ff1, ff2) while one launch cannot fill the chip anyway (up to
-        two clips: M <= 3128 rows); with more rows every kernel fills all CUs and the library's stand-alone choice is faster
-        (8 clips: text feed-forward 325 us on the 256x256 kernel against 556 us on forced 128x256 tiles).  `side_tiles` maps
-        (stream, op) to a tile configuration of v2a_tuning.gemm_force_tile; missing entries take `side_tile`."""
-        if self.split:                      # split-operand GEMMs have their own tile shapes (v2a_gemm): 0 = by shape
-            return (self.split_big_tiles if self._regime() == 2 else self.split_tiles).get((stream, op), 0)
-        if self.side_tile < 0:
-            return 0
+    def _tile_hint(self, stream, op):
+        """tile_hint of a GEMM (v2a_gemm_args; 0 = the library's choice) on the audio stream "a" (ops: x_tfa skip qkv out q2 out2
+        ff1 ff2) or a text / frames stream "t" / "f" (cross qkv out ff1 ff2).  `side_tiles` / `big_tiles` map (stream, op) to a
+        tile configuration of v2a_tuning.gemm_force_tile; missing entries take the stream's policy tile: `side_tile` on the side
+        streams (-1: the library's), `main_tile` on the audio stream's narrow GEMMs.  Up to two clips (M <= 3128 rows) one launch
+        cannot fill the chip anyway; with more rows every kernel fills all CUs and the library's stand-alone choice is faster
+        (8 clips: text feed-forward 325 us on the 256x256 kernel against 556 us on forced 128x256 tiles): `big_tiles` only."""
         r = self._regime()
+        if self.split:                      # split-operand GEMMs have their own tile shapes (v2a_gemm): 0 = by shape
+            return (self.split_big_tiles if r == 2 else self.split_tiles).get((stream, op), 0)
+        side = stream != "a"
+        if side and self.side_tile < 0:
+            return 0
         if r == 2:
             return self.big_tiles.get((stream, op), -1) + 1
-        if r == 1 or not self._tuned_dims():        # two clips: the table below was tuned at one clip and costs 4 % here (6214 vs 6467)
-            return self.side_tile + 1
-        return self.side_tiles.get((stream, op), self.side_tile) + 1
-
-    def _main_hint(self, op=None):
-        if self.split:
-            t = (self.split_big_tiles if self._regime() == 2 else self.split_tiles).get(("a", op), 0)
-            return dict(tile_hint=t) if t else {}
-        r = self._regime()
-        if r == 2:
-            t = self.big_tiles.get(("a", op), -1)
-            return dict(tile_hint=t + 1) if t >= 0 else {}
-        if r == 1 or not self._tuned_dims():
-            return {}
-        t = self.side_tiles.get(("a", op), self.main_tile if op in ("x_tfa", "skip", "out", "out2", "ff2") else -1)
-        return dict(tile_hint=t + 1) if t >= 0 else {}
+        if r == 1 or not self._tuned_dims():        # two clips: the one-clip table costs 4 % here (6214 vs 6467)
+            return self.side_tile + 1 if side else 0
+        narrow = self.main_tile if op in ("x_tfa", "skip", "out", "out2", "ff2") else -1
+        return max(self.side_tiles.get((stream, op), self.side_tile if side else narrow), -1) + 1
 
     def _side_block(self, ly, s, src, dst, nseq, d, parts=(0, 1, 2)):
         """text / frames stream block (x3:1081-1086, 1097-1101): conv, attention, feed-forward.  `parts` selects
         0 = conv + norm, 1 = attention, 2 = norm + feed-forward, so that the caller can interleave the CAPTURE order of the
-        two side blocks and the audio block (a replayed graph hands kernels to the queues in capture order)."""
+        two side blocks and the audio block (a replayed graph hands kernels to the queues in capture order).  src: fp32 rows;
+        dst: a _Stream, whose operand copy the feed-forward writes."""
         p = self.plan
         N, rows = p["N"], nseq * p["N"]
         lens = p["seq_len"] if p["ragged"] else None
         cv = ly[f"{s}_conv"]
-        hq, ho, h1, h2 = (dict(tile_hint=self._side_hint(s, op)) for op in ("qkv", "out", "ff1", "ff2"))
+        hq, ho, h1, h2 = (self._tile_hint(s, op) for op in ("qkv", "out", "ff1", "ff2"))
         fold, fold2 = self._fold(), self._fold_gemm()
         hn, ssq = p[f"hn_{s}"], p[f"ssq_{s}"]
         nc = self._ncons(s, d)
-        cons = dict(**hq, **nc)
-        cons2 = dict(**h1, **(nc if fold2 else {}))
+        cons = dict(tile_hint=hq, **nc)
+        cons2 = dict(tile_hint=h1, **(nc if fold2 else {}))
+        x = dst.x
         if 0 in parts:
             if fold:
-                L.dwconv(src, dst, cv.wt, cv.b, B=nseq, N=N, d=d, ksize=cv.k, lens=lens,
+                L.dwconv(src, x, cv.wt, cv.b, B=nseq, N=N, d=d, ksize=cv.k, lens=lens,
                          norm=dict(out_bf16=hn, ld_out_bf16=hn.stride(-2), gamma=ly[f"{s}_g1"], ssq=ssq, split=self.split))
             else:
-                L.dwconv(src, dst, cv.wt, cv.b, B=nseq, N=N, d=d, ksize=cv.k, lens=lens)
-                self._norm_plain(dst, hn, rows, d, ly[f"{s}_g1"])
+                L.dwconv(src, x, cv.wt, cv.b, B=nseq, N=N, d=d, ksize=cv.k, lens=lens)
+                self._norm_plain(x, hn, rows, d, ly[f"{s}_g1"])
         if 1 in parts:
-            prod = dict(out_bf16=hn, ld_out_bf16=hn.stride(-2), norm_gamma=ly[f"{s}_g2"], norm_ssq=ssq) if fold2 else {}
-            self._self_attn(ly[f"{s}_attn"], dst, s, nseq, d, dict(epilogue=L.EPI_RESID, **ho, **prod), cons)
+            prod = dict(shadow=self._rows(hn), norm_gamma=ly[f"{s}_g2"], norm_ssq=ssq) if fold2 else {}
+            self._self_attn(ly[f"{s}_attn"], x, s, nseq, d, dict(epilogue=L.EPI_RESID, tile_hint=ho, **prod), cons)
         if 2 in parts:
             if not fold2:
-                self._norm_plain(dst, hn, rows, d, ly[f"{s}_g2"])
-            self._ff(ly[f"{s}_ff"], dst, s, nseq, d, dict(epilogue=L.EPI_RESID, **h2), cons2)
+                self._norm_plain(x, hn, rows, d, ly[f"{s}_g2"])
+            self._ff(ly[f"{s}_ff"], x, s, nseq, d, dict(epilogue=L.EPI_RESID, tile_hint=h2, shadow=dst.sh), cons2)
 
     def _audio_cross_attention(self, i, ly, x, nctx, cons2, fold2, lens):
         """x[:nctx] += gate * to_out(attend(q(x), K_ctx, V_ctx)) of layer i (x3:1126-1133) on the current stream: one launch
@@ -633,7 +625,6 @@ class DiTEngine:
         N, D = p["N"], c.dim
         inner = c.heads * c.dim_head
         nkv = 2 * c.depth * inner
-        mh = self._main_hint
         r2 = nctx * N
         A2 = ly["a_attn2"]
         if not fold2:
@@ -650,16 +641,17 @@ class DiTEngine:
         if one_launch:
             rk = dict(rope_table=p["rope"], rope_cols=A2.inner, rope_pos_offset=0) if self.rope_cross else {}
             nk = dict(row_ssq=cons2["row_ssq"], row_norm_dim=cons2["row_norm_dim"]) if cons2 else {}
-            L.qproj_xattn(p["hn_a"], p["hn_a"].stride(-2) if self.split else D, D, A2.w_in, bias=A2.b_in, M=r2, N=A2.n_pad, rows_per_batch=N,
+            L.qproj_xattn(p["hn_a"], p["hn_a"].stride(-2), D, A2.w_in, bias=A2.b_in, M=r2, N=A2.n_pad, rows_per_batch=N,
                           k=kb, v=vb, out=p["ao_a"].data_ptr(), split=self.split,
                           kv_strides=(nkv, nkv, p["nc"] * nkv, p["nc"] * nkv), out_strides=(aw, N * aw), B=nctx, H=A2.heads, Nk=p["nc"],
                           kv_len=p["ctx_len"], q_len=lens if self.zero_masked_queries else None, scale=c.dim_head ** -0.5,
                           softclamp=self.softclamp, **rk, **nk)
         elif self.rope_cross and self._fuse_rope:
-            self._mm([(p["hn_a"], D, D)], A2.w_in, q2, M=r2, N=A2.n_pad, bias=A2.b_in, ldo=A2.n_pad,
-                     rope_table=p["rope"], rope_cols=A2.inner, rope_pos_offset=0, rows_per_batch=N, **cons2, **mh("q2"))
+            self._mm([self._rows(p["hn_a"])], A2.w_in, q2, M=r2, N=A2.n_pad, bias=A2.b_in, ldo=A2.n_pad, rope_table=p["rope"],
+                     rope_cols=A2.inner, rope_pos_offset=0, rows_per_batch=N, tile_hint=self._tile_hint("a", "q2"), **cons2)
         else:
-            self._mm([(p["hn_a"], D, D)], A2.w_in, q2, M=r2, N=A2.n_pad, bias=A2.b_in, ldo=A2.n_pad, **cons2, **mh("q2"))
+            self._mm([self._rows(p["hn_a"])], A2.w_in, q2, M=r2, N=A2.n_pad, bias=A2.b_in, ldo=A2.n_pad,
+                     tile_hint=self._tile_hint("a", "q2"), **cons2)
             if self.rope_cross:
                 L.rope(q2, rows=r2, row_stride=A2.n_pad, nheads=A2.heads, rows_per_batch=N, pos_offset=0,
                        table=p["rope"], layout=self.rope_layout)
@@ -670,12 +662,8 @@ class DiTEngine:
                         B=nctx, H=A2.heads, Nq=N, Nk=p["nc"], kv_len=p["ctx_len"],
                         q_len=lens if self.zero_masked_queries else None,
                         scale=c.dim_head ** -0.5, softclamp=self.softclamp, dtype=self.adc, out_split=self.split)
-        prod2 = {}
-        if fold2:
-            n2 = {k: v for k, v in self._nprod_ada(i, 2).items() if k not in ("step", "rows_per_batch")}
-            prod2 = dict(out_bf16=p["hn_a"], ld_out_bf16=p["hn_a"].stride(-2), **n2)
-        self._mm([(p["ao_a"], inner, inner)], A2.w_out, x, M=r2, N=D, resid=x, ldo=D, ldr=D,
-                 epilogue=L.EPI_GATE_RESID, **self._gate_kw(i, 1), **mh("out2"), **prod2)
+        self._mm([self._rows(p["ao_a"])], A2.w_out, x, M=r2, N=D, resid=x, ldo=D, ldr=D, epilogue=L.EPI_GATE_RESID,
+                 tile_hint=self._tile_hint("a", "out2"), **self._gate_kw(i, 1), **(self._nprod_ada(i, 2) if fold2 else {}))
 
     # ------------------------------------------------------------------------------ prepare
     def prepare(self, text, frames_roll, context, context_mask, t_points, *, lens=None,
@@ -758,7 +746,7 @@ class DiTEngine:
         p["ctx_len"].copy_(cl)
         inner = c.heads * c.dim_head
         nkv = 2 * c.depth * inner
-        self._mm([(p["ctx"], c.ctx_dim, c.ctx_dim)], W.ctx_kv_w, p["ctx_kv"], M=B * nc, N=nkv, ldo=nkv)
+        self._mm([self._rows(p["ctx"])], W.ctx_kv_w, p["ctx_kv"], M=B * nc, N=nkv, ldo=nkv)
         if self.rope_cross:                                   # A7: keys take the LAST nc table rows
             off = (N if rope_len is None else int(rope_len)) - (nc if rope_ctx_len is None else int(rope_ctx_len))
             assert 0 <= off and off + nc <= p["rope"].shape[0], (off, nc, N)
@@ -774,14 +762,15 @@ class DiTEngine:
         """x0 = [registers ; proj_in(y) + abs_pos_emb]  (x3:2027, 957-960, 975-976) into xA."""
         p, c, W = self.plan, self.cfg, self.W
         B, Bt, T, N, D = p["B"], p["Bt"], p["T"], p["N"], c.dim
-        L.linear_small(y, W.pin_wt, W.pin_b, p["padd"] if p["has_cond"] else W.pos_emb, p["xA"], M=B * T, K=c.num_channels, T=T,
+        x = p["xA"]
+        L.linear_small(y, W.pin_wt, W.pin_b, p["padd"] if p["has_cond"] else W.pos_emb, x.x, M=B * T, K=c.num_channels, T=T,
                        out_batch_stride=N * D, row_off=c.num_registers, d=D, dup=(B if Bt > B else 0),
-                       regs=W.regs, out_bf16=None if self.split else self._sh(p["xA"]))
+                       regs=W.regs, out_bf16=None if self.split or x.sh is None else x.sh.t)
         if self.split:              # operand planes of x0 (both halves); the conditional half is rewritten by the GEMM below
-            L.split_bf16(p["xA"], self._sh(p["xA"]), rows=Bt * N, d=D)
+            L.split_bf16(x.x, x.sh.t, rows=Bt * N, d=D)
         if p["has_cond"]:           # conditional half: x += cond_proj_in.weight @ step_cond (the bias sits in the position table)
-            self._mm([(p["condbuf"], W.cond_k, W.cond_k)], W.cond_w, p["xA"], M=B * N, N=D, epilogue=L.EPI_RESID, resid=p["xA"],
-                     ldo=D, ldr=D, out_bf16=self._sh(p["xA"]))
+            self._mm([self._rows(p["condbuf"])], W.cond_w, x.x, M=B * N, N=D, epilogue=L.EPI_RESID, resid=x.x,
+                     ldo=D, ldr=D, shadow=x.sh)
 
     def forward(self, n_ctx_seqs: int | None = None):
         """Transformer.forward over the plan's Bt sequences starting from xA; result in plan['pred'].
@@ -845,30 +834,28 @@ class DiTEngine:
             # ~100 us per layer across two cross-stream hand-offs, each costing 10-50 us of queue-to-queue latency.)
             wait(main, eT, eF)
             xn = p["skips"][i] if i < half else xo
-            ax, at_, af_ = self._opnd(xc), self._opnd(tc_), self._opnd(fc_)
-            mh = self._main_hint
+            ax, at_, af_ = xc.op, tc_.op, fc_.op
             fused = fz and i >= half
             if fused:
                 # second half, bf16 mode: cross-condition + skip projection in one GEMM over [x | skip | text | frames]; x's
                 # bf16 copy was written into the left half of the skip's wide buffer by the previous layer's FF2 epilogue
                 wd = p["wide"][c.depth - 1 - i]
-                ax = wd[..., :D]
-                self._mm([(wd, 2 * D, 2 * D), (at_, Dt, Dt), (af_, Df, Df)], ly["x_skip"], p["xS"], M=rows, N=D, ldo=D, **mh("x_tfa"))
+                ax = wd.x
+                self._mm([wd.whole, at_, af_], ly["x_skip"], p["xS"], M=rows, N=D, ldo=D, tile_hint=self._tile_hint("a", "x_tfa"))
             else:
-                self._mm([(ax, D, D), (at_, Dt, Dt), (af_, Df, Df)], ly["x_tfa"], xn, M=rows, N=D,
-                         epilogue=L.EPI_RESID, resid=xc, ldo=D, ldr=D, out_bf16=self._sh(xn), **mh("x_tfa"))
-            ax_ld = ax.stride(-2)
+                self._mm([ax, at_, af_], ly["x_tfa"], xn.x, M=rows, N=D, epilogue=L.EPI_RESID, resid=xc.x, ldo=D, ldr=D,
+                         shadow=xn.sh, tile_hint=self._tile_hint("a", "x_tfa"))
             if not last:
                 nxt = W.layers[i + 1]
                 on_side = multi and not self.cross_on_main
-                hint_t = self._side_hint("t", "cross") if on_side else 0
-                hint = self._side_hint("f", "cross") if on_side else 0
+                hint_t = self._tile_hint("t", "cross") if on_side else 0
+                hint = self._tile_hint("f", "cross") if on_side else 0
                 def cross_t():
-                    self._mm([(ax, ax_ld, D), (at_, Dt, Dt)], ly["x_at"], tbuf[0], M=rows, N=Dt,
-                             epilogue=L.EPI_RESID, resid=tc_, ldo=Dt, ldr=Dt, tile_hint=hint_t)
+                    self._mm([ax, at_], ly["x_at"], tbuf[0].x, M=rows, N=Dt,
+                             epilogue=L.EPI_RESID, resid=tc_.x, ldo=Dt, ldr=Dt, tile_hint=hint_t)
                 def cross_f():
-                    self._mm([(ax, ax_ld, D), (af_, Df, Df)], ly["x_af"], fbuf[0], M=rows, N=Df,
-                             epilogue=L.EPI_RESID, resid=fc_, ldo=Df, ldr=Df, tile_hint=hint)
+                    self._mm([ax, af_], ly["x_af"], fbuf[0].x, M=rows, N=Df,
+                             epilogue=L.EPI_RESID, resid=fc_.x, ldo=Df, ldr=Df, tile_hint=hint)
                 if self.cross_on_main or not multi:
                     cross_t()
                     cross_f()
@@ -884,48 +871,41 @@ class DiTEngine:
                         cross_f()
             # U-Net skip (x3:1108-1117).  First half: the cross-condition output buffer IS the saved skip.  Second half:
             # skip_proj(cat(x, skip)) -> spare buffer.  The conv output (and the whole audio block after it) goes to xo.
-            if i < half:
-                src = xn
-            elif fused:
-                src = p["xS"]
-            else:
-                src = p["xS"]
-                sk = self._opnd(p["skips"][c.depth - 1 - i])          # bf16 mode: the right half of a wide operand buffer
-                self._mm([(self._opnd(xn), D, D), (sk, sk.stride(-2), D)], ly["skip"], src, M=rows, N=D, ldo=D, **mh("skip"))
-            dst = xo
+            src = xn.x if i < half else p["xS"]
+            if i >= half and not fused:     # the skip's operand: in bf16 mode the right half of a wide operand buffer
+                self._mm([xn.op, p["skips"][c.depth - 1 - i].op], ly["skip"], src, M=rows, N=D, ldo=D, tile_hint=self._tile_hint("a", "skip"))
             # audio stream (x3:1121-1137)
             cv = ly["a_conv"]
             fold, fold2 = self._fold(), self._fold_gemm()       # norm after the conv / norms after GEMM epilogues
             cons = self._ncons("a", D)
             cons2 = cons if fold2 else {}
-            x = dst
+            x = xo.x
             r2 = nctx * N
             prod1 = {}
             if fold:
-                n0 = self._nprod_ada(i, 0)
-                L.dwconv(src, dst, cv.wt, cv.b, B=Bt, N=N, d=D, ksize=cv.k, lens=lens,
-                         norm=dict(out_bf16=p["hn_a"], ld_out_bf16=p["hn_a"].stride(-2), gamma=n0["norm_gamma"], ssq=p["ssq_a"], step=n0.get("step"),
-                                   step_stride=n0.get("norm_step_stride", 0), batch_stride=n0.get("norm_batch_stride", 0), split=self.split))
+                ps, ss = p["per_sample_t"], p["norm_tab"].stride(0)
+                L.dwconv(src, x, cv.wt, cv.b, B=Bt, N=N, d=D, ksize=cv.k, lens=lens,
+                         norm=dict(out_bf16=p["hn_a"], ld_out_bf16=p["hn_a"].stride(-2), gamma=p["norm_tab"][0, i, 0], ssq=p["ssq_a"],
+                                   split=self.split, **(dict(batch_stride=ss) if ps else dict(step=p["step"], step_stride=ss))))
             else:
-                L.dwconv(src, dst, cv.wt, cv.b, B=Bt, N=N, d=D, ksize=cv.k, lens=lens)
+                L.dwconv(src, x, cv.wt, cv.b, B=Bt, N=N, d=D, ksize=cv.k, lens=lens)
                 self._norm_ada(x, p["hn_a"], rows, D, i, 0)
             if fold2:
                 # the norm after self-attention is cross-attention's (slot 1) for the rows that have a context, the
                 # feed-forward's (slot 2) for the rest
-                n1 = self._nprod_ada(i, 1, switch_row=r2 if r2 < rows else 0) if nctx > 0 else self._nprod_ada(i, 2)
-                n1 = {k: v for k, v in n1.items() if k not in ("step", "rows_per_batch")}       # the gate already passes them
-                prod1 = dict(out_bf16=p["hn_a"], ld_out_bf16=p["hn_a"].stride(-2), **n1)
-            self._self_attn(ly["a_attn"], x, "a", Bt, D, dict(epilogue=L.EPI_GATE_RESID, **self._gate_kw(i, 0), **mh("out"), **prod1), dict(**cons, **mh("qkv")))
+                prod1 = self._nprod_ada(i, 1, switch_row=r2 if r2 < rows else 0) if nctx > 0 else self._nprod_ada(i, 2)
+            self._self_attn(ly["a_attn"], x, "a", Bt, D, dict(epilogue=L.EPI_GATE_RESID, tile_hint=self._tile_hint("a", "out"),
+                                                            **self._gate_kw(i, 0), **prod1), dict(tile_hint=self._tile_hint("a", "qkv"), **cons))
             if not last and self.interleave_capture:
                 for part in (0, 1):
                     with _On(st):
                         if part == 0:
                             wait(st, eX)
-                        self._side_block(nxt, "t", tbuf[0], tbuf[1], Bt, Dt, (part,))
+                        self._side_block(nxt, "t", tbuf[0].x, tbuf[1], Bt, Dt, (part,))
                     with _On(sf):
                         if part == 0:
                             wait(sf, eX)
-                        self._side_block(nxt, "f", fbuf[0], fbuf[1], Bt, Df, (part,))
+                        self._side_block(nxt, "f", fbuf[0].x, fbuf[1], Bt, Df, (part,))
             if nctx > 0:
                 self._audio_cross_attention(i, ly, x, nctx, cons2, fold2, lens)
             # (holding the side streams' feed-forward launches back until here -- this out-projection's 208 small workgroups take 118-134 us
@@ -934,10 +914,11 @@ class DiTEngine:
             if not fold2:
                 self._norm_ada(x, p["hn_a"], rows, D, i, 2)
             # the bf16 copy of this layer's output: into the wide buffer of the next layer's skip when that layer is fused
-            xsh = dict(out_bf16=p["wide"][c.depth - 2 - i][..., :D]) if (fz and half <= i + 1 < c.depth) else {}
+            xsh = dict(shadow=p["wide"][c.depth - 2 - i].x if (fz and half <= i + 1 < c.depth) else xo.sh)
             if last and fold2:      # the final RMSNorm folded like the others: gamma on the operand copy, 1 / rms per row in to_pred's epilogue
-                xsh = dict(out_bf16=p["hn_a"], ld_out_bf16=p["hn_a"].stride(-2), norm_gamma=W.final_g, norm_ssq=p["ssq_a"])
-            self._ff(ly["a_ff"], x, "a", Bt, D, dict(epilogue=L.EPI_GATE_RESID, **self._gate_kw(i, 2), **mh("ff2"), **xsh), dict(**cons2, **mh("ff1")))
+                xsh = dict(shadow=self._rows(p["hn_a"]), norm_gamma=W.final_g, norm_ssq=p["ssq_a"])
+            self._ff(ly["a_ff"], x, "a", Bt, D, dict(epilogue=L.EPI_GATE_RESID, tile_hint=self._tile_hint("a", "ff2"), **self._gate_kw(i, 2), **xsh),
+                     dict(tile_hint=self._tile_hint("a", "ff1"), **cons2))
             if not last:
                 if not self.cross_on_main:
                     eA = rec(main)             # x of the next layer is ready
@@ -949,21 +930,22 @@ class DiTEngine:
                 with _On(st):
                     if not self.interleave_capture:
                         wait(st, eX)
-                    self._side_block(nxt, "t", tbuf[0], tbuf[1], Bt, Dt, rest)
+                    self._side_block(nxt, "t", tbuf[0].x, tbuf[1], Bt, Dt, rest)
                     eT = rec(st)
                 with _On(sf):
                     if not self.interleave_capture:
                         wait(sf, eX)
-                    self._side_block(nxt, "f", fbuf[0], fbuf[1], Bt, Df, rest)
+                    self._side_block(nxt, "f", fbuf[0].x, fbuf[1], Bt, Df, rest)
                     eF = rec(sf)
                 tc_, fc_ = tbuf[1], fbuf[1]
             xc, xo = xo, xc
         # final norm over all rows (registers are dropped by the consumer) + to_pred (x3:1141-1143, 2083)
         if self._fold_gemm():
-            self._mm([(p["hn_a"], D, D)], W.pred_w, p["pred"], M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels, **self._ncons("a", D))
+            self._mm([self._rows(p["hn_a"])], W.pred_w, p["pred"], M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels,
+                     **self._ncons("a", D))
         else:
-            L.rmsnorm(xc, p["hn_a"], rows=rows, d=D, gamma=W.final_g, split=self.split)
-            self._mm([(p["hn_a"], D, D)], W.pred_w, p["pred"], M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels)
+            L.rmsnorm(xc.x, p["hn_a"], rows=rows, d=D, gamma=W.final_g, split=self.split)
+            self._mm([self._rows(p["hn_a"])], W.pred_w, p["pred"], M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels)
         return p["pred"]
 
     def euler_step(self, y, cfg_strength: float, remove_parallel_component: bool = False, keep_parallel_frac: float = 0.0):

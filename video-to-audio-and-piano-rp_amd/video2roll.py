@@ -69,12 +69,6 @@ def expected_state_dict_shapes(num_classes: int = NOTES) -> dict[str, tuple]:
     return s
 
 
-def _split_rows(w):
-    """fp32 rows -> [W_hi | W_lo] bf16 rows (V2A_BF16_SPLIT): hi = bf16(w), lo = bf16(w - hi)."""
-    hi = w.to(torch.bfloat16)
-    return torch.cat([hi, (w - hi.float()).to(torch.bfloat16)], 1)
-
-
 class _Conv:
     """One convolution as a GEMM operand: weight [Cout][Kpad] in the compute dtype (BatchNorm scale folded in),
     fp32 bias (folded BatchNorm shift, plus the conv's own bias where it has one).  split (bf16x3 mode): weight rows
@@ -96,7 +90,7 @@ class _Conv:
         self.Kpad = (K + kq - 1) // kq * kq
         wp = torch.zeros(co, self.Kpad)
         wp[:, :K] = wk
-        self.w = (_split_rows(wp) if split else wp.to(cd)).to(dev).contiguous()
+        self.w = (L.split_planes(wp) if split else wp.to(cd)).to(dev).contiguous()
         self.w_pack = None
         if window and cd == torch.bfloat16:
             # implicit first layer (v2a_frames_pack): per input channel kh rows of 16 columns, padded to whole 64-element K tiles
@@ -104,7 +98,7 @@ class _Conv:
             wq = torch.zeros(co, ci, g * 4, 16)
             wq[:, :, :kh, :kw] = w
             wq = wq.reshape(co, ci * g * 64)
-            self.w_pack = (_split_rows(wq) if split else wq.to(cd)).to(dev).contiguous()
+            self.w_pack = (L.split_planes(wq) if split else wq.to(cd)).to(dev).contiguous()
             self.g = g
         self.bias = None if bias is None else bias.to(dev).contiguous()
         self.co, self.ci, self.kh, self.kw, self.stride, self.pad, self.window = co, ci, kh, kw, stride, pad, window
@@ -184,12 +178,16 @@ class Video2RollEngine:
     # ---- activation maps --------------------------------------------------------------------------
     class _Map:
         """NHWC fp32 activation (n, H + 2b, W + 2b, C) with a zero border of b pixels, plus its bf16 copy when a
-        convolution reads it (the DMA GEMM moves raw bf16 bytes).  bf16x3 mode: the copy is a split shadow
-        (2, n, H + 2b, W + 2b, C) -- plane 0 hi, plane 1 lo, both zero-bordered."""
-        __slots__ = ("f32", "b16", "n", "H", "W", "C", "border")
+        convolution reads it (the DMA GEMM moves raw bf16 bytes): `sh`, an operand record of rows of C.  bf16x3 mode: the copy
+        is a split shadow (2, n, H + 2b, W + 2b, C) -- plane 0 hi, plane 1 lo (sh.lo = one plane further), both zero-bordered."""
+        __slots__ = ("f32", "sh", "n", "H", "W", "C", "border")
 
-        def __init__(self, f32, b16, n, H, W, C, border):
-            self.f32, self.b16, self.n, self.H, self.W, self.C, self.border = f32, b16, n, H, W, C, border
+        def __init__(self, f32, sh, n, H, W, C, border):
+            self.f32, self.sh, self.n, self.H, self.W, self.C, self.border = f32, sh, n, H, W, C, border
+
+        @property
+        def b16(self):
+            return None if self.sh is None else self.sh.t
 
         def interior(self):
             b = self.border
@@ -205,7 +203,8 @@ class Video2RollEngine:
             shp = (n, H + 2 * border, W + 2 * border, C)
             f32 = torch.zeros(shp, device=self.dev, dtype=torch.float32)
             b16 = torch.zeros(((2,) if split else ()) + shp, device=self.dev, dtype=torch.bfloat16) if shadow else None
-            m = self._maps[key] = self._Map(f32, b16, n, H, W, C, border)
+            sh = None if b16 is None else L.Operand(b16, C, C, b16[0].numel() if split else 0)
+            m = self._maps[key] = self._Map(f32, sh, n, H, W, C, border)
         return m
 
     def _colbuf(self, rows, kpad):
@@ -260,8 +259,8 @@ class Video2RollEngine:
         rs = None if resid is None else resid.f32
         # bf16x3: the A operand's lo plane is a whole map (plane) after its hi plane; weight rows are [W_hi | W_lo]
         sp = dict(a_split=True) if self.split else {}
-        if self.split and dst.b16 is not None:
-            sp.update(out_bf16_split=True, out_bf16_lo_offset=dst.b16[0].numel())
+        if self.split and dst.sh is not None:
+            sp.update(out_bf16_split=True, out_bf16_lo_offset=dst.sh.lo)
         if cv.window and patches is not None:
             # first layer over the packed column patches of this clip (v2a_frames_pack): windows [first, first + n) of the clip
             key = ("c1", T, first, n, H, W)
@@ -275,19 +274,16 @@ class Video2RollEngine:
                 a_row = ((ni * Wo + xo) * Hp + yo * cv.stride) * 16
                 kt = torch.arange(cv.ci * cv.g, device=dev, dtype=torch.int64)
                 a_k = (kt // cv.g) * (Wo * Hp * 16) + (kt % cv.g) * 64
-                assert int(a_row.max()) + int(a_k.max()) + 64 <= patches.numel() // (2 if self.split else 1) < 2 ** 31
+                assert int(a_row.max()) + int(a_k.max()) + 64 <= (patches.lo or patches.t.numel()) < 2 ** 31      # within the hi plane
                 t = self._tabs[key] = (a_row.reshape(-1).to(torch.int32).contiguous(), a_k.to(torch.int32).contiguous())
-            K = cv.ci * cv.g * 64
-            seg = (patches, K, K, patches.numel() // 2) if self.split else (patches, K, K)
-            L.gemm([seg], cv.w_pack, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
+            L.gemm([patches], cv.w_pack, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
                    relu=relu, ldo=cv.co, ldr=cv.co, a_row_offset=t[0], a_ktile_offset=t[1], **sp)
             return dst
         if self.implicit and not cv.window:
             a_row, a_k, o_row = self._tables(cv, src, Ho, Wo, dst.border)
             K = cv.kh * cv.kw * cv.ci
             assert K == cv.Kpad, "NHWC convolutions have whole 64-element K tiles (C % 64 == 0)"
-            seg = (src.b16, K, K, src.b16[0].numel()) if self.split else (src.b16, K, K)
-            L.gemm([seg], cv.w, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
+            L.gemm([src.sh._replace(ld=K, k=K)], cv.w, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
                    relu=relu, ldo=cv.co, ldr=cv.co, out_bf16=dst.b16, ld_out_bf16=cv.co,
                    a_row_offset=a_row, a_ktile_offset=a_k, out_row_offset=o_row, **sp)
             return dst
@@ -309,8 +305,8 @@ class Video2RollEngine:
         Ho, Wo = (src.H + 2 * pad - k) // stride + 1, (src.W + 2 * pad - k) // stride + 1
         if dst is None:
             dst = self._map(dst_name, src.n, Ho, Wo, src.C, border, shadow)
-        if self.split and dst.b16 is not None:
-            L.pool2d_split(src.f32, dst.f32, dst.b16, lo_offset=dst.b16[0].numel(), B=src.n, H=src.H, W=src.W, C_=src.C, k=k,
+        if self.split and dst.sh is not None:
+            L.pool2d_split(src.f32, dst.f32, dst.b16, lo_offset=dst.sh.lo, B=src.n, H=src.H, W=src.W, C_=src.C, k=k,
                            stride=stride, pad=pad, mode=mode, Ho=Ho, Wo=Wo, in_border=src.border, out_border=dst.border)
             return dst
         L.pool2d(src.f32, dst.f32, B=src.n, H=src.H, W=src.W, C_=src.C, k=k, stride=stride, pad=pad, mode=mode, Ho=Ho, Wo=Wo,
@@ -381,20 +377,22 @@ class Video2RollEngine:
         return hb, P
 
     def _pack(self, clip_frames, T, H, W):
-        """bf16 column patches of one clip for the implicit first layer (v2a_frames_pack); bf16x3: hi | lo planes, one after
-        the other (v2a_frames_pack_split)."""
+        """bf16 column patches of one clip for the implicit first layer (v2a_frames_pack) as the operand record of that GEMM;
+        bf16x3: hi | lo planes, one after the other (v2a_frames_pack_split)."""
         cv = self.convs["conv1"]
         _, Wo = cv.out_hw(H, W)
         key = ("patches", T, H, W, self.split)
         plane = (T + 4) * Wo * (H + 2 * cv.pad) * 16
-        buf = self._maps.get(key)
-        if buf is None:
-            buf = self._maps[key] = torch.empty(plane * (2 if self.split else 1), device=self.dev, dtype=torch.bfloat16)
+        op = self._maps.get(key)
+        if op is None:
+            K = cv.ci * cv.g * 64
+            buf = torch.empty(plane * (2 if self.split else 1), device=self.dev, dtype=torch.bfloat16)
+            op = self._maps[key] = L.Operand(buf, K, K, plane if self.split else 0)
         if self.split:
-            L.frames_pack_split(clip_frames, buf, lo_offset=plane, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
+            L.frames_pack_split(clip_frames, op.t, lo_offset=op.lo, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
         else:
-            L.frames_pack(clip_frames, buf, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
-        return buf
+            L.frames_pack(clip_frames, op.t, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
+        return op
 
     def _run(self, frames, T, sigmoid, windows=None, taps=None):
         """frames (clips, T, H, W).  windows: explicit (clip, index) pairs (tests); default every window, clip by clip in chunks."""
