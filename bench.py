@@ -12,7 +12,9 @@ shapes; they are resident in HBM before the timed region, which covers everythin
 (modulation tables, cross-attention K/V, the Euler loop) plus, for N > 1, the single all-gather
 of latents.  Ranks are clip-sharded (weak scaling, no per-step communication).
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set up, warm up, time the steps,
+write --dump-outputs, print.  Everything else the script measures or checks runs only with --full (the --no-* options then
+leave single legs out).  With --full, an N > 1 line carries `scaling_reference`, and at N = 1 the line also carries
   roofline     : the dominant kernel class (the bf16 MFMA GEMM instantiation with the most time per evaluation) of the
                  configuration the sampler RUNS -- three streams, the per-(stream, op) tile table -- measured live with HIP
                  event pairs on the stream each kernel is launched on (`scope: production`); `standalone` holds the same class
@@ -127,7 +129,12 @@ def main():
                          "says so in `data`; its numbers measure nothing")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last one returned (the gathered mel latents) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the supplementary legs: roofline, parity modes, 8 clips per GPU, configs[3] / [4], Video2Roll, "
+                         "vocoder, CPU baselines (N = 1), scaling_reference (N > 1).  Without it the line holds the headline only")
     args = ap.parse_args()
+    if (args.shapes or args.graph_roofline) and not args.full:
+        ap.error("--shapes and --graph-roofline act on the roofline leg, which runs only with --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -314,7 +321,7 @@ def main():
         "prepare_ms": round(ph[0], 3), "euler_loop_ms": round(ph[1], 3),     # device-side split of the LAST sample() call of the timed region
     }
 
-    if world > 1:
+    if world > 1 and args.full:
         # Like-for-like comparator of the scaling curve: the N = 1 default of this script is ONE clip (configs[1]), an N > 1 run
         # samples `clips_per_gpu` clips per GPU (configs[2]) -- a ratio of the two `value`s would mix a shape change into the
         # scaling.  Rank 0 therefore times the SAME per-GPU shape alone (its own shard, no all-gather, the other ranks idle at a
@@ -337,7 +344,7 @@ def main():
         dist.barrier()
         if rank == 0:
             res["scaling_reference"] = scaling_reference(B, same, frames_per_s, world)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         hbm = {}
         if not args.no_batched and B == 1:
             res["batched"] = batched_leg(model, cfg, cfm_steps, args, T, NC, dev)
@@ -413,7 +420,7 @@ def standin_main(args, v2a_amd, dist, rank, world):
            "vs_baseline": None, "dtype": "none", "data": "stand-in sampler on CPU tensors over gloo: no GPU work",
            "config": {"workload": "stand-in", "clips_per_gpu": per, "global_clips": n_clips, "parallelism": "clip-sharded x%d, 1 all-gather" % world},
            "standin_gather_ok": bool(ok), "standin_shard": [lo, hi, per]}
-    if world > 1:
+    if world > 1 and args.full:
         same = None
         if rank == 0:
             ts = time.perf_counter()

@@ -54,6 +54,14 @@ def test_bench_help_lists_the_contract_flags():
         assert flag in out.stdout, flag
 
 
+def test_bench_help_lists_full_and_roofline_options_need_it():
+    """--full runs the supplementary legs; the options that only act inside the roofline leg are refused without it."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout, out.stderr[-500:]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--shapes"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--full" in out.stderr, out.stderr[-500:]
+
+
 def test_steps_must_be_positive():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and "--steps" in out.stderr, out.stderr[-500:]

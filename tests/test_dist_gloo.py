@@ -95,8 +95,8 @@ def _bench_standin(world, clips=None, extra=()):
 def test_bench_two_rank_control_path_end_to_end():
     """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one process per rank), with the sampler replaced by a
     stand-in on CPU tensors: sharding, barriers, the timed loop, MAX over ranks, ONE all-gather and the like-for-like `scaling_reference`
-    are bench.py's own code."""
-    r = _bench_standin(2)
+    are bench.py's own code.  `scaling_reference` is a measurement of its own and runs with --full."""
+    r = _bench_standin(2, extra=("--full",))
     assert r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["scaling"] == "weak"
     assert r["config"]["parallelism"] == "clip-sharded x2, 1 all-gather" and r["config"]["global_clips"] == 16 and r["config"]["clips_per_gpu"] == 8
     assert r["standin_gather_ok"] and r["standin_gather_ok_all_ranks"]
@@ -104,6 +104,14 @@ def test_bench_two_rank_control_path_end_to_end():
     assert sr["clips_per_gpu"] == 8 and sr["n1_same_shape_mel_frames_per_s"] > 0
     assert abs(sr["efficiency"] - r["value"] / (2 * sr["n1_same_shape_mel_frames_per_s"])) < 1e-3
     assert "stand-in" in r["data"]
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """Without --full an N-rank line is the headline alone: the same timed steps and gather, no `scaling_reference` leg."""
+    r = _bench_standin(2)
+    assert r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0
+    assert r["standin_gather_ok"] and r["standin_gather_ok_all_ranks"] and r["config"]["global_clips"] == 16
+    assert "scaling_reference" not in r
 
 
 def test_bench_dump_outputs_after_the_timed_steps(tmp_path):
