@@ -71,8 +71,13 @@ enum {
                              out[m][j] = (acc_v + b_v) * gelu_erf(acc_g + b_g); out has N/2 cols */
   V2A_EPI_RESID = 3,      /* out = resid + acc + bias             (text/frames streams, cross-condition) */
   V2A_EPI_GATE_RESID = 4, /* out = resid + gate[n] * (acc + bias) (AdaLNZero x3:546-551 + residual x3:1128) */
-  V2A_EPI_GEGLU_TANH = 5  /* v2a_gemm_skinny_f32 only (v2a_gemm rejects it): the GEGLU row packing with value = wi_1, gate = wi_0,
+  V2A_EPI_GEGLU_TANH = 5, /* v2a_gemm_skinny_f32 only (v2a_gemm rejects it): the GEGLU row packing with value = wi_1, gate = wi_0,
                              out[m][j] = (acc_v + b_v) * gelu_new(acc_g + b_g), gelu_new(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) */
+  V2A_EPI_GELU = 6        /* ABI 8, additive: out = gelu_erf(acc + bias), gelu_erf(x) = 0.5 x (1 + erf(x / sqrt(2))) -- CLIPMLP.fc1 + activation_fn
+                             of the CLIP image encoder (transformers CLIPEncoderLayer, reached from x3:1714, 1733-1735).  fp32 compute (exact erff,
+                             fp32 output) or split operands (the bf16x3 mode; output fp32 with exact erff, or out_dtype V2A_BF16_SPLIT: row m =
+                             [hi of the N outputs | lo of them], ldo >= 2N, erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7, the fc2 operand
+                             written directly).  Plain bf16 compute refuses it. */
 };
 
 typedef struct v2a_gemm_args {
@@ -144,8 +149,8 @@ typedef struct v2a_gemm_args {
   int32_t row_ssq_parts, row_norm_dim;
   /* non-zero: the out_bf16 shadow is written in the V2A_BF16_SPLIT layout, row m = [hi_0 .. hi_{N-1} | lo_0 .. lo_{N-1}] of the
    * (gamma-scaled, when norm_gamma is given) fp32 result, ld_out_bf16 >= 2 * N: the operand of a later split-bf16 GEMM without a
-   * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU epilogue only): out row m = [hi | lo] planes of the N/2
-   * hidden values, ldo >= N, exact erf GELU. */
+   * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU and GELU epilogues only): out row m = [hi | lo] planes of the N/2
+   * hidden values, ldo >= N (GELU: of the N values, ldo >= 2N). */
   int32_t out_bf16_split;
   /* ABI 8, split operands / split shadow only.  a_lo_offset[s]: elements from the hi plane of a row of segment s to its lo plane; 0 = ka[s], the
    * layout [hi k | lo k].  out_bf16_lo_offset: the same for the shadow row; 0 = N.  They let ONE buffer of rows [x_hi | s_hi | x_lo | s_lo] serve
@@ -472,6 +477,61 @@ int v2a_t5_attention(const v2a_t5_attn_args* args, v2a_stream_t stream);
  * Replaces: the Linears of transformers T5Attention (fused q|k|v, o) and T5DenseGatedActDense (wi_0 | wi_1, wo) with the
  * residual add of T5LayerSelfAttention / T5LayerFF, reached from x3:1413,1654. */
 int v2a_gemm_skinny_f32(const v2a_gemm_args* args, v2a_stream_t stream);
+
+/* =======================================================================================
+ * N3: CLIP ViT image encoder, `video_encoder="clip_vit"` of the reference: transformers CLIPImageProcessor() +
+ * CLIPVisionModelWithProjection (IP-Adapter sdxl_models/image_encoder = OpenCLIP ViT-bigG/14), x3:1423-1425, 1714, 1733-1735.
+ * Per layer: h += out_proj(Attn(LN1(h))); h += fc2(gelu(fc1(LN2(h)))); image_embeds = visual_projection(post_layernorm(h[CLS])).
+ * The Linears are v2a_gemm calls (fc1 with V2A_EPI_GELU); the kernels below are the rest.
+ * ===================================================================================== */
+
+/* Pillow BICUBIC resize (Image.resize(..., BICUBIC, reducing_gap=None), the 8-bit path of ImagingResample), horizontal pass:
+ *   tmp[f][y - y0][x][c] = clip8((2^21 + sum_{i < bounds[2x+1]} frames[f][y][bounds[2x] + i][c] * coef[x * ksize + i]) >> 22)
+ * frames (F, H, W, 3) uint8 RGB; tmp (F, rows, S, 3) uint8 for the input rows y0 <= y < y0 + rows and the S output columns of the
+ * centre crop.  bounds / coef: Pillow's precompute_coeffs + normalize_coeffs_8bpc for those columns (22 fraction bits), built on
+ * the host; the CALLER guarantees bounds[2x] + bounds[2x+1] <= W.
+ * Replaces: the resize of CLIPImageProcessor.preprocess (transformers image_transforms.resize -> PIL), reached from x3:1714. */
+int v2a_clip_resize_h(const uint8_t* frames, int32_t F, int32_t H, int32_t W, uint8_t* tmp, int32_t y0, int32_t rows, int32_t S,
+                      const int32_t* bounds, const int32_t* coef, int32_t ksize, v2a_stream_t stream);
+/* Vertical pass of the same resize over tmp, for the S crop rows (bounds relative to row y0 of tmp; the CALLER guarantees
+ * bounds[2y] + bounds[2y+1] <= rows), then rescale + normalise through lut[c * 256 + u] (the processor's fp32 value of byte u in
+ * channel c, built on the host), written as the patch matrix of the stride-P patch convolution:
+ *   patches[f * (1 + (S/P)^2) + 1 + (y/P) * (S/P) + x/P][c * P * P + (y % P) * P + x % P]
+ * Row f * (1 + (S/P)^2) (the class-token slot) and columns >= 3 P^2 are never written: the caller zeroes them once.  out_dtype
+ * V2A_F32 (ldp floats per row) or V2A_BF16_SPLIT (hi at the column, lo lo_offset bf16 further, ldp bf16 per row).  crop (or NULL)
+ * receives the uint8 crop (F, S, S, 3).  Replaces: resize + center_crop + rescale + normalize of CLIPImageProcessor (x3:1423, 1714). */
+int v2a_clip_resize_v(const uint8_t* tmp, int32_t F, int32_t rows, int32_t S, int32_t P, const int32_t* bounds, const int32_t* coef,
+                      int32_t ksize, const float* lut, void* patches, int64_t ldp, int32_t out_dtype, int64_t lo_offset, uint8_t* crop,
+                      v2a_stream_t stream);
+/* h[r][c] = pos[r % T][c] + (r % T == 0 ? cls[c] : 0) for rows r < rows: the class / position embedding rows of the residual stream,
+ * onto which the patch GEMM (RESID epilogue over the patch matrix above, whose class rows are zero) adds the patch embeddings.
+ * Replaces: CLIPVisionEmbeddings (class_embedding, position_embedding) reached from x3:1733-1735. */
+int v2a_clip_embed_init(float* h, int64_t ldh, int64_t rows, int32_t T, int32_t d, const float* cls, const float* pos,
+                        v2a_stream_t stream);
+/* nn.LayerNorm: y[r] = (x[r] - mean) / sqrt(var + eps) * gamma + beta (biased variance, fp32, centred two-pass), d % 4 == 0,
+ * d <= 4096.  y_dtype V2A_F32 or V2A_BF16_SPLIT (row = [hi | lo] halves of ldy >= 2d bf16, lo at ldy / 2: columns d .. ldy/2 - 1 of
+ * each half are not written, a zero K pad for the GEMM).  ldx is free: ldx = T * d with rows = F
+ * normalises the class rows only.  Replaces: CLIPVisionTransformer.pre_layrnorm / post_layernorm and CLIPEncoderLayer
+ * layer_norm1 / layer_norm2 (transformers), reached from x3:1733-1735. */
+int v2a_clip_layernorm(const float* x, int64_t ldx, void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t d, const float* gamma,
+                       const float* beta, float eps, v2a_stream_t stream);
+/* Bidirectional, unmasked attention core, fp32 (VALU FMA, online softmax over 32-key blocks) in every compute mode:
+ *   o[b,i,h,:] = softmax_j(scale * q[b,i,h,:] . k[b,j,h,:]) v[b,j,h,:]
+ * q / k / v (fp32) are addressed as base + b * batch_stride + token * row_stride + h * d_head (+c) -- read in place from the fused
+ * [q | k | v] GEMM output; d_head a multiple of 4, <= 112 (104 for ViT-bigG), N <= 4096 (257 at 224 px, 577 at 336 px).
+ * out_split = 0: fp32 out; 1: bf16 out row = [hi of the H * d_head outputs | lo of them], the lo plane at out_row_stride / 2 (the
+ * out-projection's split operand; columns past H * d_head in each half are not written).
+ * Replaces: transformers CLIPAttention minus its Linears (eager path), reached from x3:1733-1735. */
+typedef struct v2a_clip_attn_args {
+  const float *q, *k, *v;
+  void* out;
+  int64_t row_stride, batch_stride;          /* q / k / v, in floats          */
+  int64_t out_row_stride, out_batch_stride;  /* in elements of out            */
+  int32_t B, H, N, d_head;
+  float scale;
+  int32_t out_split;
+} v2a_clip_attn_args;
+int v2a_clip_attention(const v2a_clip_attn_args* args, v2a_stream_t stream);
 
 #ifdef __cplusplus
 }

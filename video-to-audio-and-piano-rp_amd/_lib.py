@@ -21,6 +21,7 @@ CSRC = os.path.join(_HERE, "csrc")
 F32, BF16, BF16_SPLIT = 0, 1, 2
 EPI_STORE, EPI_SIGMOID, EPI_GEGLU, EPI_RESID, EPI_GATE_RESID = 0, 1, 2, 3, 4
 EPI_GEGLU_TANH = 5           # v2a_gemm_skinny_f32 only
+EPI_GELU = 6                 # fp32 compute or split operands (CLIP's MLP)
 
 _lib = None
 
@@ -90,6 +91,13 @@ class T5AttnArgs(C.Structure):
     ]
 
 
+class ClipAttnArgs(C.Structure):
+    """Mirror of `v2a_clip_attn_args`."""
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+                ("row_stride", C.c_int64), ("batch_stride", C.c_int64), ("out_row_stride", C.c_int64), ("out_batch_stride", C.c_int64),
+                ("B", C.c_int32), ("H", C.c_int32), ("N", C.c_int32), ("d_head", C.c_int32), ("scale", C.c_float), ("out_split", C.c_int32)]
+
+
 class RollHeadArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x2", "x3", "x4", "x5")] + [("B", C.c_int32), ("P", C.c_int32)] +
                 [(f"frb{i}_{n}", C.c_void_p) for i in (4, 3, 2) for n in ("w1t", "b1", "w2t", "b2")] +
@@ -103,6 +111,7 @@ EXPORTS = [
     "v2a_apg_reduce", "v2a_cfg_euler", "v2a_step_advance", "v2a_cast_bf16", "v2a_split_bf16",
     "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand", "v2a_frames_pack_split", "v2a_pool2d_split",
     "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2", "v2a_t5_rmsnorm", "v2a_t5_attention", "v2a_gemm_skinny_f32",
+    "v2a_clip_resize_h", "v2a_clip_resize_v", "v2a_clip_embed_init", "v2a_clip_layernorm", "v2a_clip_attention",
 ]
 
 
@@ -157,6 +166,11 @@ def _declare(lib):
     lib.v2a_t5_rmsnorm.argtypes = [vp, i64, vp, i32, vp, i64, vp, i64, i64, i32, vp, f32, vp]
     lib.v2a_t5_attention.argtypes = [C.POINTER(T5AttnArgs), vp]
     lib.v2a_gemm_skinny_f32.argtypes = [C.POINTER(GemmArgs), vp]
+    lib.v2a_clip_resize_h.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, i32, vp]
+    lib.v2a_clip_resize_v.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, i32, i64, vp, vp]
+    lib.v2a_clip_embed_init.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp]
+    lib.v2a_clip_layernorm.argtypes = [vp, i64, vp, i64, i32, i64, i32, vp, vp, f32, vp]
+    lib.v2a_clip_attention.argtypes = [C.POINTER(ClipAttnArgs), vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -308,7 +322,7 @@ def _launch(key, flops, nbytes, call):
         _prof.launch(key, flops, nbytes, lambda: check(call()))
 
 
-_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh"}
+_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh", 6: "gelu"}
 
 
 # ------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ FLAN-T5 context `<video>.t5.npz` (arr_0 = (nc, 1024) hidden states) unless `--t5
 local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec latent that the reference feeds to
 `vocos.decode` (src/inference_v2a.py / predict.py:277-278).
 
+  --clip DIR         encode the videos that have no CLIP feature cache (moviepy decode, HIP CLIP encoder of this rank's GPU)
   --t5-engine hip    run --t5 on the HIP FLAN-T5 encoder (t5.py) of this rank's GPU instead of transformers on the CPU
   --piano            V2P (src/inference_v2p.py): the cached grey frames `<video>.generated_frames_raw.2.npz` (features.py) go
                      through the HIP Video2Roll encoder; the checkpoint must hold `video2roll_net.*`
@@ -41,12 +42,25 @@ def read_scp(path: str, start: int, end: int, step: int = 1):
     return out[start:end:step]
 
 
-def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None):
+def read_frames_with_moviepy(video_path: str):
+    """x3:98-113: every decoded frame, (F, H, W, 3) uint8 RGB, and the clip duration in seconds (moviepy, imported on use)."""
+    from moviepy.editor import VideoFileClip
+    clip = VideoFileClip(video_path)
+    return np.array(list(clip.iter_frames())), clip.duration
+
+
+def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None):
+    """clip_encode: optional `video_path -> (image_embeds, duration)` that makes a missing `<video>.generated.npz` (--clip)."""
     from .collate import ClipRequest
-    from .features import feature_cache_path, load_clip_cache, resample_clip_features
+    from .features import feature_cache_path, load_clip_cache, resample_clip_features, save_clip_cache
     reqs = []
     for vp, cap in items:
-        emb, duration = load_clip_cache(feature_cache_path(vp))
+        fp = feature_cache_path(vp)
+        if not os.path.exists(fp):
+            if clip_encode is None:
+                raise FileNotFoundError(f"{fp}: no cached CLIP features for {vp}; pass --clip DIR (with moviepy installed) to encode it")
+            save_clip_cache(fp, *clip_encode(vp))                                # x3:1706-1793
+        emb, duration = load_clip_cache(fp)
         n = min(n_frames, int(duration * 24000) // 320) if n_frames > 0 else int(duration * 24000) // 320
         clip = resample_clip_features(emb.float(), duration, n)
         prompt = "" if drop_prompt else cap
@@ -82,6 +96,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--t5", default=None, help="local FLAN-T5 directory (reference: ./ckpts/flan-t5-large)")
     ap.add_argument("--t5-engine", default="torch", choices=["torch", "hip"],
                     help="what runs --t5: stock transformers on the CPU (torch) or the HIP T5Encoder on this rank's GPU (hip)")
+    ap.add_argument("--clip", default=None, help="local CLIP image encoder directory (IP-Adapter sdxl_models/image_encoder): videos "
+                    "without <video>.generated.npz are decoded with moviepy and encoded on this rank's GPU, and the cache is written")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the cached piano frames through the Video2Roll encoder")
@@ -127,6 +143,16 @@ def main(argv=None):
             b = tok([prompt], max_length=tok.model_max_length, padding=True, truncation=True, return_tensors="pt")
             with torch.no_grad():
                 return enc(input_ids=b.input_ids, attention_mask=b.attention_mask)[0][0]
+    clip_encode = None
+    if a.clip:
+        from .clip import CLIPImageEncoder
+        cenc = CLIPImageEncoder.from_pretrained(a.clip, torch.device("cuda", local))
+        def clip_encode(vp):
+            try:
+                frames, duration = read_frames_with_moviepy(vp)
+            except ImportError as e:
+                raise FileNotFoundError(f"{vp}: no cached CLIP features and moviepy is not installed to decode it for --clip") from e
+            return cenc(frames).cpu(), duration
     vocoder = None
     if a.encodec and rank == 0:
         from .encodec import EncodecDecoder
@@ -140,7 +166,7 @@ def main(argv=None):
         s, e, per = shard_range(len(chunk), rank, world)
         mine = chunk[s:e]
         if mine:
-            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode), channels, gen)
+            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode), channels, gen)
             frames = None
             if a.piano:
                 from .features import load_piano_frames

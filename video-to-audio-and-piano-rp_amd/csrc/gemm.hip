@@ -148,6 +148,9 @@ int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
     case V2A_EPI_SIGMOID:
       if (out_f32) return launch<T, A_F32, V2A_EPI_SIGMOID, float, BM, BN>(p, s);
       break;
+    case V2A_EPI_GELU:
+      if (out_f32) return launch<T, A_F32, V2A_EPI_GELU, float, BM, BN>(p, s);
+      break;
     case V2A_EPI_GEGLU:
       if (out_f32) {
         if constexpr (sizeof(T) == 4) return launch<T, A_F32, V2A_EPI_GEGLU, float, BM, BN>(p, s);
@@ -515,6 +518,10 @@ int dispatch_s3(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
         if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GEGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
       }
       break;
+    case V2A_EPI_GELU:
+      if (out_f32) return launch_dma<V2A_EPI_GELU, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GELU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      break;
     case V2A_EPI_RESID:
       if (out_f32) return launch_dma<V2A_EPI_RESID, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
       break;
@@ -635,7 +642,14 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
       V2A_REQUIRE(a->a_lo_offset[sg] == 0, "v2a_gemm: a_lo_offset goes with split operands");
   }
   p.out_split = a->out_dtype == V2A_BF16_SPLIT ? 1 : 0;
-  if (p.out_split) V2A_REQUIRE(a->epilogue == V2A_EPI_GEGLU && a->ldo >= a->N, "v2a_gemm: out_dtype V2A_BF16_SPLIT goes with the GEGLU epilogue and ldo >= N");
+  if (p.out_split)
+    V2A_REQUIRE((a->epilogue == V2A_EPI_GEGLU && a->ldo >= a->N) || (a->epilogue == V2A_EPI_GELU && split_in && a->ldo >= 2 * (int64_t)a->N),
+                "v2a_gemm: out_dtype V2A_BF16_SPLIT goes with the GEGLU epilogue and ldo >= N, or GELU on split operands and ldo >= 2N");
+  // GELU (CLIP's MLP): the exact-fp32 kernel and the split-operand kernels carry it; plain bf16 compute has no GELU instantiation
+  if (a->epilogue == V2A_EPI_GELU)
+    V2A_REQUIRE((a->compute_dtype == V2A_F32 || split_in) && !a->out_bf16 && !a->relu && !a->rope_table && !a->a_row_offset && !a->out_row_offset &&
+                    !a->norm_gamma && !a->norm_ssq && !a->row_ssq,
+                "v2a_gemm: the GELU epilogue needs fp32 compute or split operands, dense rows, and none of out_bf16 / relu / rope / norm folding");
   p.resid = a->resid;
   p.ldr = a->ldr;
   p.gate = a->gate;

@@ -313,6 +313,9 @@ int v2a_detail::launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dt
       return out_f32 ? launch_8ph<V2A_EPI_STORE, float>(p, s) : launch_8ph<V2A_EPI_STORE, bf16_t>(p, s);
     case V2A_EPI_GEGLU:
       return out_f32 ? launch_8ph<V2A_EPI_GEGLU, float>(p, s) : launch_8ph<V2A_EPI_GEGLU, bf16_t>(p, s);
+    case V2A_EPI_GELU:     // v2a_gemm admits it here with split operands only (fp32 output, or hi | lo planes through bf16_t + out_split)
+      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_GELU, float>(p, s) : launch_8ph<V2A_EPI_GELU, bf16_t>(p, s);
+      break;
     case V2A_EPI_RESID:
       if (out_f32) return launch_8ph<V2A_EPI_RESID, float>(p, s);
       break;

@@ -251,6 +251,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
           float v = acc[i][j][jj];
           if (p.bias) v += p.bias[n];
           if constexpr (EPI == V2A_EPI_SIGMOID) v = sigmoid_f(v);
+          if constexpr (EPI == V2A_EPI_GELU) v = gelu_erf_f(v);
           if constexpr (EPI == V2A_EPI_RESID) v += p.resid[(int64_t)m * p.ldr + n];
           if constexpr (EPI == V2A_EPI_GATE_RESID) v = p.resid[(int64_t)m * p.ldr + n] + gvec[n] * v;
           if (p.relu) v = fmaxf(v, 0.f);
@@ -537,6 +538,12 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = sigmoid_f(v[e]);
         }
+        if constexpr (EPI == V2A_EPI_GELU) {
+          // fp32 output: exact erff (fp32 parity of CLIPMLP); hi | lo planes: Abramowitz-Stegun erf (|error| <= 1.5e-7, below the
+          // 2^-17 the planes keep), as the GEGLU epilogue's split form
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = sizeof(OutT) == 2 ? gelu_fast_f(v[e]) : gelu_erf_f(v[e]);
+        }
         if constexpr (EPI == V2A_EPI_STORE) {
           if (p.rope && n < p.rope_cols) {
             // interleaved RoPE (A6): columns (n, n+1) and (n+2, n+3) are pairs (n & 63) / 2 and +1 of this head
@@ -575,6 +582,14 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
           *reinterpret_cast<bf16x4*>(out + o_out + n) = o;
+          if constexpr (EPI == V2A_EPI_GELU) {
+            if (p.out_split) {       // bf16x3 mode: the lo plane, N columns after the hi plane (the next GEMM's split operand)
+              bf16x4 lo;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) lo[e] = (bf16_t)(v[e] - (float)o[e]);
+              *reinterpret_cast<bf16x4*>(out + o_out + p.N + n) = lo;
+            }
+          }
         } else {
           *reinterpret_cast<f32x4*>(out + o_out + n) = v;
           if (out2) {

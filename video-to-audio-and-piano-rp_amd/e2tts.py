@@ -16,10 +16,12 @@ There is no fallback path: without libv2a_cfm.so (gfx950) construction raises.
 """
 from __future__ import annotations
 
+import os
 from collections import namedtuple
 from pathlib import Path
 from typing import Callable
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -210,6 +212,7 @@ class E2TTS:
         self._engine: DiTEngine | None = None
         self._v2r_sd, self._v2r = None, None      # optional Video2Roll frame encoder (video2roll_net.*, x3:1523)
         self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
+        self._clip = None                         # optional CLIP image encoder (load_image_encoder, x3:1423-1425)
         L.lib()  # no library -> no sampler
 
     # ---- nn.Module-like surface used by the callers (predict.py:156-170) -------------------
@@ -221,6 +224,8 @@ class E2TTS:
         self._device = torch.device(device)
         self._engine = None
         self._v2r = None
+        if self._clip is not None:
+            self._clip.to(self._device)        # weights follow, buffers and tables are rebuilt on first use
         return self
 
     def eval(self):
@@ -314,6 +319,46 @@ class E2TTS:
         self._t5 = enc
         return enc
 
+    def load_image_encoder(self, src, **kw):
+        """The CLIP image encoder behind `video_frames=` and uncached `video_paths` (x3:1423-1425, 1714, 1733-1735): a
+        `CLIPImageEncoder`, a local HF directory (IP-Adapter sdxl_models/image_encoder) or a state dict (CLIPVisionModelWithProjection
+        keys, or a reference checkpoint with `image_encoder.*`).  `kw` go to the CLIPImageEncoder constructor (compute, chunk,
+        config).  Only video_encoder="clip_vit" has this encoder."""
+        if self.video_encoder != "clip_vit":
+            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit' has the HIP CLIP encoder)")
+        from .clip import CLIPImageEncoder
+        if isinstance(src, CLIPImageEncoder):
+            enc = src
+        elif isinstance(src, (str, Path)):
+            enc = CLIPImageEncoder.from_pretrained(str(src), self._device, **kw)
+        elif isinstance(src, dict):
+            enc = CLIPImageEncoder(src, self._device, **kw)
+        else:
+            raise TypeError(f"load_image_encoder: a CLIPImageEncoder, a directory or a state dict, got {type(src).__name__}")
+        self._clip = enc
+        return enc
+
+    def _encode_video_frames(self, clips) -> list:
+        """[(frames uint8 (F, H, W, 3), duration) or None] -> [(image_embeds (F, dim) float32 on the CPU, duration) or None]; the
+        frames of all clips of one frame size go through the encoder in one batched pass."""
+        out = [None] * len(clips)
+        groups: dict[tuple, list[int]] = {}
+        arrs = {}
+        for i, c in enumerate(clips):
+            if c is None:
+                continue
+            fr = c[0] if torch.is_tensor(c[0]) else torch.from_numpy(np.ascontiguousarray(c[0]))
+            arrs[i] = fr
+            groups.setdefault(tuple(fr.shape[1:]), []).append(i)
+        for idx in groups.values():
+            emb = self._clip(torch.cat([arrs[i] for i in idx], 0)).cpu()
+            o = 0
+            for i in idx:
+                n = arrs[i].shape[0]
+                out[i] = (emb[o:o + n], float(clips[i][1]))
+                o += n
+        return out
+
     def _get_context(self, prompt, context, context_mask, b, video_drop_prompt=None):
         if context is None:
             if prompt is None:
@@ -401,13 +446,17 @@ class E2TTS:
                return_raw_output=None, save_to_filename=None, prompt=None, video_drop_prompt=None,
                audio_drop_prompt=None, video_paths=None, frames=None, midis=None,
                # build-side extensions
-               y0=None, text_embed=None, context=None, context_mask=None, frames_embed=None, trajectory_out=None):
+               y0=None, text_embed=None, context=None, context_mask=None, frames_embed=None, trajectory_out=None, video_frames=None):
         """x3:2127-2305.  With lens == duration (every shipped call, predict.py:261-263) `cond` (b, n, C) only fixes shape and
         device.  With lens[0] != duration[0] it is the audio prompt of the infilling branch (x3:2196-2231, 2260-2261; needs
         if_cond_proj_in=True): zero-padded to the longest duration, masked to lens, added through cond_proj_in at every
         evaluation (dropped in the null pass), and returned unchanged in the first lens[b] frames.
         `trajectory_out`: optional list that receives a device copy of y at every grid point (the `trajectory` of
-        x3:2255, of which the reference keeps only [-1]); test aid, adds a copy per step."""
+        x3:2255, of which the reference keeps only [-1]); test aid, adds a copy per step.
+        `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) per clip (or None), encoded by the CLIP image encoder
+        (load_image_encoder): with `video_paths` only the clips without a feature cache are encoded -- in one batched pass -- and
+        their caches written (x3:1706-1793; an existing cache wins); without `video_paths` the embeddings are resampled to the
+        latent rate and nothing is written."""
         self.eval()
         if cond.ndim == 2:
             raise NotImplementedError("raw-wave `cond` needs mel_spec_module, which the shipped config does not set")
@@ -436,10 +485,37 @@ class E2TTS:
                 text_embed = self.video_encoder_fn(video_paths, cond_seq_len)
             elif video_paths is not None:
                 # cached CLIP features next to the videos, resampled to the latent rate (encode_video's cache branch,
-                # x3:1796-1813); the CLIP encoder itself is outside the accelerated path
-                from .features import encode_video_cached
+                # x3:1796-1813); with video_frames and the image encoder, missing caches are encoded first (x3:1706-1793)
+                from .features import encode_video_cached, feature_cache_path
+                encoder_fn = None
+                if video_frames is not None:
+                    if self._clip is None:
+                        raise RuntimeError("video_frames needs the CLIP image encoder: call load_image_encoder first")
+                    if len(video_frames) != len(video_paths):
+                        raise ValueError(f"video_frames: {len(video_frames)} entries for {len(video_paths)} video_paths")
+                    plain = [vp[0] if isinstance(vp, tuple) else vp for vp in video_paths]
+                    todo = [fr if vp is not None and fr is not None and not os.path.exists(feature_cache_path(vp, self.video_encoder)) else None
+                            for vp, fr in zip(plain, video_frames)]
+                    done = {vp: e for vp, e in zip(plain, self._encode_video_frames(todo)) if e is not None}
+                    def encoder_fn(vp):
+                        if vp not in done:
+                            raise FileNotFoundError(f"{feature_cache_path(vp, self.video_encoder)}: no cached CLIP features and no frames for {vp}")
+                        return done[vp]
                 text_embed = encode_video_cached(video_paths, cond_seq_len, dim=cfgm.dim_text, video_encoder=self.video_encoder,
-                                                 sampling_rate=self.sampling_rate or 24000, frame_size=self.frame_size)
+                                                 sampling_rate=self.sampling_rate or 24000, frame_size=self.frame_size,
+                                                 encoder_fn=encoder_fn)
+            elif video_frames is not None:
+                if self._clip is None:
+                    raise RuntimeError("video_frames needs the CLIP image encoder: call load_image_encoder first")
+                if len(video_frames) != batch:
+                    raise ValueError(f"video_frames: {len(video_frames)} entries for a batch of {batch}")
+                from .features import resample_clip_features
+                rows = []
+                for e in self._encode_video_frames(list(video_frames)):
+                    rows.append(torch.zeros(cond_seq_len, cfgm.dim_text) if e is None else
+                                resample_clip_features(e[0], e[1], cond_seq_len, sampling_rate=self.sampling_rate or 24000,
+                                                       frame_size=self.frame_size))
+                text_embed = torch.stack(rows, 0)
             elif torch.is_tensor(text) and text.ndim == 3:
                 text_embed = text
             else:

@@ -7,7 +7,8 @@ video and its output is kept next to the video as an `.npz` written by
     arr_0 : (n_video_frames, dim) float embeddings, one per decoded video frame
     arr_1 : 0-d float, clip duration in seconds
 and every later call only resamples those rows to the 75 Hz latent rate by nearest video frame
-(x3:1803-1813).  The encoder itself (ViT-bigG) is outside the accelerated path.
+(x3:1803-1813).  A missing cache is made by the HIP ViT-bigG encoder (clip.py: 0.75 s per 250-frame clip in bf16x3) through
+`encode_video_cached(..., encoder_fn=)`, which E2TTS.sample(video_frames=...) and the CLI's --clip drive.
 """
 from __future__ import annotations
 

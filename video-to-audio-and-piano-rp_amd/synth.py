@@ -176,3 +176,65 @@ def random_t5_encoder_state_dict(config: dict, seed: int = 0, amplify: float = 1
         sd[P + "1.layer_norm.weight"] = t(1.0 + 0.1 * rs.standard_normal(d))
     sd["encoder.final_layer_norm.weight"] = t(1.0 + 0.1 * rs.standard_normal(d))
     return sd
+
+
+# OpenCLIP ViT-bigG/14 as CLIPVisionModelWithProjection: IP-Adapter sdxl_models/image_encoder, the reference's "clip_vit" (x3:1423-1425)
+VIT_BIGG_14 = dict(hidden_size=1664, intermediate_size=8192, num_hidden_layers=48, num_attention_heads=16, image_size=224, patch_size=14,
+                   projection_dim=1280, layer_norm_eps=1e-5, hidden_act="gelu", num_channels=3)
+
+
+def random_clip_vision_state_dict(config: dict, seed: int = 0, outlier: float = 0.0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `CLIPVisionModelWithProjection(CLIPVisionConfig(**config))` (the IP-Adapter image
+    encoder is not reachable offline).  numpy PCG64 float32 normals: the same tensors on any machine.  Matrices ~ N(0, 1/fan_in),
+    biases and LayerNorm beta ~ 0.1 N, gamma ~ 1 + 0.1 N, so every epilogue term is exercised.  `outlier > 0` scales the out_proj
+    and fc2 rows (and biases) of a few residual channels by `outlier`, which drives those channels to |h| ~ 1e2 over the layers, as
+    real CLIP ViTs carry them."""
+    import numpy as np
+
+    c = dict(config)
+    d, dff, nl, P, S = c["hidden_size"], c["intermediate_size"], c["num_hidden_layers"], c["patch_size"], c["image_size"]
+    T = 1 + (S // P) ** 2
+    rng = np.random.default_rng(seed)
+    nrm = lambda shp, s: torch.from_numpy(rng.standard_normal(shp, dtype=np.float32) * np.float32(s))
+    hot = torch.from_numpy(rng.choice(d, size=4, replace=False)) if outlier > 0 else None
+
+    def boost(w, b):
+        if hot is not None:
+            w[hot] *= outlier
+            b[hot] *= outlier
+        return w, b
+
+    E = "vision_model.embeddings."
+    sd = {E + "class_embedding": nrm((d,), 0.5), E + "patch_embedding.weight": nrm((d, c.get("num_channels", 3), P, P), 1.0 / math.sqrt(3 * P * P)),
+          E + "position_embedding.weight": nrm((T, d), 0.2)}
+    sd["vision_model.pre_layrnorm.weight"] = 1.0 + nrm((d,), 0.1)
+    sd["vision_model.pre_layrnorm.bias"] = nrm((d,), 0.1)
+    for i in range(nl):
+        p = f"vision_model.encoder.layers.{i}."
+        for n in ("q", "k", "v"):
+            sd[p + f"self_attn.{n}_proj.weight"] = nrm((d, d), 1.0 / math.sqrt(d))
+            sd[p + f"self_attn.{n}_proj.bias"] = nrm((d,), 0.1)
+        sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"] = boost(nrm((d, d), 1.0 / math.sqrt(d)), nrm((d,), 0.1))
+        sd[p + "layer_norm1.weight"], sd[p + "layer_norm1.bias"] = 1.0 + nrm((d,), 0.1), nrm((d,), 0.1)
+        sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = nrm((dff, d), 1.0 / math.sqrt(d)), nrm((dff,), 0.1)
+        sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = boost(nrm((d, dff), 1.0 / math.sqrt(dff)), nrm((d,), 0.1))
+        sd[p + "layer_norm2.weight"], sd[p + "layer_norm2.bias"] = 1.0 + nrm((d,), 0.1), nrm((d,), 0.1)
+    sd["vision_model.post_layernorm.weight"] = 1.0 + nrm((d,), 0.1)
+    sd["vision_model.post_layernorm.bias"] = nrm((d,), 0.1)
+    sd["visual_projection.weight"] = nrm((c["projection_dim"], d), 1.0 / math.sqrt(d))
+    return sd
+
+
+def synthetic_video_frames(n: int, h: int, w: int, seed: int = 0) -> "np.ndarray":
+    """(n, h, w, 3) uint8 RGB test frames: smooth per-frame colour gradients plus noise, so the resize filters really average."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.linspace(0, 1, h), np.linspace(0, 1, w), indexing="ij")
+    out = np.empty((n, h, w, 3), np.uint8)
+    for f in range(n):
+        a = rng.uniform(-1, 1, (3, 3))
+        base = 128 + 90 * np.tanh(a[:, 0, None, None] * yy + a[:, 1, None, None] * xx + a[:, 2, None, None] * np.sin(6 * xx * yy + f))
+        img = base.transpose(1, 2, 0) + rng.normal(0, 20, (h, w, 3))
+        out[f] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    return out
