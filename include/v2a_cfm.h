@@ -440,6 +440,29 @@ int v2a_lstm2(const float* gates_x0, const float* w_hh0, const float* w_ih1, con
               const float* resid, float* y, int32_t T, int32_t H, int32_t* workspace, v2a_stream_t stream);
 
 /* =======================================================================================
+ * Encodec 24 kHz encoder, `EncodecWrapper.forward` x3:428-432 (predict.py:222; arithmetic: transformers EncodecEncoder): the
+ * decoder's mirror.  A strided Conv1d(k = 2r, stride r) on a time-major [T][C] buffer is ONE v2a_gemm whose A rows overlap with
+ * lda = r*C, K = k*C, M = ceil(T / r), over a buffer padded by v2a_elu_pad_lr; the LSTM is v2a_lstm2.  ABI 8, additive.
+ * ===================================================================================== */
+
+/* v2a_elu_pad with a pad on both sides: out[pad_left + t][c] = act ? ELU(x[t][c]) : x[t][c] for t < T, preceded by pad_left
+ * reflected rows (row pad_left - i mirrors row i) and followed by pad_right reflected rows (row pad_left + T - 1 + i mirrors row
+ * T - 1 - i), as F.pad(x, (pad_left, pad_right), "reflect") does: EncodecConv1d pads k - stride samples in front and, where the
+ * length is not a multiple of the stride, up to stride - 1 behind.  out holds T + pad_left + pad_right rows.  C % 4 == 0, both
+ * pads < T (V2A_ERR_ARG otherwise). */
+int v2a_elu_pad_lr(const float* x, float* out, int64_t T, int32_t C, int32_t pad_left, int32_t pad_right, int32_t act,
+                   v2a_stream_t stream);
+
+/* Layers 0 and 1 of the encoder in one pass: wave (n samples) -> out [n][32] time-major,
+ *   x0 = Conv1d(1->32, k7)(reflect-pad 6 in front);  out = shortcut(x0) + block.3(ELU(block.1(ELU(x0), reflect-pad 2 in front)))
+ * with block.1 = Conv1d(32->16, k3), block.3 = Conv1d(16->32, k1), shortcut = Conv1d(32->32, k1).  n >= 8.
+ * params: 3376 floats, 16-byte aligned: stem weight [32][7], stem bias [32], shortcut weight [32][32], (shortcut bias + block.3
+ * bias) [32], block.1 weight [16][3][32] (out, tap, in), block.1 bias [16], block.3 weight [32][16].
+ * One thread per sample (~3.7 k VALU FMAs, weights at lane-uniform addresses), one coalesced write of the result.  Replaces the
+ * zero-padded K = 16 stem GEMM and the nine passes of the generic path over [n][16..32] buffers. */
+int v2a_encodec_stage0(const float* wave, const float* params, float* out, int64_t n, v2a_stream_t stream);
+
+/* =======================================================================================
  * FLAN-T5 prompt encoder: `E2TTS.encode_text` x3:1648-1657 running transformers `T5EncoderModel` (x3:1413, 1654), fp32.
  * Per block: h += o(Attn(LN1(h))); h += wo(gelu_new(wi_0 LN2(h)) * wi_1 LN2(h)); then final_layer_norm.
  * ===================================================================================== */

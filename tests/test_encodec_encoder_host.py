@@ -1,0 +1,215 @@
+"""CPU: host side of the Encodec encoder (v2a_amd.EncodecEncoder) -- key layout and generator against the library, the padding
+plan against the library's own padding arithmetic, the strided-convolution packing, the new C-ABI symbols and their argument
+checks, the length limit, and the raw-wave branch of E2TTS.sample."""
+import glob
+import os
+import re
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from v2a_amd.encodec import (EncodecEncoder, conv_padding, encoder_frames, encoder_padding_plan,  # fails at import without the feature
+                             expected_encoder_state_dict_shapes)
+from v2a_amd.synth import random_encodec_encoder_state_dict, synthetic_wave
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LENGTHS = (1921, 2333, 196161, 239999, 240000, 240001)
+
+
+@pytest.fixture(scope="module")
+def library_encoder():
+    tf = pytest.importorskip("transformers")
+    return tf.EncodecModel(tf.EncodecConfig()).eval().encoder
+
+
+def test_expected_shapes_match_the_library_key_for_key(library_encoder):
+    ref = {k: tuple(v.shape) for k, v in library_encoder.state_dict().items()}
+    exp = expected_encoder_state_dict_shapes()
+    assert list(exp) == list(ref)
+    assert exp == ref
+
+
+def test_generated_state_dict_loads_strictly(library_encoder):
+    sd = random_encodec_encoder_state_dict(3)
+    res = library_encoder.load_state_dict(sd, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    assert torch.equal(random_encodec_encoder_state_dict(3)["layers.0.conv.bias"], sd["layers.0.conv.bias"])     # seeded
+
+
+def test_padding_plan_matches_the_library(library_encoder):
+    """Every convolution of the stack, in execution order: the reflected pads the library applies and the length it returns."""
+    from transformers.models.encodec.modeling_encodec import EncodecConv1d
+    names = {m: n for n, m in library_encoder.named_modules()}
+    rec = []
+    hooks = []
+    for m in library_encoder.modules():
+        if isinstance(m, EncodecConv1d):
+            hooks.append(m.register_forward_pre_hook(
+                lambda m, a: rec.append([names[m], int(m.padding_total), int(m._get_extra_padding_for_conv1d(a[0]))])))
+            hooks.append(m.register_forward_hook(lambda m, a, o: rec[-1].append(int(o.shape[-1]))))
+    try:
+        for n in LENGTHS:
+            rec.clear()
+            with torch.no_grad():
+                z = library_encoder(synthetic_wave(n, 1).view(1, 1, n))
+            plan = encoder_padding_plan(n)
+            assert [tuple(r) for r in rec] == plan, n
+            assert z.shape == (1, 128, -(-n // 320)) and plan[-1][3] == z.shape[2] == encoder_frames(n)
+    finally:
+        for h in hooks:
+            h.remove()
+    # right pads of the four strided layers: the cases the fixtures are built on
+    right = lambda n: [pr for p, _, pr, _ in encoder_padding_plan(n) if p in ("layers.3", "layers.6", "layers.9", "layers.12")]
+    assert right(2333) == [1, 1, 3, 5] and right(240000) == [0, 0, 0, 0] and right(196161) == [1, 3, 4, 7]
+    # from the shortest accepted input on, every layer's input is longer than both of its reflected pads
+    T = 1921
+    for _, pl, pr, To in encoder_padding_plan(1921):
+        assert pl < T and pr < T
+        T = To
+
+
+@pytest.mark.parametrize("k,r,C,T", [(4, 2, 32, 101), (10, 5, 128, 83)])
+def test_strided_conv_is_one_gemm_over_overlapping_rows(k, r, C, T):
+    """Rows of the time-major padded buffer taken with stride r*C, times the (co, k*ci) packing, equal F.conv1d(stride=r)."""
+    g = torch.Generator().manual_seed(k)
+    co = 2 * C
+    x = torch.randn(1, C, T, generator=g, dtype=torch.float64)
+    w = torch.randn(co, C, k, generator=g, dtype=torch.float64)
+    b = torch.randn(co, generator=g, dtype=torch.float64)
+    pl, pr, To = conv_padding(T, k, r)
+    assert T % r and pr > 0 and To == -(-T // r)
+    xp = F.pad(x, (pl, pr), mode="reflect")
+    ref = F.conv1d(xp, w, b, stride=r)[0].t()
+    a = xp[0].t().contiguous()                                     # (T + pl + pr, C) time-major
+    rows = torch.as_strided(a, (To, k * C), (r * C, 1))            # lda = r*C, K = k*C
+    assert (To - 1) * r * C + k * C == a.numel()                   # the last row ends exactly at the end of the buffer
+    got = rows @ w.permute(0, 2, 1).reshape(co, k * C).t() + b
+    torch.testing.assert_close(got, ref, atol=1e-12, rtol=1e-12)
+
+
+def test_new_symbols_are_declared_exported_and_check_arguments():
+    from v2a_amd import _lib
+    _lib.build(verbose=False)
+    h = open(os.path.join(ROOT, "include", "v2a_cfm.h")).read()
+    for name in ("v2a_elu_pad_lr", "v2a_encodec_stage0"):
+        assert re.search(r"int %s\(" % name, h) and name in _lib.EXPORTS
+    assert _lib.ABI_VERSION == 8
+    L = _lib.lib()
+    assert L.v2a_elu_pad_lr(None, 32, 8, 4, 1, 1, 1, None) == -1 and b"null" in L.v2a_last_error()
+    assert L.v2a_elu_pad_lr(16, 16, 8, 4, 1, 1, 1, None) == -1 and b"aliased" in L.v2a_last_error()
+    assert L.v2a_elu_pad_lr(16, 4096, 8, 4, 8, 0, 1, None) == -1 and b"pad_left=8" in L.v2a_last_error()       # pad == T
+    assert L.v2a_elu_pad_lr(16, 4096, 8, 4, 0, 9, 1, None) == -1 and b"pad_right=9" in L.v2a_last_error()
+    assert L.v2a_elu_pad_lr(16, 4096, 8, 6, 1, 1, 1, None) == -1 and b"C=6" in L.v2a_last_error()
+    assert L.v2a_encodec_stage0(None, 16, 32, 4000, None) == -1 and b"null" in L.v2a_last_error()
+    assert L.v2a_encodec_stage0(16, 32, 4096, 5, None) == -1 and b"n=5" in L.v2a_last_error()
+    assert L.v2a_encodec_stage0(16, 36, 4096, 4000, None) == -1 and b"alignment" in L.v2a_last_error()
+
+
+def test_encoder_device_assembly_has_no_scratch():
+    """The rule of test_isa_guard.py (whose source list is fixed) for csrc/encodec_enc.hip."""
+    from v2a_amd import _lib
+    _lib.build(verbose=False)
+    build = os.path.join(ROOT, "video-to-audio-and-piano-rp_amd", "csrc", "build")
+    paths = glob.glob(os.path.join(build, "encodec_enc-hip-amdgcn-amd-amdhsa-gfx950.s"))
+    assert paths, "no device assembly for encodec_enc.hip: csrc/build.sh must compile it with -save-temps=obj"
+    blocks = open(paths[0]).read().split("- .agpr_count:")[1:]
+    names = [re.search(r"\.name:\s+(\S+)", b).group(1) for b in blocks]
+    assert sum("elu_pad_lr" in n or "encodec_stage0" in n for n in names) == 2, names
+    for b, n in zip(blocks, names):
+        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", b).group(1)) == 0, n
+        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", b).group(1)) == 0, n
+
+
+def test_length_limit():
+    """6 frames are refused, 7 accepted -- by the helper the engine calls before any launch."""
+    with pytest.raises(ValueError, match="at least 7"):
+        encoder_frames(1920)
+    assert encoder_frames(1921) == 7 and encoder_frames(240000) == 750 and encoder_frames(239999) == 750
+    assert encoder_frames(196161) == 614 and encoder_frames(2333) == 8
+    enc = EncodecEncoder.__new__(EncodecEncoder)                   # no device: the check comes before anything else
+    with pytest.raises(ValueError, match="at least 7"):
+        enc.encode_list([torch.zeros(1920)])
+    with pytest.raises(ValueError, match="at least 7"):
+        enc.encoder(torch.zeros(2, 1, 1000))
+
+
+def test_weight_packing_of_the_engine(monkeypatch):
+    """Loads on the CPU (weights only): legacy names, the `encoder.` prefix, the stage-0 parameter block's layout."""
+    from v2a_amd import _lib
+    _lib.build(verbose=False)
+    sd = random_encodec_encoder_state_dict(5)
+    enc = EncodecEncoder(sd, "cpu")
+    legacy = {"encoder." + k.replace("parametrizations.weight.original0", "weight_g").replace("parametrizations.weight.original1", "weight_v"): v
+              for k, v in sd.items()}
+    legacy["decoder.layers.0.conv.bias"] = torch.zeros(3)          # ignored
+    enc2 = EncodecEncoder(legacy, "cpu", fused_stem=False)
+    assert torch.equal(enc2.stage0, enc.stage0) and torch.equal(enc2.cf["w"], enc.cf["w"]) and not enc2.fused_stem
+    g, v = sd["layers.3.conv.parametrizations.weight.original0"], sd["layers.3.conv.parametrizations.weight.original1"]
+    w = g * v / v.norm(dim=(1, 2), keepdim=True)
+    d = enc.stages[0]["down"]
+    assert (d["k"], d["r"], d["ci"], d["co"]) == (4, 2, 32, 64)
+    torch.testing.assert_close(d["w"], w.permute(0, 2, 1).reshape(64, 128))
+    assert enc.stage0.numel() == _lib.ENCODEC_STAGE0_PARAMS == 3376
+    assert [s["down"]["r"] for s in enc.stages] == [2, 4, 5, 8] and enc.hop == 320
+    # block layout: stem weight [32][7] first, block.3 weight [32][16] last
+    g0, v0 = sd["layers.0.conv.parametrizations.weight.original0"], sd["layers.0.conv.parametrizations.weight.original1"]
+    torch.testing.assert_close(enc.stage0[:224].view(32, 7), (g0 * v0 / v0.norm(dim=(1, 2), keepdim=True))[:, 0])
+    torch.testing.assert_close(enc.stage0[-512:].view(32, 16), enc.stages[0]["b3"]["w"])
+
+
+def _small_model(**kw):
+    import v2a_amd
+    return v2a_amd.E2TTS(transformer=dict(dim=128, dim_text=192, dim_frames=64, depth=2, heads=2, frames_heads=1, num_registers=4,
+                                          max_seq_len=256, if_text_modules=True, if_cross_attn=True, if_audio_conv=True, if_text_conv=True),
+                         num_channels=128, if_cond_proj_in=True, device="cpu", **kw)
+
+
+def test_raw_wave_cond_without_mel_spec_module_is_still_refused():
+    with pytest.raises(NotImplementedError, match="mel_spec_module"):
+        _small_model().sample(torch.zeros(2, 4000))
+
+
+def test_raw_wave_cond_goes_through_mel_spec_module():
+    """x3:2157-2160: (b, nw) -> mel_spec -> (b, d, n) -> (b, n, d), d == num_channels asserted."""
+    seen = []
+
+    def wrong_width(w):
+        seen.append(tuple(w.shape))
+        return torch.zeros(w.shape[0], 64, 13)
+    with pytest.raises(AssertionError):
+        _small_model(mel_spec_module=wrong_width).sample(torch.zeros(2, 4000))
+    assert seen == [(2, 4000)]
+    m = _small_model()
+    assert m.mel_spec is None
+    with pytest.raises(TypeError):
+        m.load_audio_encoder("facebook/encodec_24khz")
+
+
+def test_cli_audio_prompt_flag(tmp_path, monkeypatch):
+    """--audio-prompt-seconds: refused without --encodec; the wave reader takes the first S seconds of <video>.wav through
+    soundfile when torchaudio is absent, and says so when neither is installed."""
+    import sys
+    import types
+
+    import numpy as np
+
+    from v2a_amd import cli
+    assert cli.build_parser().parse_args(["ck", "0", "scp", "0", "1", "out"]).audio_prompt_seconds == 0.0
+    with pytest.raises(SystemExit):
+        cli.main(["ck", "0", "scp", "0", "1", "out", "--audio-prompt-seconds", "2"])
+    monkeypatch.setitem(sys.modules, "torchaudio", None)           # import torchaudio -> ImportError
+    monkeypatch.setitem(sys.modules, "soundfile", None)
+    with pytest.raises(RuntimeError, match="torchaudio or soundfile"):
+        cli.read_audio_prompt(str(tmp_path / "a.mp4"), 1.0)
+    data = np.arange(2 * 30000, dtype=np.float32).reshape(30000, 2) / 60000
+    rate = [24000]
+    fake = types.SimpleNamespace(read=lambda path, dtype, always_2d: (data, rate[0]))
+    monkeypatch.setitem(sys.modules, "soundfile", fake)
+    w = cli.read_audio_prompt(str(tmp_path / "a.mp4"), 1.0)
+    assert w.shape == (24000,) and w.dtype == torch.float32 and torch.equal(w, torch.from_numpy(data[:24000, 0].copy()))
+    with pytest.raises(ValueError, match="needs 36000"):
+        cli.read_audio_prompt(str(tmp_path / "a.mp4"), 1.5)
+    rate[0] = 16000
+    with pytest.raises(ValueError, match="16000 Hz"):
+        cli.read_audio_prompt(str(tmp_path / "a.mp4"), 1.0)

@@ -112,6 +112,7 @@ EXPORTS = [
     "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand", "v2a_frames_pack_split", "v2a_pool2d_split",
     "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2", "v2a_t5_rmsnorm", "v2a_t5_attention", "v2a_gemm_skinny_f32",
     "v2a_clip_resize_h", "v2a_clip_resize_v", "v2a_clip_embed_init", "v2a_clip_layernorm", "v2a_clip_attention",
+    "v2a_elu_pad_lr", "v2a_encodec_stage0",
 ]
 
 
@@ -171,6 +172,8 @@ def _declare(lib):
     lib.v2a_clip_embed_init.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp]
     lib.v2a_clip_layernorm.argtypes = [vp, i64, vp, i64, i32, i64, i32, vp, vp, f32, vp]
     lib.v2a_clip_attention.argtypes = [C.POINTER(ClipAttnArgs), vp]
+    lib.v2a_elu_pad_lr.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
+    lib.v2a_encodec_stage0.argtypes = [vp, vp, vp, i64, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -581,6 +584,19 @@ def roll_expand(roll, out, *, B, t, notes, rep, l):
 def elu_pad(x, out, *, T, C_, pad, reflect, act=True):
     _launch("elu_pad", 0.0, 4.0 * C_ * (2 * T + pad),
             lambda: lib().v2a_elu_pad(x.data_ptr(), out.data_ptr(), T, C_, pad, 1 if reflect else 0, 1 if act else 0, stream_ptr()))
+
+
+def elu_pad_lr(x, out, *, T, C_, pad_left, pad_right, act=True):
+    _launch("elu_pad_lr", 0.0, 4.0 * C_ * (2 * T + pad_left + pad_right),
+            lambda: lib().v2a_elu_pad_lr(x.data_ptr(), out.data_ptr(), T, C_, pad_left, pad_right, 1 if act else 0, stream_ptr()))
+
+
+ENCODEC_STAGE0_PARAMS = 3376     # floats of the parameter block of v2a_encodec_stage0 (include/v2a_cfm.h)
+
+
+def encodec_stage0(wave, params, out, *, n):
+    _launch("encodec_stage0", 2.0 * n * 3744, 4.0 * n * 33,
+            lambda: lib().v2a_encodec_stage0(wave.data_ptr(), params.data_ptr(), out.data_ptr(), n, stream_ptr()))
 
 
 def lstm_layer(gates_x, w_hh, h, workspace, *, T, H, resid=None, y=None):

@@ -18,6 +18,9 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
   --encodec STATE    torch-saved state dict of `EncodecModel.from_pretrained("facebook/encodec_24khz")` (or of its decoder):
                      each clip's valid frames are decoded by the HIP vocoder and written as `<name>.wav` (24 kHz float32),
                      what the reference does with `save_to_filename` / torchaudio.save (x3:2291-2303, predict.py:279-281).
+  --audio-prompt-seconds S   (with --encodec, checkpoint built with if_cond_proj_in) the first S seconds of `<video>.wav` (24 kHz) are
+                     encoded by the HIP Encodec encoder and given to the sampler as the audio prompt: `cond` = the raw waves,
+                     `lens` = ceil(24000 S / 320) frames, which come back unchanged in front of the generated ones (x3:2196-2231).
 The moviepy mux of audio and video stays outside (out of scope).
 """
 from __future__ import annotations
@@ -47,6 +50,28 @@ def read_frames_with_moviepy(video_path: str):
     from moviepy.editor import VideoFileClip
     clip = VideoFileClip(video_path)
     return np.array(list(clip.iter_frames())), clip.duration
+
+
+def read_audio_prompt(video_path: str, seconds: float) -> torch.Tensor:
+    """The first `seconds` of `<video>.wav` as (nw,) float32 (first channel): 24 kHz, read with torchaudio or soundfile."""
+    path = video_path.rsplit(".", 1)[0] + ".wav"
+    nw = int(round(24000 * seconds))
+    try:
+        import torchaudio
+        wav, rate = torchaudio.load(path)
+        wav = wav[0]
+    except ImportError:
+        try:
+            import soundfile
+        except ImportError as e:
+            raise RuntimeError("--audio-prompt-seconds reads <video>.wav with torchaudio or soundfile; neither is installed") from e
+        data, rate = soundfile.read(path, dtype="float32", always_2d=True)
+        wav = torch.from_numpy(data[:, 0].copy())
+    if rate != 24000:
+        raise ValueError(f"{path}: {rate} Hz, the Encodec encoder takes 24 000 Hz")
+    if wav.shape[0] < nw:
+        raise ValueError(f"{path}: {wav.shape[0]} samples, --audio-prompt-seconds {seconds} needs {nw}")
+    return wav[:nw].float().contiguous()
 
 
 def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None):
@@ -105,11 +130,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="compute mode of the Video2Roll encoder behind --piano (default: bf16 under --dtype bf16, else fp32); bf16x3: "
                          "split-bf16 implicit GEMM inside 1e-4 of the reference probabilities")
     ap.add_argument("--encodec", default=None, help="state dict (.pt) of the Encodec model / decoder: also write <name>.wav")
+    ap.add_argument("--audio-prompt-seconds", type=float, default=0.0, help="with --encodec and a checkpoint built with if_cond_proj_in: "
+                    "prompt every clip with the first S seconds of <video>.wav, encoded by the HIP Encodec encoder")
     return ap
 
 
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.audio_prompt_seconds < 0 or (a.audio_prompt_seconds > 0 and not a.encodec):
+        ap.error("--audio-prompt-seconds needs a positive S and --encodec (the state dict that holds the encoder)")
 
     import torch.distributed as dist
     from . import E2TTS, collate_clips, gather_latents, shard_range
@@ -123,7 +153,7 @@ def main(argv=None):
         tk = json.loads(a.model_config)
     channels = tk.pop("num_channels", 128)
     model = E2TTS(transformer=dict(if_text_modules=True, if_cross_attn=True, if_audio_conv=True, if_text_conv=True, **tk),
-                  num_channels=channels, sampling_rate=24000, if_cond_proj_in=False, tokenizer="phoneme_zh",
+                  num_channels=channels, sampling_rate=24000, if_cond_proj_in=a.audio_prompt_seconds > 0, tokenizer="phoneme_zh",
                   compute_dtype=a.dtype, device=torch.device("cuda", local), bucket_frames=a.bucket_frames, bucket_ctx=a.bucket_ctx,
                   frames_compute_dtype=a.frames_dtype)
     ck = torch.load(a.ckpt, map_location="cpu")
@@ -153,6 +183,8 @@ def main(argv=None):
             except ImportError as e:
                 raise FileNotFoundError(f"{vp}: no cached CLIP features and moviepy is not installed to decode it for --clip") from e
             return cenc(frames).cpu(), duration
+    if a.audio_prompt_seconds > 0:                                   # a checkpoint without cond_proj_in.* was refused above
+        model.load_audio_encoder(torch.load(a.encodec, map_location="cpu"))
     vocoder = None
     if a.encodec and rank == 0:
         from .encodec import EncodecDecoder
@@ -171,7 +203,11 @@ def main(argv=None):
             if a.piano:
                 from .features import load_piano_frames
                 frames = load_piano_frames([vp for vp, _ in mine], int(batch8[3].max()))       # x3:1829, predict.py:231
-            lat = model.sample(batch8[1], lens=batch8[3], duration=batch8[3], steps=a.steps, cfg_strength=a.cfg_strength,
+            cond, lens = batch8[1], batch8[3]
+            if a.audio_prompt_seconds > 0:                           # raw waves (b, nw): sample() encodes them (x3:2157-2160)
+                cond = torch.stack([read_audio_prompt(vp, a.audio_prompt_seconds) for vp, _ in mine])
+                lens = torch.full((len(mine),), -(-cond.shape[1] // 320), dtype=torch.int32)
+            lat = model.sample(cond, lens=lens, duration=batch8[3], steps=a.steps, cfg_strength=a.cfg_strength,
                                remove_parallel_component=False, sway_sampling=True, video_drop_prompt=batch8[4],
                                return_raw_output=True, frames=frames, **extras).to(torch.device("cuda", local))
         else:

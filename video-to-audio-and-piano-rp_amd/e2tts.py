@@ -213,6 +213,7 @@ class E2TTS:
         self._v2r_sd, self._v2r = None, None      # optional Video2Roll frame encoder (video2roll_net.*, x3:1523)
         self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
         self._clip = None                         # optional CLIP image encoder (load_image_encoder, x3:1423-1425)
+        self._audio_encoder = None                # optional Encodec encoder behind a raw-wave cond (load_audio_encoder, x3:1350)
         L.lib()  # no library -> no sampler
 
     # ---- nn.Module-like surface used by the callers (predict.py:156-170) -------------------
@@ -317,6 +318,21 @@ class E2TTS:
         else:
             raise TypeError(f"load_text_encoder: a T5Encoder, a directory or a state dict, got {type(src).__name__}")
         self._t5 = enc
+        return enc
+
+    def load_audio_encoder(self, src, **kw):
+        """The Encodec encoder behind a raw-wave `cond` (b, nw) (x3:1350, 2157-2160; `EncodecWrapper.forward`, x3:428-432): an
+        `EncodecEncoder` or an EncodecModel / encoder state dict.  Sets `mel_spec` to an adapter (b, nw) -> (b, 128, ceil(nw / 320));
+        every row of the batch has the same nw, so the latent length is one number.  `kw` go to the EncodecEncoder constructor."""
+        from .encodec import EncodecEncoder
+        if isinstance(src, EncodecEncoder):
+            enc = src
+        elif isinstance(src, dict):
+            enc = EncodecEncoder(src, self._device, **kw)
+        else:
+            raise TypeError(f"load_audio_encoder: an EncodecEncoder or a state dict, got {type(src).__name__}")
+        self._audio_encoder = enc
+        self.mel_spec = lambda wave: enc.encoder(wave.unsqueeze(1))
         return enc
 
     def load_image_encoder(self, src, **kw):
@@ -458,8 +474,12 @@ class E2TTS:
         their caches written (x3:1706-1793; an existing cache wins); without `video_paths` the embeddings are resampled to the
         latent rate and nothing is written."""
         self.eval()
-        if cond.ndim == 2:
-            raise NotImplementedError("raw-wave `cond` needs mel_spec_module, which the shipped config does not set")
+        if cond.ndim == 2:                                                          # raw wave (x3:2157-2160)
+            if self.mel_spec is None:
+                raise NotImplementedError("raw-wave `cond` needs mel_spec_module, which the shipped config does not set "
+                                          "(load_audio_encoder sets the Encodec encoder)")
+            cond = self.mel_spec(cond).permute(0, 2, 1)                              # b d n -> b n d
+            assert cond.shape[-1] == self.num_channels, (tuple(cond.shape), self.num_channels)
         batch, cond_seq_len = cond.shape[:2]
         out_device = cond.device
         cfgm = self.cfg

@@ -1,4 +1,4 @@
-"""Encodec 24 kHz decoder (the vocoder) on the MI355X kernels.
+"""Encodec 24 kHz decoder (the vocoder) and encoder on the MI355X kernels.
 
 Mirrors `EncodecWrapper.decode` (src/e2_tts_pytorch/e2_tts_crossatt3.py:434-437): `self.model.decoder(emb)` then
 `output[0]`, called on the sampler's latents at predict.py:277-278.  The network is the SEANet decoder of
@@ -13,10 +13,20 @@ up-sampled [L*r][Cout] signal in place -- no col2im, no scatter.  `v2a_elu_pad` 
 pass; `v2a_lstm2` runs both LSTM layers' recurrences in one persistent kernel (weights in registers, T + 1 exchange steps).  Weight norm is
 resolved at load time.  Everything is fp32 (exact-fp32 MFMA): the whole decoder is ~30 GFLOP, memory- and latency-bound.
 There is no CPU fallback: without libv2a_cfm.so every call raises.
+
+`EncodecEncoder` is the mirror (`EncodecWrapper.forward`, x3:428-432, predict.py:222): Conv1d(1->32, k7), four [residual block, ELU,
+Conv1d(k = 2r, stride r)] stages for r = 2, 4, 5, 8, the LSTM, ELU, Conv1d(512->128, k7).  A strided convolution is ONE `v2a_gemm`
+whose A rows overlap with lda = r*C (K = k*C, M = ceil(T/r)) over a buffer that `v2a_elu_pad_lr` padded on both sides: the library
+reflects k - r samples in front and, where the length is not a multiple of r, up to r - 1 behind (`encoder_padding_plan`).  The
+wide, thin end -- stem + the C = 32 block over 240 000 time steps -- is one fused VALU kernel (`v2a_encodec_stage0`);
+`fused_stem=False` keeps the generic composition of it reachable for A/B runs.
 """
 from __future__ import annotations
 
+import math
+
 import torch
+import torch.nn.functional as F
 
 from . import _lib as L
 
@@ -62,7 +72,7 @@ def _resolve_weight(sd, p):
         if gk in sd and vk in sd:
             g, v = sd[gk].float(), sd[vk].float()
             return g * v / v.norm(dim=(1, 2), keepdim=True)
-    raise KeyError(f"EncodecDecoder: no weight for {p}.conv (looked for .weight, parametrizations.weight.original0/1, weight_g/v)")
+    raise KeyError(f"Encodec: no weight for {p}.conv (looked for .weight, parametrizations.weight.original0/1, weight_g/v)")
 
 
 class EncodecDecoder:
@@ -180,3 +190,212 @@ class EncodecDecoder:
     def decode(self, emb):
         """`EncodecWrapper.decode(emb)` (x3:434-437): the first clip's waveform, shape (1, samples)."""
         return self.decoder(emb)[0]
+
+
+# ---- encoder -----------------------------------------------------------------------------------------------------------
+MIN_FRAMES = 7          # the final k7 convolution reflects 6 frames; below that the library zero-extends first (not mirrored here)
+
+
+def expected_encoder_state_dict_shapes() -> dict[str, tuple]:
+    """Key layout of `EncodecModel(EncodecConfig()).encoder.state_dict()` (weight_norm parametrisation)."""
+    s: dict[str, tuple] = {}
+
+    def conv(p, co, ci, k):
+        s[f"{p}.conv.bias"] = (co,)
+        s[f"{p}.conv.parametrizations.weight.original0"] = (co, 1, 1)
+        s[f"{p}.conv.parametrizations.weight.original1"] = (co, ci, k)
+
+    c = FILTERS
+    conv("layers.0", c, 1, 7)
+    idx = 1
+    for r in reversed(RATIOS):
+        conv(f"layers.{idx}.block.1", c // 2, c, 3)
+        conv(f"layers.{idx}.block.3", c, c // 2, 1)
+        conv(f"layers.{idx}.shortcut", c, c, 1)
+        conv(f"layers.{idx + 2}", 2 * c, c, 2 * r)
+        c *= 2
+        idx += 3
+    for l in range(2):
+        s[f"layers.{idx}.lstm.weight_ih_l{l}"] = (4 * c, c)
+        s[f"layers.{idx}.lstm.weight_hh_l{l}"] = (4 * c, c)
+        s[f"layers.{idx}.lstm.bias_ih_l{l}"] = (4 * c,)
+        s[f"layers.{idx}.lstm.bias_hh_l{l}"] = (4 * c,)
+    conv(f"layers.{idx + 2}", HIDDEN, c, 7)
+    return s
+
+
+def conv_padding(length: int, k: int, stride: int = 1) -> tuple[int, int, int]:
+    """(pad_left, pad_right, out_len) of a causal `EncodecConv1d(k, stride)` on `length` samples: k - stride reflected samples in
+    front, and behind as many as make the last window full (`_get_extra_padding_for_conv1d`, in integers)."""
+    pad_left = k - stride
+    n_frames = -((length - k + pad_left) // -stride)              # ceil((length - k + pad_total) / stride + 1) - 1
+    pad_right = n_frames * stride + k - pad_left - length
+    return pad_left, pad_right, (length + pad_left + pad_right - k) // stride + 1
+
+
+def encoder_padding_plan(n: int) -> list[tuple[str, int, int, int]]:
+    """(conv prefix, pad_left, pad_right, out_len) of every convolution of the encoder, in execution order, for n samples: `conv_padding`,
+    which the engine sizes every buffer and launch with, walked over the stack."""
+    plan = []
+    T = n
+
+    def add(p, k, stride=1):
+        nonlocal T
+        pl, pr, T = conv_padding(T, k, stride)
+        plan.append((p, pl, pr, T))
+
+    add("layers.0", 7)
+    idx = 1
+    for r in reversed(RATIOS):
+        add(f"layers.{idx}.block.1", 3)
+        add(f"layers.{idx}.block.3", 1)
+        add(f"layers.{idx}.shortcut", 1)
+        add(f"layers.{idx + 2}", 2 * r, r)
+        idx += 3
+    add(f"layers.{idx + 2}", 7)
+    return plan
+
+
+def encoder_frames(n: int) -> int:
+    """Latent frames of n samples, ceil(n / 320); ValueError below MIN_FRAMES (n < 1 921), the decoder's limit too."""
+    hop = math.prod(RATIOS)
+    T = -(-int(n) // hop)
+    if T < MIN_FRAMES:
+        raise ValueError(f"EncodecEncoder: {n} samples give {T} latent frames, need at least {MIN_FRAMES} "
+                         f"({(MIN_FRAMES - 1) * hop + 1} samples: reflect padding of the k=7 convolutions)")
+    return T
+
+
+class EncodecEncoder:
+    """HIP mirror of `EncodecWrapper.forward` / `EncodecModel.encoder` (no quantizer).
+
+    state_dict: an `EncodecModel` state dict (keys `encoder.layers...`) or the encoder's own (`layers...`).
+    fused_stem: layers 0 and 1 in the one-pass `v2a_encodec_stage0` kernel; False composes them from `v2a_gemm` / `v2a_elu_pad_lr`
+    like the later stages (the stem as a GEMM over a zero-padded K = 16 patch buffer) -- kept for A/B timing and value comparison."""
+
+    def __init__(self, state_dict, device="cuda:0", fused_stem=True):
+        L.lib()                                                   # fail loudly without the HIP library
+        self.dev = dev = torch.device(device)
+        self.fused_stem = bool(fused_stem)
+        sd = {k: v.detach().cpu() for k, v in state_dict.items()}
+        if any(k.startswith("encoder.layers.") for k in sd):
+            sd = {k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}
+        f32 = lambda t: t.float().contiguous().to(dev)
+
+        def conv(p, stride=1):
+            w = _resolve_weight(sd, p)                            # (co, ci, k)
+            co, ci, k = w.shape
+            # w3 / b_cpu: the resolved (co, ci, k) weight and the bias on the host -- the stage-0 parameter block is packed from them
+            return dict(w=f32(w.permute(0, 2, 1).reshape(co, k * ci)), b=f32(sd[f"{p}.conv.bias"]), co=co, ci=ci, k=k, r=stride, w3=w,
+                        b_cpu=sd[f"{p}.conv.bias"].float())
+
+        self.stem = conv("layers.0")
+        assert (self.stem["ci"], self.stem["k"]) == (1, 7)
+        self.stem["w"] = f32(F.pad(self.stem["w3"][:, 0], (0, 16 - 7)))           # (32, 16): K padded to the GEMM's granule
+        self.stages = []
+        idx = 1
+        for r in reversed(RATIOS):
+            self.stages.append(dict(b1=conv(f"layers.{idx}.block.1"), b3=conv(f"layers.{idx}.block.3"), sc=conv(f"layers.{idx}.shortcut"),
+                                    down=conv(f"layers.{idx + 2}", r)))
+            assert self.stages[-1]["down"]["k"] == 2 * r
+            idx += 3
+        self.lstm = []
+        for l in range(2):
+            self.lstm.append(dict(wih=f32(sd[f"layers.{idx}.lstm.weight_ih_l{l}"]), whh=f32(sd[f"layers.{idx}.lstm.weight_hh_l{l}"]),
+                                  b=f32(sd[f"layers.{idx}.lstm.bias_ih_l{l}"].float() + sd[f"layers.{idx}.lstm.bias_hh_l{l}"].float())))
+        self.cf = conv(f"layers.{idx + 2}")
+        self.H = self.cf["ci"]
+        self.hop = math.prod(RATIOS)
+        s0 = self.stages[0]
+        # parameter block of v2a_encodec_stage0 (include/v2a_cfm.h)
+        self.stage0 = f32(torch.cat([self.stem["w3"].reshape(-1), self.stem["b_cpu"], s0["sc"]["w3"].reshape(-1),
+                                     s0["sc"]["b_cpu"] + s0["b3"]["b_cpu"], s0["b1"]["w3"].permute(0, 2, 1).reshape(-1), s0["b1"]["b_cpu"],
+                                     s0["b3"]["w3"].reshape(-1)]))
+        assert self.stage0.numel() == L.ENCODEC_STAGE0_PARAMS
+        self._bufs: dict = {}
+        self._ws = torch.zeros(8 * self.H + 2, dtype=torch.int32, device=dev)      # exchange tables of both LSTM layers + error flag
+
+    _buf = EncodecDecoder._buf
+
+    def _conv(self, cv, src, T, name, *, act, resid=None):
+        """Causal Conv1d(k, stride r) on time-major src (T, ci): ELU (optional) + reflect pads, then one GEMM over overlapping rows."""
+        k, ci, co, r = cv["k"], cv["ci"], cv["co"], cv["r"]
+        pl, pr, To = conv_padding(T, k, r)
+        a = src
+        if act or pl or pr:
+            a = self._buf(name + ".in", T + pl + pr, ci)
+            L.elu_pad_lr(src, a, T=T, C_=ci, pad_left=pl, pad_right=pr, act=act)
+        out = self._buf(name, To, co)
+        L.gemm([(a, r * ci, k * ci)], cv["w"], out, M=To, N=co, compute=L.F32, bias=cv["b"], ldo=co,
+               epilogue=L.EPI_RESID if resid is not None else L.EPI_STORE, resid=resid, ldr=co)
+        return out, To
+
+    def _resblock(self, st, x, T, name):
+        h1, _ = self._conv(st["b1"], x, T, name + ".b1", act=True)
+        h2, _ = self._conv(st["b3"], h1, T, name + ".b3", act=True)
+        return self._conv(st["sc"], x, T, name + ".out", act=False, resid=h2)[0]
+
+    def _stage0(self, wave, n):
+        """Layers 0 and 1: wave (n,) -> (n, 32) time-major."""
+        out = self._buf("s0.out", n, FILTERS)
+        if self.fused_stem:
+            L.encodec_stage0(wave, self.stage0, out, n=n)
+            return out
+        # composed form: the stem's 7-tap patches in a zero-padded (n, 16) buffer, then the generic path
+        patches = self._buf("stem.in", n, 16)
+        patches.zero_()
+        patches[:, :7].copy_(F.pad(wave.view(1, 1, n), (6, 0), mode="reflect").view(-1).unfold(0, 7, 1))
+        x0 = self._buf("stem", n, FILTERS)
+        L.gemm([(patches, 16, 16)], self.stem["w"], x0, M=n, N=FILTERS, compute=L.F32, bias=self.stem["b"], ldo=FILTERS)
+        return self._resblock(self.stages[0], x0, n, "s0")
+
+    def _encode_one(self, wave, taps=None):
+        """wave (n,) fp32 on the device -> latent (128, ceil(n / 320))."""
+        n = wave.shape[0]
+        x = self._stage0(wave, n)
+        T = n
+        if taps is not None:
+            taps["layer1"] = x.t().clone()
+        for si, st in enumerate(self.stages):
+            if si:
+                x = self._resblock(st, x, T, f"s{si}")
+            x, T = self._conv(st["down"], x, T, f"s{si}.down", act=True)
+            if taps is not None:
+                taps[f"layer{3 * si + 3}"] = x.t().clone()
+        H = self.H
+        l0, l1 = self.lstm
+        gx = self._buf("gx0", T, 4 * H)
+        L.gemm([(x, H, H)], l0["wih"], gx, M=T, N=4 * H, compute=L.F32, bias=l0["b"], ldo=4 * H)
+        y = self._buf("lstm_out", T, H)
+        L.lstm2(gx, l0["whh"], l1["wih"], l1["b"], l1["whh"], y, self._ws, T=T, H=H, resid=x)
+        if taps is not None:
+            taps["layer13"] = y.t().clone()
+        z, _ = self._conv(self.cf, y, T, "final", act=True)                        # (T, 128)
+        return z.t().contiguous()
+
+    @torch.no_grad()
+    def encode_list(self, waves, taps=None):
+        """Ragged lengths: a list of 1-D waves -> a list of (128, ceil(n_i / 320)) latents on the device, one clip at a time."""
+        lens = [encoder_frames(w.shape[-1]) for w in waves]                         # refuse before any launch
+        out = []
+        for i, (w, T) in enumerate(zip(waves, lens)):
+            assert w.ndim == 1, f"encode_list takes 1-D waves, got {tuple(w.shape)}"
+            z = self._encode_one(w.to(self.dev, torch.float32).contiguous(), taps if i == 0 else None)
+            assert z.shape == (HIDDEN, T), (tuple(z.shape), T)
+            out.append(z)
+            if int(self._ws[8 * self.H].item()):                                   # one host sync per clip
+                raise L.V2AError("v2a_lstm2: a workgroup timed out at the step barrier (GPU oversubscribed?); result discarded")
+        return out
+
+    def encoder(self, wave, taps=None):
+        """`EncodecModel.encoder(wave)`: wave (b, 1, n) -> (b, 128, ceil(n / 320)) fp32 on the device."""
+        assert wave.ndim == 3 and wave.shape[1] == 1, f"wave must be (b, 1, n), got {tuple(wave.shape)}"
+        return torch.stack(self.encode_list([wave[i, 0] for i in range(wave.shape[0])], taps))
+
+    def forward(self, waveform):
+        """`EncodecWrapper.forward(waveform)` (x3:428-432): waveform (channels, n); the processor is handed `waveform[0]` and, for
+        this model, neither normalises nor chunks it -> (1, 128, T)."""
+        assert waveform.ndim == 2, f"waveform must be (channels, n), got {tuple(waveform.shape)}"
+        return self.encoder(waveform[:1].unsqueeze(0))
+
+    __call__ = forward

@@ -141,6 +141,45 @@ def random_encodec_decoder_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
     return sd
 
 
+def random_encodec_encoder_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `EncodecModel(EncodecConfig()).encoder.state_dict()`, by the scale rules of
+    `random_encodec_decoder_state_dict`: the library's latents of a peak-1 wave come out O(1)."""
+    import numpy as np
+
+    from .encodec import expected_encoder_state_dict_shapes
+
+    rs = np.random.RandomState(seed)
+    sd = {}
+    for k, shp in expected_encoder_state_dict_shapes().items():
+        if k.endswith("original0"):
+            v = rs.uniform(0.8, 1.6, shp)
+        elif k.endswith("original1"):
+            v = rs.standard_normal(shp) / math.sqrt(shp[1] * shp[2])
+        elif "lstm.weight" in k:
+            v = rs.uniform(-1.0, 1.0, shp) / math.sqrt(shp[1])
+        elif "lstm.bias" in k:
+            v = rs.uniform(-0.1, 0.1, shp)
+        else:
+            v = 0.05 * rs.standard_normal(shp)
+        sd[k] = torch.from_numpy(v.astype(np.float32))
+    return sd
+
+
+def synthetic_wave(n: int, seed: int = 0, rate: int = 24000) -> torch.Tensor:
+    """A seeded (n,) fp32 test signal: 12 sines at 60 - 6000 Hz with random amplitude and phase plus 0.05 white noise, scaled to
+    peak <= 1 (numpy RandomState: the same samples on any machine)."""
+    import numpy as np
+
+    rs = np.random.RandomState(seed)
+    t = np.arange(n, dtype=np.float64) / rate
+    f = np.exp(rs.uniform(math.log(60.0), math.log(6000.0), 12))
+    a = rs.uniform(0.2, 1.0, 12)
+    ph = rs.uniform(0.0, 2 * math.pi, 12)
+    x = (a[:, None] * np.sin(2 * math.pi * f[:, None] * t[None] + ph[:, None])).sum(0) / a.sum()
+    x = 0.8 * x + 0.05 * rs.standard_normal(n)
+    return torch.from_numpy((x / max(1.0, np.abs(x).max())).astype(np.float32))
+
+
 FLAN_T5_LARGE = dict(vocab_size=32128, d_model=1024, d_kv=64, num_heads=16, d_ff=2816, num_layers=24, relative_attention_num_buckets=32,
                      relative_attention_max_distance=128, layer_norm_epsilon=1e-6)
 
