@@ -556,6 +556,30 @@ typedef struct v2a_clip_attn_args {
 } v2a_clip_attn_args;
 int v2a_clip_attention(const v2a_clip_attn_args* args, v2a_stream_t stream);
 
+/* =======================================================================================
+ * N3: piano-frame preprocessing, the uncached `piano` branch of `E2TTS.encode_video_frames` (x3:1876-1891 with the
+ * module-level `transform`, x3:60-63): per decoded frame Image.convert('L'), Image.resize((900, 100)) (BICUBIC), / 255.
+ * Two integer passes, equal to Pillow bit for bit; tables from the host as for v2a_clip_resize_h / _v.
+ * ===================================================================================== */
+
+/* Grey + horizontal pass.  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (Pillow rgb2l) of every tap is formed in registers, then
+ *   tmp[j][y - y0][x] = clip8((2^21 + sum_{i < bounds[2x+1]} L(frames[f_j][y][bounds[2x] + i]) * coef[x * ksize + i]) >> 22)
+ * for j < n, y0 <= y < y0 + rows, x < Wo, with f_j = sel[j] (device int32, any order, repeats allowed; the CALLER guarantees
+ * 0 <= sel[j] < F) or j when sel is NULL (then n <= F).  frames (F, H, W, 3) uint8 RGB, 4-byte aligned; tmp (n, rows, ldt) uint8,
+ * ldt >= Wo a multiple of 4 (columns >= Wo of a row hold nothing).  n <= 65535 per call; 4 * ceil(W / 4) * 4 bytes of LDS.  The
+ * CALLER guarantees bounds[2x] + bounds[2x+1] <= W and bounds[2x+1] <= ksize.
+ * Replaces: Image.convert('L') and the horizontal pass of Image.resize at x3:1883-1886. */
+int v2a_piano_resize_h(const uint8_t* frames, int32_t F, int32_t H, int32_t W, const int32_t* sel, int32_t n, uint8_t* tmp, int32_t ldt,
+                       int32_t y0, int32_t rows, int32_t Wo, const int32_t* bounds, const int32_t* coef, int32_t ksize,
+                       v2a_stream_t stream);
+/* Vertical pass over tmp (bounds relative to its row 0; the CALLER guarantees bounds[2y] + bounds[2y+1] <= rows and
+ * bounds[2y+1] <= ksize), clipped to a byte u, stored as lut[u] (256 floats, float32(float64(u) / 255.0) built on the host):
+ *   out[j][y][x] = lut[clip8((2^21 + sum_i tmp[j][bounds[2y] + i][x] * coef[y * ksize + i]) >> 22)],  out (n, Ho, Wo) fp32 contiguous,
+ * 16-byte aligned when Wo % 4 == 0.  Replaces: the vertical pass of Image.resize, the reshape and `x / 255.` of `transform` (x3:60-63)
+ * and the float32 cast of x3:1890. */
+int v2a_piano_resize_v(const uint8_t* tmp, int32_t n, int32_t rows, int32_t ldt, int32_t Ho, int32_t Wo, const int32_t* bounds,
+                       const int32_t* coef, int32_t ksize, const float* lut, float* out, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,13 +9,14 @@ from .collate import collate_clips, ClipRequest  # noqa: F401
 from .dist import shard_range, gather_latents  # noqa: F401
 from .features import (feature_cache_path, save_clip_cache, load_clip_cache, resample_indices,  # noqa: F401
                        resample_clip_features, encode_video_cached, piano_frames_cache_path, save_piano_frames_cache,
-                       piano_frame_indices, load_piano_frames)
+                       piano_frame_indices, load_piano_frames, piano_frames_from_video)
 from .video2roll import Video2RollEngine  # noqa: F401
 from .encodec import EncodecDecoder, EncodecEncoder  # noqa: F401
 from .t5 import T5Encoder  # noqa: F401
 from .clip import CLIPImageEncoder  # noqa: F401
+from .piano_frames import PianoFramePlan, PianoFramePreprocessor  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
            "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "expected_state_dict_shapes", "NOTES",
-           "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "T5Encoder", "CLIPImageEncoder"]
+           "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "T5Encoder", "CLIPImageEncoder", "PianoFramePlan", "PianoFramePreprocessor"]

@@ -112,7 +112,7 @@ EXPORTS = [
     "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand", "v2a_frames_pack_split", "v2a_pool2d_split",
     "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2", "v2a_t5_rmsnorm", "v2a_t5_attention", "v2a_gemm_skinny_f32",
     "v2a_clip_resize_h", "v2a_clip_resize_v", "v2a_clip_embed_init", "v2a_clip_layernorm", "v2a_clip_attention",
-    "v2a_elu_pad_lr", "v2a_encodec_stage0",
+    "v2a_elu_pad_lr", "v2a_encodec_stage0", "v2a_piano_resize_h", "v2a_piano_resize_v",
 ]
 
 
@@ -174,6 +174,8 @@ def _declare(lib):
     lib.v2a_clip_attention.argtypes = [C.POINTER(ClipAttnArgs), vp]
     lib.v2a_elu_pad_lr.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
     lib.v2a_encodec_stage0.argtypes = [vp, vp, vp, i64, vp]
+    lib.v2a_piano_resize_h.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp]
+    lib.v2a_piano_resize_v.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int

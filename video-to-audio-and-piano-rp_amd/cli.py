@@ -13,7 +13,8 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
 
   --clip DIR         encode the videos that have no CLIP feature cache (moviepy decode, HIP CLIP encoder of this rank's GPU)
   --t5-engine hip    run --t5 on the HIP FLAN-T5 encoder (t5.py) of this rank's GPU instead of transformers on the CPU
-  --piano            V2P (src/inference_v2p.py): the cached grey frames `<video>.generated_frames_raw.2.npz` (features.py) go
+  --piano            V2P (src/inference_v2p.py): the grey frames `<video>.generated_frames_raw.2.npz` (features.py; made on the GPU
+                     by piano_frames.py from a moviepy decode when the cache is missing) go
                      through the HIP Video2Roll encoder; the checkpoint must hold `video2roll_net.*`
   --encodec STATE    torch-saved state dict of `EncodecModel.from_pretrained("facebook/encodec_24khz")` (or of its decoder):
                      each clip's valid frames are decoded by the HIP vocoder and written as `<name>.wav` (24 kHz float32),
@@ -100,6 +101,23 @@ def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip
     return reqs
 
 
+def piano_frames_for(video_paths, l: int, preprocess, decode):
+    """--piano: the (b, 1, t, 100, 900) stack of a batch.  Clips with a frame cache are read from it; the others are decoded by
+    `decode(video_path) -> (frames, duration)` and go through `preprocess` (a PianoFramePreprocessor), which also writes their cache.
+    Without moviepy (`decode` raises ImportError) a missing cache is load_piano_frames' FileNotFoundError, as without this path."""
+    from .features import load_piano_frames, piano_frames_cache_path
+
+    def frames_of(vp):
+        if os.path.exists(piano_frames_cache_path(vp)):
+            return None
+        try:
+            return decode(vp)
+        except ImportError:
+            return None
+
+    return load_piano_frames(video_paths, l, video_frames=[frames_of(vp) for vp in video_paths], preprocess=preprocess)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("ckpt")
@@ -125,7 +143,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "without <video>.generated.npz are decoded with moviepy and encoded on this rank's GPU, and the cache is written")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
-    ap.add_argument("--piano", action="store_true", help="V2P: condition on the cached piano frames through the Video2Roll encoder")
+    ap.add_argument("--piano", action="store_true", help="V2P: condition on the piano frames through the Video2Roll encoder; a video without "
+                    "<video>.generated_frames_raw.2.npz is decoded with moviepy and resized on this rank's GPU, and the cache is written")
     ap.add_argument("--frames-dtype", default=None, choices=["fp32", "bf16", "bf16x3"],
                     help="compute mode of the Video2Roll encoder behind --piano (default: bf16 under --dtype bf16, else fp32); bf16x3: "
                          "split-bf16 implicit GEMM inside 1e-4 of the reference probabilities")
@@ -173,13 +192,20 @@ def main(argv=None):
             b = tok([prompt], max_length=tok.model_max_length, padding=True, truncation=True, return_tensors="pt")
             with torch.no_grad():
                 return enc(input_ids=b.input_ids, attention_mask=b.attention_mask)[0][0]
+    decoded: dict = {}                 # video path -> (frames, duration): --clip and --piano share one moviepy decode per batch
+
+    def decode(vp):
+        if vp not in decoded:
+            decoded[vp] = read_frames_with_moviepy(vp)
+        return decoded[vp]
+
     clip_encode = None
     if a.clip:
         from .clip import CLIPImageEncoder
         cenc = CLIPImageEncoder.from_pretrained(a.clip, torch.device("cuda", local))
         def clip_encode(vp):
             try:
-                frames, duration = read_frames_with_moviepy(vp)
+                frames, duration = decode(vp)
             except ImportError as e:
                 raise FileNotFoundError(f"{vp}: no cached CLIP features and moviepy is not installed to decode it for --clip") from e
             return cenc(frames).cpu(), duration
@@ -201,8 +227,9 @@ def main(argv=None):
             batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode), channels, gen)
             frames = None
             if a.piano:
-                from .features import load_piano_frames
-                frames = load_piano_frames([vp for vp, _ in mine], int(batch8[3].max()))       # x3:1829, predict.py:231
+                # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
+                frames = piano_frames_for([vp for vp, _ in mine], int(batch8[3].max()), model.piano_frame_preprocessor(), decode)
+            decoded.clear()
             cond, lens = batch8[1], batch8[3]
             if a.audio_prompt_seconds > 0:                           # raw waves (b, nw): sample() encodes them (x3:2157-2160)
                 cond = torch.stack([read_audio_prompt(vp, a.audio_prompt_seconds) for vp, _ in mine])

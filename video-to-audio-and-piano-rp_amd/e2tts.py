@@ -214,6 +214,7 @@ class E2TTS:
         self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
         self._clip = None                         # optional CLIP image encoder (load_image_encoder, x3:1423-1425)
         self._audio_encoder = None                # optional Encodec encoder behind a raw-wave cond (load_audio_encoder, x3:1350)
+        self._piano_pre = None                    # piano-frame preprocessor of this device (piano_frame_preprocessor, x3:1877-1891)
         L.lib()  # no library -> no sampler
 
     # ---- nn.Module-like surface used by the callers (predict.py:156-170) -------------------
@@ -225,6 +226,7 @@ class E2TTS:
         self._device = torch.device(device)
         self._engine = None
         self._v2r = None
+        self._piano_pre = None
         if self._clip is not None:
             self._clip.to(self._device)        # weights follow, buffers and tables are rebuilt on first use
         return self
@@ -299,6 +301,37 @@ class E2TTS:
             from .video2roll import Video2RollEngine
             self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute)
         return self._v2r.encode_frames(x, l)
+
+    def encode_video_frames(self, video_paths, l: int, piano, *, video_frames=None):
+        """x3:1829-1991, the `piano` branch: the grey frame stacks of a batch of clips and the (unused) MIDI ground truth,
+        `(frames (b, 1, t, 100, 900), midis (b, l, NOTES) zeros)`, or `(None, None)` when `piano` is false or no clip has frames.
+        `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) or None per clip, the convention of `sample` -- not to be
+        confused with `_encode_video_frames`, the CLIP batcher over the same list.  A clip with a frame cache
+        `<video>.generated_frames_raw.2.npz` is read from it; one without goes through the HIP piano-frame preprocessor
+        (piano_frames.py), all its frames, and its cache is written (x3:1877-1891).  `video_paths=None`: the clips have no
+        place for a cache, only the frames each one uses are resized and nothing is written.  The stack is on this model's
+        device whenever a clip was preprocessed."""
+        if not piano:
+            return None, None
+        from .features import load_piano_frames
+        write = video_paths is not None
+        if video_paths is None:
+            if video_frames is None:
+                return None, None
+            # names under which no cache can exist; nothing is written (write_cache=False)
+            video_paths = [None if fr is None else f"<clip {i}>.mp4" for i, fr in enumerate(video_frames)]
+        stack = load_piano_frames(video_paths, l, video_frames=video_frames, write_cache=write,
+                                  preprocess=None if video_frames is None else self.piano_frame_preprocessor())
+        if stack is None:
+            return None, None
+        return stack, torch.zeros(stack.shape[0], int(l), self.cfg.notes)
+
+    def piano_frame_preprocessor(self):
+        """The `PianoFramePreprocessor` of this model's device (made on first use)."""
+        if self._piano_pre is None:
+            from .piano_frames import PianoFramePreprocessor
+            self._piano_pre = PianoFramePreprocessor(self._device)
+        return self._piano_pre
 
     def load_text_encoder(self, src, tokenizer=None):
         """The FLAN-T5 prompt encoder behind `prompt=` (x3:1412-1413): a `T5Encoder`, a local HF directory
@@ -462,7 +495,8 @@ class E2TTS:
                return_raw_output=None, save_to_filename=None, prompt=None, video_drop_prompt=None,
                audio_drop_prompt=None, video_paths=None, frames=None, midis=None,
                # build-side extensions
-               y0=None, text_embed=None, context=None, context_mask=None, frames_embed=None, trajectory_out=None, video_frames=None):
+               y0=None, text_embed=None, context=None, context_mask=None, frames_embed=None, trajectory_out=None, video_frames=None,
+               piano=False):
         """x3:2127-2305.  With lens == duration (every shipped call, predict.py:261-263) `cond` (b, n, C) only fixes shape and
         device.  With lens[0] != duration[0] it is the audio prompt of the infilling branch (x3:2196-2231, 2260-2261; needs
         if_cond_proj_in=True): zero-padded to the longest duration, masked to lens, added through cond_proj_in at every
@@ -472,7 +506,10 @@ class E2TTS:
         `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) per clip (or None), encoded by the CLIP image encoder
         (load_image_encoder): with `video_paths` only the clips without a feature cache are encoded -- in one batched pass -- and
         their caches written (x3:1706-1793; an existing cache wins); without `video_paths` the embeddings are resampled to the
-        latent rate and nothing is written."""
+        latent rate and nothing is written.
+        `piano`: with `frames` None and `video_frames` given, the same list also feeds the V2P frame encoder: `encode_video_frames`
+        builds the grey (b, 1, t, 100, 900) stack on the GPU (frame caches next to `video_paths` honoured and written; without
+        `video_paths` nothing is written) and hands it to `encode_frames` without leaving the device."""
         self.eval()
         if cond.ndim == 2:                                                          # raw wave (x3:2157-2160)
             if self.mel_spec is None:
@@ -484,6 +521,10 @@ class E2TTS:
         out_device = cond.device
         cfgm = self.cfg
         # -- frames / piano roll (x3:2164-2176)
+        if frames_embed is None and frames is None and piano and video_frames is not None:
+            if len(video_frames) != batch:
+                raise ValueError(f"video_frames: {len(video_frames)} entries for a batch of {batch}")
+            frames, _ = self.encode_video_frames(video_paths, cond_seq_len, True, video_frames=video_frames)      # predict.py:231
         if frames_embed is None:
             if frames is None or isinstance(frames, (int, float)):
                 # no frames (V2A): all-zero roll (x3:2164-2165).  predict.py:270 also lets a float placeholder through, which the

@@ -9,6 +9,8 @@ video and its output is kept next to the video as an `.npz` written by
 and every later call only resamples those rows to the 75 Hz latent rate by nearest video frame
 (x3:1803-1813).  A missing cache is made by the HIP ViT-bigG encoder (clip.py: 0.75 s per 250-frame clip in bf16x3) through
 `encode_video_cached(..., encoder_fn=)`, which E2TTS.sample(video_frames=...) and the CLI's --clip drive.
+The V2P side has the same two halves: the grey-frame cache `<video>.generated_frames_raw.2.npz` with its nearest-frame selection,
+and, for a video without one, `load_piano_frames(video_frames=, preprocess=)` over the HIP preprocessor of piano_frames.py.
 """
 from __future__ import annotations
 
@@ -123,12 +125,32 @@ def piano_frame_indices(n_video_frames: int, duration: float, l: int, start_samp
     return out
 
 
-def load_piano_frames(video_paths, l: int) -> torch.Tensor | None:
-    """Batch form of the cached `piano` branch of encode_video_frames: (b, 1, t, 100, 900) float32 with
+def piano_frames_from_video(frames, duration: float, l: int, preprocess, start_sample: int = 0, max_sample: int | None = None) -> torch.Tensor:
+    """One clip's (t_i, Ho, Wo) float32 stack from its decoded frames (F, H, W, 3) uint8: the frames `piano_frame_indices` picks,
+    each distinct one resized once by `preprocess(frames, select=[...]) -> (n, Ho, Wo)` (a `PianoFramePreprocessor`) and then
+    gathered -- a 30 fps clip repeats no frame, a 12 fps one uses each about twice.  The result stays on preprocess's device."""
+    idx = piano_frame_indices(frames.shape[0], duration, l, start_sample, max_sample)
+    distinct = sorted(set(idx))
+    out = preprocess(frames, select=distinct)
+    if len(distinct) == len(idx):
+        return out
+    pos = {j: k for k, j in enumerate(distinct)}
+    return out[torch.tensor([pos[j] for j in idx], device=out.device)]
+
+
+def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None, write_cache: bool = True) -> torch.Tensor | None:
+    """Batch form of the `piano` branch of encode_video_frames: (b, 1, t, 100, 900) float32 with
     t = max(floor(l / 3) + 1, longest clip) and zero frames as padding (x3:1935-1948); `None` paths give all-zero clips
-    (x3:1939-1941).  Returns None when no path has frames (x3:1927-1928).  Tuples are (path, start_sample, max_sample)."""
+    (x3:1939-1941).  Returns None when no path has frames (x3:1927-1928).  Tuples are (path, start_sample, max_sample).
+    `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) or None per path, the decoded video of a clip whose cache may be
+    missing; such a clip goes through `preprocess` (x3:1877-1891) instead of raising.  With `write_cache` all its F frames are
+    resized and saved in the reference's format, so that the reference and the next call read them; without, only the frames the
+    clip uses are resized and nothing is written.  An existing cache wins.  The result is on preprocess's device when any clip
+    was preprocessed, else on the CPU."""
+    if video_frames is not None and len(video_frames) != len(video_paths):
+        raise ValueError(f"video_frames: {len(video_frames)} entries for {len(video_paths)} video_paths")
     clips, lens = [], []
-    for vp in video_paths:
+    for n, vp in enumerate(video_paths):
         if vp is None:
             clips.append(None)
             lens.append(0)
@@ -137,18 +159,32 @@ def load_piano_frames(video_paths, l: int) -> torch.Tensor | None:
         if isinstance(vp, tuple):
             vp, start_sample, max_sample = vp
         fp = piano_frames_cache_path(vp)
-        if not os.path.exists(fp):
+        if os.path.exists(fp):
+            data = np.load(fp)
+            raw = torch.from_numpy(data["arr_0"])
+            idx = piano_frame_indices(raw.shape[0], data["arr_1"].item(), l, start_sample, max_sample)
+            clip = raw[torch.tensor(idx)]
+        elif video_frames is not None and video_frames[n] is not None:
+            if preprocess is None:
+                raise ValueError("load_piano_frames: video_frames needs preprocess= (a PianoFramePreprocessor)")
+            fr, duration = video_frames[n]
+            if write_cache:
+                raw = preprocess(fr).unsqueeze(-1)                                # (F, 100, 900, 1), x3:1890
+                save_piano_frames_cache(fp, raw, float(duration))
+                idx = piano_frame_indices(raw.shape[0], float(duration), l, start_sample, max_sample)
+                clip = raw[torch.tensor(idx, device=raw.device)]
+            else:
+                clip = piano_frames_from_video(fr, float(duration), l, preprocess, start_sample, max_sample).unsqueeze(-1)
+        else:
             raise FileNotFoundError(f"{fp}: no cached piano frames for {vp} (the reference decodes the video with moviepy here)")
-        data = np.load(fp)
-        raw = torch.from_numpy(data["arr_0"])
-        idx = piano_frame_indices(raw.shape[0], data["arr_1"].item(), l, start_sample, max_sample)
-        clips.append(raw[torch.tensor(idx)])
-        lens.append(len(idx))
+        clips.append(clip)
+        lens.append(clip.shape[0])
     if not any(c is not None for c in clips):
         return None
     H, W = next(c for c in clips if c is not None).shape[1:3]
+    dev = next((c.device for c in clips if c is not None and c.device.type != "cpu"), torch.device("cpu"))
     t = max(int(l // 3.0) + 1, max(lens))
-    out = torch.zeros(len(clips), t, H, W, 1)
+    out = torch.zeros(len(clips), t, H, W, 1, device=dev)
     for i, c in enumerate(clips):
         if c is not None:
             out[i, : c.shape[0]] = c

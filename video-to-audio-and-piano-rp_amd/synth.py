@@ -277,3 +277,29 @@ def synthetic_video_frames(n: int, h: int, w: int, seed: int = 0) -> "np.ndarray
         img = base.transpose(1, 2, 0) + rng.normal(0, 20, (h, w, 3))
         out[f] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
     return out
+
+
+def synthetic_edge_frames(n: int, h: int, w: int, seed: int = 0) -> "np.ndarray":
+    """(n, h, w, 3) uint8 RGB test frames of hard edges, which a bicubic filter overshoots on both sides of [0, 255] (the smooth
+    frames above never do): frame f cycles through vertical bars, horizontal bars and a checkerboard of 0 / 255 with a period of
+    1 to 4 pixels on top of a coarse seeded 0 / 255 block pattern (so that the overshoot survives a reducing filter, which
+    averages the fine pattern away), and a frame of saturated colours (every channel 0 or 255, in seeded blocks)."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    yy, xx = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    out = np.empty((n, h, w, 3), np.uint8)
+    for f in range(n):
+        px = 1 + (f // 4) % 4
+        by, bx = max(1, h // int(rng.integers(3, 9))), max(1, w // int(rng.integers(3, 9)))
+        coarse = rng.integers(0, 2, (h // by + 1, w // bx + 1, 3))[yy // by, xx // bx]          # (h, w, 3) of 0 / 1
+        kind = f % 4
+        if kind == 3:
+            out[f] = (coarse * 255).astype(np.uint8)                                              # saturated colours
+            continue
+        fine = ((xx // px) % 2, (yy // px) % 2, (xx // px + yy // px) % 2)[kind]
+        # fine pattern in the upper left half of every block, plain blocks elsewhere: edges at both scales
+        use_fine = ((yy // by + xx // bx) % 2 == 0)
+        grey = np.where(use_fine, fine, coarse[..., 0])
+        out[f] = (grey * 255).astype(np.uint8)[..., None]
+    return out
