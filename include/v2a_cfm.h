@@ -128,7 +128,14 @@ typedef struct v2a_gemm_args {
   /* 0 = the library picks the tile shape for the fastest stand-alone launch.  k + 1 = use LDS-DMA tile configuration k of
    * v2a_tuning.gemm_force_tile for THIS call (bf16 x bf16 only).  The sampler passes 1 (128x256 tiles, one workgroup per CU) for
    * the text / frames streams: their GEMMs run beside the audio stream's, and few fat workgroups that own whole CUs disturb
-   * the critical path less than many small ones spread over every CU (+3.5 % end to end, measured). */
+   * the critical path less than many small ones spread over every CU (+3.5 % end to end, measured).
+   * Split operands (a_dtype V2A_BF16_SPLIT) have tile shapes of their own, 0 = by shape or 1..7 (any other value is rejected):
+   *   1 = 64x64, 2 = 128x64, 3 = 128x128 (8 waves, 2-deep ring), 4 = 64x128 (8 waves): LDS-DMA ring, a stage = 64 k of the four planes;
+   *   5 = the 256x256 phase-interleaved (8-phase) kernel: a stage = 32 logical k, staged as rows [32 k hi | 32 k lo] of both operands,
+   *       three products (A_lo W_hi, A_hi W_lo, A_hi W_hi) from one set of fragments; dense rows only; every ka a multiple of 64;
+   *   6 = 128x256, 7 = 128x128 (8 waves, 3-deep ring): a stage = 32 k of the four planes.
+   * With a_row_offset / out_row_offset only 0 and 1..4 are admitted (a_ktile_offset is laid out for 64-wide K tiles).  The sum order
+   * of an output element depends on the shape chosen, so results of different tile_hint values agree to rounding, not bit for bit. */
   int32_t tile_hint;
   /* RMSNorm folded into its neighbours (bf16 x bf16, 16-byte aligned epilogue operands, N % 32 == 0):
    * PRODUCER (RESID / GATE_RESID with out_bf16): with norm_gamma the shadow is out_bf16[m][n] = bf16(out[m][n] * gamma[n]),

@@ -3,8 +3,8 @@
 process: each configuration inside a hipGraph of back-to-back launches on random data, interleaved rounds, best of 5 (rule 24 of the
 CDNA guide).  K may be a '+'-joined list of logical segments (cross-condition: 1024+1280+512).
 
-tile_hint: 0 = by shape, 1 = 64x64, 2 = 128x64, 3 = 128x128 / 8 waves / 2 stages, 4 = 64x128 / 8 waves, 5 = the 256x256 8-phase kernel on
-three passes, 6 = 128x256 / 8 waves (32-wide K stages), 7 = 128x128 / 8 waves (32-wide K stages).
+tile_hint: 0 = by shape, 1 = 64x64, 2 = 128x64, 3 = 128x128 / 8 waves / 2 stages, 4 = 64x128 / 8 waves, 5 = the 256x256 8-phase kernel (stages of
+32 logical k x hi | lo planes, three products per stage), 6 = 128x256 / 8 waves (32-wide K stages), 7 = 128x128 / 8 waves (32-wide K stages).
 (profiles/r05_split_probe.txt was taken with two more shapes in the build: there t7 / t9 = 64x128 / 4 waves on 32-wide stages with 3 / 4 stages, and t8 = today's 7.)
 usage: python scripts/split_probe.py [--tiles 0,4,5,6,7] [--epi resid|store|geglu|gate] 1564x1024x4096 1564x1024x1024+1280+512 ...
 """

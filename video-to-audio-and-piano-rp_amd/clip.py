@@ -29,7 +29,7 @@ OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 PRECISION_BITS = 32 - 8 - 2          # Pillow's 8-bit resample
 _PREFIXES = ("image_encoder.",)
-# bf16x3 tile of every GEMM pinned (the 256x256 8-phase kernel, three passes over K): the summation order of a split GEMM depends on
+# bf16x3 tile of every GEMM pinned (the 256x256 8-phase kernel, three products per 32-wide K stage): the summation order of a split GEMM depends on
 # the kernel, and a by-shape choice would make a frame's result depend on how many frames share its chunk
 _SPLIT_TILE = 5
 

@@ -532,12 +532,9 @@ int dispatch_s3(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
   return v2a_fail(V2A_ERR_ARG, "v2a_gemm(split bf16): unsupported epilogue %d / out_dtype %d for this tile shape", a->epilogue, a->out_dtype);
 }
 
-// split operands on the 8-phase kernel: three passes over the logical K -- A_hi x W_hi, A_hi x W_lo, A_lo x W_hi -- each over all logical
-// segments (GemmParams::s3_kl; the kernel derives plane and segment of every K tile)
-void split_as_three_passes(GemmParams& q) {
-  q.s3_kl = q.K;
-  q.K = 3 * q.K;
-}
+// split operands on the 8-phase kernel: marks the launch as split (GemmParams::s3_kl = the logical K, K stays the logical K).  The kernel
+// stages 32 logical k of the hi and the lo plane of both operands together and forms A_lo x W_hi, A_hi x W_lo, A_hi x W_hi from one set of fragments
+void mark_split_8phase(GemmParams& q) { q.s3_kl = q.K; }
 
 }  // namespace
 
@@ -746,7 +743,6 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
   GemmParams p;
   if (int rc = gemm_prepare(a, p)) return rc;
   const bool split_in = a->a_dtype == V2A_BF16_SPLIT;
-  const int K = p.K;
   const v2a_detail::GemmTuning tune = v2a_detail::g_gemm_tuning;
   hipStream_t s = (hipStream_t)stream;
   if (a->compute_dtype == V2A_F32) {
@@ -770,17 +766,17 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
     // 8 waves (wave tile 64x64; 3 stages of 48 KB), 7 = 128x128 with 8 waves (3 stages of 32 KB).  (64x128 with four waves on 32-wide
     // stages -- 72 KB, two workgroups per CU -- measured 15-25 % slower than shape 4 at every size: profiles/r05_split_probe.txt; not kept.)
     int cfg = a->tile_hint;
-    // the phase-interleaved 256x256 kernel on three passes over the logical K (hi x hi, hi x lo, lo x hi; it re-reads A_hi and W_hi, but
-    // its K loop hides the operand stream behind the MFMAs): wide outputs from 150 tiles (audio feed-forward at one clip: 76 us against
-    // 102 us on the best split ring tile) and -- round 5 -- narrow ones (512 < N < 2048, any number of logical segments) from 150 tiles,
+    // the phase-interleaved 256x256 kernel on stages of 32 logical k x (hi | lo) planes, three products per stage (lo x hi, hi x lo,
+    // hi x hi; every plane is staged and read once, and its K loop hides the operand stream behind the MFMAs): wide outputs from 150
+    // tiles (audio feed-forward at one clip, measured on the earlier three-pass form: 76 us against 102 us on the best split ring tile) and -- round 5 -- narrow ones (512 < N < 2048, any number of logical segments) from 150 tiles,
     // i.e. from ~6 clips per GPU: at 8 clips the 64x128 split ring ran them at 28 % of the MFMA peak (issued products) against 46 % here.
     // tile_hint 5 asks for it, 0 picks by shape.
     const bool wide8 = !scattered && tune.use_8phase && (cfg == 5 || (cfg == 0 && a->N > 512 && nt(256, 256) >= 150));
     if (wide8) {
       GemmParams q = p;
-      split_as_three_passes(q);
+      mark_split_8phase(q);
 #ifdef V2A_GEMM_PROBE
-      if (tune.dbg & 32) { q.s3_kl = 0; q.K = K; }      // error attribution: hi x hi only
+      if (tune.dbg & 32) q.s3_kl = 0;                   // error attribution: hi x hi only (the plain form on the hi planes)
 #endif
       return v2a_detail::launch_gemm_8phase(q, a->epilogue, a->out_dtype == V2A_BF16_SPLIT ? V2A_BF16 : a->out_dtype, s);
     }

@@ -1,7 +1,8 @@
 // 256x256 bf16 MFMA GEMM for gfx950 with a phase-interleaved K loop:  acc[m][n] = sum_k A[m][k] * W[n][k].
 //
 // One workgroup = 8 waves (2 along M x 4 along N) = one 256x256 output tile, wave tile 128x64 = four 64x32 quadrants.
-// A K tile (64 deep) lives in LDS as four 16 KB half tiles, two LDS buffers (128 KB, one workgroup per CU):
+// A K tile (64 deep; split operands: a stage of 32 logical k, see below) lives in LDS as four 16 KB half tiles, two LDS buffers
+// (128 KB, one workgroup per CU):
 //   AH0 / AH1 : the first / second 64 rows of BOTH wave rows      (local row r -> tile row r + 64*(r >= 64) + 64*s)
 //   BH0 / BH1 : the first / second 32 columns of ALL FOUR wave columns (local row r -> tile col 64*(r >> 5) + (r & 31) + 32*s)
 // so that every wave reads one A sub-tile (8 x ds_read_b128) or one B sub-tile (4 x ds_read_b128) per phase.  Rows are
@@ -21,8 +22,13 @@
 // SIMDs pairwise), so on every SIMD one wave multiplies while its partner reads LDS and issues DMA.  vmcnt is never 0 inside
 // the loop: three half tiles stay in flight across every barrier.
 //
-// Dense operands only (no offset tables); up to 3 K-concatenated A segments; split (hi | lo plane) operands as three passes over the
-// logical K (GemmParams::s3_kl); epilogues shared with gemm.hip.
+// Dense operands only (no offset tables); up to 3 K-concatenated A segments; epilogues shared with gemm.hip.
+//
+// Split (hi | lo plane) operands (SPLIT, GemmParams::s3_kl): a stage is 32 LOGICAL k and the 128-B LDS row of tile row r is
+// [32 k of the hi plane | 32 k of the lo plane], for A and for W alike -- only the DMA source address knows (logical chunks 0-3 come from the
+// hi plane, 4-7 from the lo plane of the same k).  The unchanged fragment reads then return the hi fragment in [..][0] and the lo fragment of the
+// same k in [..][1], and a quadrant is 24 MFMAs: A_lo x W_hi, A_hi x W_lo, A_hi x W_hi (the term order of the split ring kernel's K step).  Every
+// plane byte is staged and read once; phase table, barriers and the counted vmcnt chain are those of the plain form, on stages of 32.
 #include "gemm_common.h"
 
 namespace {
@@ -39,7 +45,7 @@ constexpr int kSkip = 0;
 // was 2-3 % faster per launch only while its DMAs were issued in the read blocks, where the wave row that runs one barrier behind may
 // still have fragment reads of the restaged half tile in flight: safe by timing, not by a barrier.  Issued behind the barriers that make
 // it safe by construction it was 10-15 % slower than four phases: profiles/r03_8phase_two_phase_mode.txt.  Four phases stay.)
-template <int EPI, typename OutT, int MODE>
+template <int EPI, typename OutT, int MODE, bool SPLIT>
 __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
   constexpr bool STAGGER = MODE != 2;
   constexpr int BM = 256, BN = 256, WM = 128, WN = 64, TM = 8, TN = 4;
@@ -66,7 +72,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
 
   // ---- LDS-DMA source geometry: wave w fills 8-row groups w and w + 8 of every half tile
   const int srow = lane >> 3;
-  const uint32_t schunk_b = (uint32_t)(((lane & 7) ^ srow) << 4);   // byte offset of the logical chunk this lane fetches
+  const int schunk = (lane & 7) ^ srow;                             // the logical 16-B chunk of the LDS row this lane fetches
+  // byte offset of that chunk in the source row.  Split operands: chunks 0-3 are 32 k of the hi plane, chunks 4-7 the same k of the lo plane
+  // (the plane distance is added per operand and segment below)
+  const uint32_t schunk_b = (uint32_t)((SPLIT ? schunk & 3 : schunk) << 4);
+  const bool slo = SPLIT && schunk >= 4;
+  const int kl = SPLIT ? p.s3_kl : 0;                               // split operands: the logical K = elements from W_hi to W_lo of a row
   uint32_t woff[2][2];       // byte offset into W per (half s, group i)
 #pragma unroll
   for (int s = 0; s < 2; ++s)
@@ -74,10 +85,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
     for (int i = 0; i < 2; ++i) {
       const int r = 8 * (wave + 8 * i) + srow;                 // local row of the half tile
       const int wrw = n0 + 64 * (r >> 5) + (r & 31) + 32 * s;
-      woff[s][i] = (uint32_t)(((int64_t)(wrw < p.N ? wrw : p.N - 1) * p.ldw) * 2) + schunk_b;
+      woff[s][i] = (uint32_t)(((int64_t)(wrw < p.N ? wrw : p.N - 1) * p.ldw) * 2) + schunk_b + (slo ? (uint32_t)kl * 2 : 0u);
     }
   const char* wbase = reinterpret_cast<const char*>(p.w);
-  const int nk = p.K / 64;
+  constexpr int KS = SPLIT ? 32 : 64;            // k per stage, and the bytes one plane of a row advances per stage
+  constexpr int KSH = SPLIT ? 5 : 6;
+  const int nk = p.K / KS;                       // p.K is the logical K in both forms
 
   // segment table as scalar base + deltas: a segment switch is two s_cselect per quantity, not a kernel-argument load.  Deltas rather
   // than a select between the three values themselves: a select of two captured variables becomes a load through a selected address,
@@ -89,38 +102,33 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
   const int32_t dl1 = nseg > 1 ? (int32_t)(p.lda[1] * 2) - ldb0 : 0, dl2 = nseg > 2 ? (int32_t)((p.lda[2] - p.lda[1]) * 2) : 0;
   const int kend0 = nseg > 1 ? p.kend[0] : 0x7fffffff, kend1 = nseg > 2 ? p.kend[1] : 0x7fffffff;
   const int dk2 = nseg > 2 ? p.kend[1] - p.kend[0] : 0;
-  // split operands (GemmParams::s3_kl): K tile kt belongs to pass kt / nkl and is K tile kt % nkl of the logical K; pass 2 reads the lo
-  // plane of its A segment (GemmParams::alo further along the row), pass 1 the lo plane of W (s3_kl elements further along the row)
-  const int kl = p.s3_kl;
-  const int nkl = kl > 0 ? kl / 64 : 0x3fffffff;                 // plain operands: every K tile is in "pass 0"
-  const int klog = kl > 0 ? kl : p.K;                            // the logical K
-  const int sb0 = kl > 0 ? (int)(2 * p.alo[0]) : 0;              // bytes from a row's hi plane to its lo plane, by segment
-  const int dsb1 = kl > 0 && nseg > 1 ? (int)(2 * p.alo[1]) - sb0 : 0;
-  const int dsb2 = kl > 0 && nseg > 2 ? (int)(2 * p.alo[2]) - (sb0 + dsb1) : 0;
-  const int64_t wlo = (int64_t)kl * 2;
+  // split operands: bytes from a row's hi plane to its lo plane, by segment (GemmParams::alo)
+  const int sb0 = SPLIT ? (int)(2 * p.alo[0]) : 0;
+  const int dsb1 = SPLIT && nseg > 1 ? (int)(2 * p.alo[1]) - sb0 : 0;
+  const int dsb2 = SPLIT && nseg > 2 ? (int)(2 * p.alo[2]) - (sb0 + dsb1) : 0;
   // Operand streams (round 5).  Each of the three DMA streams -- A half 0, A half 1, W (both halves) -- is issued strictly in K-tile order, so
-  // each keeps a RUNNING wave-uniform base pointer stepped by 128 B per K tile and a count of K tiles left in its (pass, segment); per-lane
-  // row offsets (row x the segment's row stride) are VGPRs set up per (pass, segment).  Deriving pass, segment, base and row stride of EVERY K
-  // tile from kt cost ~45 scalar instructions and two 64-bit multiply-adds per staging call -- ~350 cycles of issue in the load part of a
-  // phase whose partner multiplies for 256: the load parts, not the MFMAs, paced the loop (profiles/r05_8phase_even_bands_ab.txt).
+  // each keeps a RUNNING wave-uniform base pointer stepped by one stage (128 B; 64 B of each plane for split operands) and a count of stages left
+  // in its segment; per-lane row offsets (row x the segment's row stride, plus the lane's chunk and plane) are VGPRs set up per segment.
+  // Deriving segment, base and row stride of EVERY K tile from kt cost ~45 scalar instructions and two 64-bit multiply-adds per staging
+  // call -- ~350 cycles of issue in the load part of a phase whose partner multiplies for 256: the load parts, not the MFMAs, paced the
+  // loop (profiles/r05_8phase_even_bands_ab.txt).
   const char* aptr[2];
   int aleft[2] = {0, 0};
   uint32_t aoff[2][2];
   auto a_setup = [&](int s, int kt) {
-    const bool p1 = kt >= nkl, p2 = kt >= 2 * nkl;         // p2 implies p1
-    const int k0 = (kt - (p1 ? nkl : 0) - (p2 ? nkl : 0)) * 64;
+    const int k0 = kt * KS;
     const bool s1 = k0 >= kend0, s2 = k0 >= kend1;       // s2 implies s1
     const int kbeg = (s1 ? kend0 : 0) + (s2 ? dk2 : 0);
-    const int lo = p2 ? sb0 + (s1 ? dsb1 : 0) + (s2 ? dsb2 : 0) : 0;
-    aptr[s] = reinterpret_cast<const char*>(a0 + (s1 ? da1 : 0) + (s2 ? da2 : 0)) + (int64_t)(k0 - kbeg) * 2 + lo;
+    aptr[s] = reinterpret_cast<const char*>(a0 + (s1 ? da1 : 0) + (s2 ? da2 : 0)) + (int64_t)(k0 - kbeg) * 2;
     const uint32_t ldb = (uint32_t)(ldb0 + (s1 ? dl1 : 0) + (s2 ? dl2 : 0));
-    const int kstop = min(klog, s2 ? 0x7fffffff : (s1 ? kend1 : kend0));   // end of this segment within the pass
-    aleft[s] = (kstop - k0) >> 6;
+    const uint32_t lo = slo ? (uint32_t)(sb0 + (s1 ? dsb1 : 0) + (s2 ? dsb2 : 0)) : 0u;   // this lane's chunk lies in the segment's lo plane
+    const int kstop = min(p.K, s2 ? 0x7fffffff : (s1 ? kend1 : kend0));   // end of this segment
+    aleft[s] = (kstop - k0) >> KSH;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int r = 8 * (wave + 8 * i) + srow;                 // local row of the half tile
       const int ar = m0 + r + ((r >= 64) ? 64 : 0) + 64 * s;
-      aoff[s][i] = (uint32_t)(ar < p.M ? ar : p.M - 1) * ldb + schunk_b;
+      aoff[s][i] = (uint32_t)(ar < p.M ? ar : p.M - 1) * ldb + schunk_b + lo;
     }
   };
   auto stage_a = [&](int s, int kt, int buf) {
@@ -130,17 +138,15 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
     for (int i = 0; i < 2; ++i)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(aptr[s] + aoff[s][i]),
                                        (__attribute__((address_space(3))) void*)(dst + (wave + 8 * i) * 1024), 16, 0, 0);
-    aptr[s] += 128;
+    aptr[s] += 2 * KS;
     --aleft[s];
   };
   const char* wptr = wbase;
   int wleft = 0;
   auto stage_b = [&](int kt, int buf) {                    // both halves of W's K tile kt
     if (wleft == 0) {
-      const bool p1 = kt >= nkl, p2 = kt >= 2 * nkl;
-      const int ktl = kt - (p1 ? nkl : 0) - (p2 ? nkl : 0);
-      wptr = wbase + (int64_t)ktl * 128 + (p1 && !p2 ? wlo : 0);
-      wleft = min(nkl, nk) - ktl;
+      wptr = wbase + (int64_t)kt * (2 * KS);
+      wleft = nk - kt;
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
                                          (__attribute__((address_space(3))) void*)(dst + (wave + 8 * i) * 1024), 16, 0, 0);
       }
     }
-    wptr += 128;
+    wptr += 2 * KS;
     --wleft;
   };
 
@@ -192,13 +198,26 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
     constexpr int SA = decltype(sa_c)::value, SB = decltype(sb_c)::value;
     if (!(SA == 0 ? need0 : need1)) return;
     __builtin_amdgcn_s_setprio(1);
+    if constexpr (SPLIT) {
+      // fragment [..][0] = hi plane, [..][1] = lo plane of the same 32 k: A_lo x W_hi, A_hi x W_lo, A_hi x W_hi; product-outermost, so eight
+      // independent accumulators lie between two MFMAs on the same one
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
+      for (int t = 0; t < 3; ++t)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[4 * SA + i][2 * SB + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], acc[4 * SA + i][2 * SB + j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j)
+            acc[4 * SA + i][2 * SB + j] =
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][t == 0 ? 1 : 0], bf[j][t == 1 ? 1 : 0], acc[4 * SA + i][2 * SB + j], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[4 * SA + i][2 * SB + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][kk], bf[j][kk], acc[4 * SA + i][2 * SB + j], 0, 0, 0);
+    }
     __builtin_amdgcn_s_setprio(0);
   };
   using I0 = std::integral_constant<int, 0>;
@@ -298,8 +317,15 @@ int launch_8ph(const GemmParams& p_in, hipStream_t s) {
     return 0;
   };
   int rc;
-  if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2>);
-  else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1>);
+  if (p.s3_kl != 0) {
+    if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2, true>);
+    else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1, true>);
+  } else if constexpr (EPI == V2A_EPI_GELU) {
+    return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): GELU needs split operands");
+  } else {
+    if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2, false>);
+    else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1, false>);
+  }
   if (rc) return rc;
   return v2a_check_launch("v2a_gemm(8-phase)");
 }

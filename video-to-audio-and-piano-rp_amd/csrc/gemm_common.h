@@ -59,9 +59,9 @@ struct GemmParams {
   int32_t out2_split, out_split;
   int64_t alo[3];           // split operands: elements from a row's hi plane to its lo plane, per segment (default: the segment's K extent)
   int64_t out2_lo;          // split shadow: elements from the hi plane to the lo plane of a shadow row (default: N)
-  // 8-phase kernel, split (hi | lo plane) operands: s3_kl = the LOGICAL K (sum of the segments' extents), K = 3 * s3_kl, and the K loop
-  // walks the logical K three times: pass 0 = A_hi x W_hi, pass 1 = A_hi x W_lo, pass 2 = A_lo x W_hi -- every pass over all (up to
-  // three) logical segments, whose rows are [hi k | lo k] (lda >= 2k), against weight rows [W_hi (s3_kl) | W_lo (s3_kl)].  0 = plain operands
+  // 8-phase kernel, split (hi | lo plane) operands: s3_kl = K = the LOGICAL K (sum of the segments' extents).  The K loop walks it once in
+  // stages of 32 k, each staged as [32 k hi | 32 k lo] rows of both operands, and adds A_lo x W_hi, A_hi x W_lo, A_hi x W_hi per stage -- over all (up
+  // to three) logical segments, whose rows are [hi k | lo k] (lda >= 2k), against weight rows [W_hi (s3_kl) | W_lo (s3_kl)].  0 = plain operands
   int32_t s3_kl;
   int32_t dbg;              // probe builds only (-DV2A_GEMM_PROBE, scripts/probes/kloop_probe.py): K-loop parts switched off by bit
 };
