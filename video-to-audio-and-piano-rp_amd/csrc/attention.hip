@@ -4,13 +4,16 @@
 //   o_i  = sigmoid(gate_i) * sum_j p_ij v_j;          rows i >= q_len -> 0
 //
 // The tanh soft-clamp sits between QK^T and the softmax, which rules out stock flash
-// kernels.  Two implementations:
-//   * attn_rowlane_kernel<T>: exact-fp32 arithmetic, one query row per lane, K/V tiles
-//     broadcast from LDS.  This is the parity-mode kernel (and the fallback for odd shapes).
-//   * attn_mfma_kernel (bf16): flash-style, QK^T and PV on v_mfma_f32_16x16x32_bf16 with
-//     the softmax row reductions done by wavefront shuffles.
-#include "v2a_common.h"
-#include <type_traits>
+// kernels.  Five kernels here and in qproj_xattn.hip:
+//   * attn_rowlane_kernel<T>: exact-fp32 arithmetic, one query row per lane, K/V tiles broadcast from LDS.  The fallback for
+//     shapes the MFMA kernels do not take (unaligned head slices).
+//   * attn_mfma_kernel (bf16), attn_mfma_split_kernel (fp32 tensors as hi | lo bf16 planes, the bf16x3 mode) and
+//     attn_mfma_f32_kernel (fp32 MFMA): flash-style, QK^T and PV on MFMAs, the softmax row reductions by wavefront shuffles.
+//   * qproj_xattn_kernel (qproj_xattn.hip): the bf16 and the split arithmetic over one key tile, behind the q projection.
+// The four MFMA kernels differ in their tile loads and stores and in how an operand becomes an MFMA fragment; what they share --
+// clamp / mask / softmax, the V^T fragment, the merge of two key groups, the output factor and stores, the clamp-mode dispatch --
+// is defined once in attn_core.h.
+#include "attn_core.h"
 
 namespace v2a_detail { extern int g_attn_one_group_from; extern int g_probe_dbg; }
 
@@ -28,6 +31,12 @@ struct AttnParams {
   int32_t out_split;     // split kernel only: out is a bf16 buffer that receives hi | lo planes (lo plane H * 64 columns after hi)
   int32_t dbg;           // probe builds only
 };
+
+// sigmoid of the head's gate logit of one query (1 without a gate): the MFMA kernels' input of attn_out_factor
+template <typename T>
+__device__ __forceinline__ float attn_gate(const AttnParams& p, int b, int query, int h) {
+  return p.gate ? sigmoid_f(to_f32(reinterpret_cast<const T*>(p.gate)[b * p.gbs + (int64_t)query * p.grs + h])) : 1.f;
+}
 
 // ------------------------------------------------------------------------------------------
 // Row-per-lane kernel.  grid = (ceil(Nq/64), H, B), block = 64.
@@ -166,10 +175,7 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_kernel(const AttnParams p)
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = CLAMP == 2 ? 0.f : -INFINITY, l = 0.f;
-  constexpr float LOG2E = 1.4426950408889634f;
-  // zc: raw QK^T -> argument of the base-2 exponential (2x*log2e with x = scale*s/clamp), or -> log2 units w/o clamp
-  const float zc = p.clamp > 0.f ? 2.0f * LOG2E * p.scale / p.clamp : p.scale * LOG2E;
-  const float c2 = p.clamp * LOG2E;
+  const AttnLogitScale sc = attn_logit_scale(p.scale, p.clamp);
 
   // staging registers: rows (tid>>3)+32i, 16-B chunk tid&7 of the K tile and of the V tile (same geometry, same LDS image).
   // One register set: right after the barrier that ends iteration jt-1, tile jt+1 (requested a whole iteration earlier) is
@@ -193,17 +199,6 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_kernel(const AttnParams p)
       *reinterpret_cast<bf16x8*>(base + off) = kreg[i];
       *reinterpret_cast<bf16x8*>(base + K_ELEMS + off) = vreg[i];
     }
-  };
-  // V^T fragments by the transposed LDS read (ds_read_b64_tr_b16): per 16-lane group a block of 4 keys x 16 head dimensions,
-  // lane 4q+p of the group supplies the address of (key q, dimensions 4p..4p+3), lane i receives dimension i of the 4 keys --
-  // the [d][4 consecutive keys] operand of O^T = V^T P^T straight from the row-major image (the round-1 kernel transposed V
-  // on its way into LDS with eight 4-byte writes per thread and tile).  EXEC is all ones wherever this is read.
-  const int vq = lr >> 2, vp = lr & 3;
-  auto vt_read = [&](const bf16_t* vs, int key0, int dt) {
-    const int key = key0 + 4 * g + vq;
-    const int chunk = 2 * dt + (vp >> 1);
-    const bf16_t* ad = vs + key * 64 + ((chunk ^ (key & 7)) << 3) + 4 * (vp & 1);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)ad);
   };
 
   const int ntiles_all = (kvn + TK - 1) / TK;
@@ -236,94 +231,15 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_kernel(const AttnParams p)
         s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[t], 0, 0, 0);
       }
     }
-    // ---- soft clamp, key mask, online softmax (query on the lane), all in base-2 units:
-    //   clamp*tanh(x)*log2e = C - 2C / (2^(2x log2e) + 1),  C = clamp*log2e   -> v_exp, v_rcp, 1 fma
-    //   p = 2^(t - m)                                                          -> 1 sub, v_exp
-    const int j0 = (jt * NG + grp) * TK;
-    bf16x8 pf[2];
-    if constexpr (CLAMP == 2) {
-      // p = 2^(C - 2C / (2^(2x log2e) + 1)) directly; masked keys (last tile only) get weight 0
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float e = __builtin_amdgcn_exp2f(s[t][j] * zc);
-          s[t][j] = __builtin_amdgcn_exp2f(fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2));
-        }
-      if (j0 + TK > kvn) {             // only the last tile can be partial (wave-uniform branch)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          l += s[t][j];
-          pf[t >> 1][(t & 1) * 4 + j] = (bf16_t)s[t][j];
-        }
-    } else {
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float v;
-        if constexpr (CLAMP == 1) {
-          const float e = __builtin_amdgcn_exp2f(s[t][j] * zc);
-          v = fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2);
-        } else {
-          v = s[t][j] * zc;
-        }
-        s[t][j] = v;
-      }
-    if (j0 + TK > kvn) {             // only the last tile can be partial (wave-uniform branch)
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = -INFINITY;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tmax = fmaxf(tmax, s[t][j]);
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float mn = fmaxf(m, tmax);
-    const float alpha = __builtin_amdgcn_exp2f(m - mn);
-    m = mn;
-    l *= alpha;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[dt][j] *= alpha;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float pv = __builtin_amdgcn_exp2f(s[t][j] - mn);
-        l += pv;
-        pf[t >> 1][(t & 1) * 4 + j] = (bf16_t)pv;
-      }
-    }
+    // ---- soft clamp, key mask, online softmax (query on the lane); the bf16 weights ARE the next B operand
+    attn_weights<CLAMP, true>(s, m, l, o, (jt * NG + grp) * TK, kvn, g, sc);
+    bf16x8 pf[1][2];
+    attn_pack_weights(s, l, pf);
     // ---- O^T += V^T P^T : 4 d tiles x 2 k-steps of 32 keys (permuted key order, see header)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2) {
-        const bf16x4 lo = vt_read(vt, 32 * ks2, dt);
-        const bf16x4 hi = vt_read(vt, 32 * ks2 + 16, dt);
-        bf16x8 vf;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          vf[j] = lo[j];
-          vf[4 + j] = hi[j];
-        }
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ks2], o[dt], 0, 0, 0);
-      }
+      for (int ks2 = 0; ks2 < 2; ++ks2) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(attn_vt_frag(vt, ks2, dt, g, lr), pf[0][ks2], o[dt], 0, 0, 0);
     }
     __syncthreads();
   }
@@ -331,43 +247,11 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_kernel(const AttnParams p)
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if constexpr (NG == 2) {
-    // group 1 hands (m, l, O) to group 0, lane for lane (same query / d mapping), through its own dead LDS ring
-    float* xch = reinterpret_cast<float*>(lds_all + RING);          // 18 floats x 256 lanes = 18 KB < RING bytes
-    __syncthreads();
-    if (grp == 1) {
-      float* dst = xch + tid;
-      dst[0] = m;
-      dst[256] = l;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[(2 + dt * 4 + j) * 256] = o[dt][j];
-    }
-    __syncthreads();
-    if (grp == 1) return;
-    const float* src = xch + tid;
-    const float m2 = src[0], l2 = src[256];
-    const float mn = fmaxf(m, m2);
-    const float a1 = __builtin_amdgcn_exp2f(m - mn), a2 = (m2 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
-    l = l * a1 + l2 * a2;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[dt][j] = o[dt][j] * a1 + src[(2 + dt * 4 + j) * 256] * a2;
+    if (!attn_merge_key_groups(reinterpret_cast<float*>(lds_all + RING), grp, tid, m, l, o)) return;
   }
   if (query >= p.Nq) return;
-  const int qn = p.q_len ? min(p.q_len[b], p.Nq) : p.Nq;
-  float gt = 1.f;
-  if (p.gate) gt = sigmoid_f((float)reinterpret_cast<const bf16_t*>(p.gate)[b * p.gbs + (int64_t)query * p.grs + h]);
-  const float f = (query < qn && l > 0.f) ? gt / l : 0.f;
-  bf16_t* op = reinterpret_cast<bf16_t*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    bf16x4 ov;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ov[j] = (bf16_t)(o[dt][j] * f);
-    *reinterpret_cast<bf16x4*>(op + 16 * dt) = ov;
-  }
+  const float f = attn_out_factor(p.q_len, b, p.Nq, query, l, attn_gate<bf16_t>(p, b, query, h));
+  attn_store(reinterpret_cast<bf16_t*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g, o, f);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -378,17 +262,6 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_kernel(const AttnParams p)
 // the fp32 rows into LDS (four planes per stage), q once per workgroup, P in registers after the fp32 softmax.  Replaces the
 // one-query-per-lane fp32 VALU kernel in that mode: 518 -> ~70 us per self-attention launch at one clip.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const bf16_t ha = (bf16_t)a[e], hb = (bf16_t)b[e];
-    hi[e] = ha;
-    hi[4 + e] = hb;
-    lo[e] = (bf16_t)(a[e] - (float)ha);
-    lo[4 + e] = (bf16_t)(b[e] - (float)hb);
-  }
-}
-
 // QG (round 5): 2 = TWO groups of four waves share the K / V tiles of one ring -- 128 queries per workgroup, every thread converts and
 // stages half as many K / V elements per tile and the tiles are fetched once per 128 queries instead of once per 64 (with NG = 1 only).
 template <int NG, int CLAMP, int QG = 1>
@@ -427,9 +300,12 @@ __global__ __launch_bounds__(256 * NG * QG) void attn_mfma_split_kernel(const At
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = CLAMP == 2 ? 0.f : -INFINITY, l = 0.f;
-  constexpr float LOG2E = 1.4426950408889634f;
-  const float zc = p.clamp > 0.f ? 2.0f * LOG2E * p.scale / p.clamp : p.scale * LOG2E;
-  const float c2 = p.clamp * LOG2E;
+  const AttnLogitScale sc = attn_logit_scale(p.scale, p.clamp);
+#ifdef V2A_GEMM_PROBE     // error attribution: hi planes only = the bf16 kernel's products
+  const bool small_terms = !(p.dbg & 32);
+#else
+  constexpr bool small_terms = true;
+#endif
 
   // staging registers (fp32 as loaded; split when written to LDS): K rows (tid>>3)+32i chunk tid&7; V key pair kp = lane&31,
   // d-chunk = 2*wave + (lane>>5).  Two sets, as in the bf16 kernel.
@@ -467,14 +343,6 @@ __global__ __launch_bounds__(256 * NG * QG) void attn_mfma_split_kernel(const At
       *reinterpret_cast<bf16x8*>(base + 2 * K_ELEMS + V_ELEMS + off) = lo;
     }
   };
-  // V^T fragments by ds_read_b64_tr_b16 from the row-major planes (see attn_mfma_kernel)
-  const int vq = lr >> 2, vp = lr & 3;
-  auto vt_read = [&](const bf16_t* vs, int key0, int dt) {
-    const int key = key0 + 4 * g + vq;
-    const int chunk = 2 * dt + (vp >> 1);
-    const bf16_t* ad = vs + key * 64 + ((chunk ^ (key & 7)) << 3) + 4 * (vp & 1);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)ad);
-  };
 
   const int ntiles_all = (kvn + TK - 1) / TK;
   const int nit = (ntiles_all + NG - 1) / NG;
@@ -507,114 +375,28 @@ __global__ __launch_bounds__(256 * NG * QG) void attn_mfma_split_kernel(const At
         const int off = row * 64 + (((kk * 4 + g) ^ (row & 7)) << 3);
         const bf16x8 kh = *reinterpret_cast<const bf16x8*>(ksh + off);
         const bf16x8 kl = *reinterpret_cast<const bf16x8*>(ksl + off);
-#ifdef V2A_GEMM_PROBE     // error attribution: hi planes only = the bf16 kernel's products
-        if (!(p.dbg & 32)) {
+        if (small_terms) {
           s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[kk], s[t], 0, 0, 0);
           s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[kk], s[t], 0, 0, 0);
         }
-#else
-        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[kk], s[t], 0, 0, 0);
-        s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[kk], s[t], 0, 0, 0);
-#endif
         s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[kk], s[t], 0, 0, 0);
       }
     }
-    const int j0 = (jt * NG + grp) * TK;
-    if constexpr (CLAMP == 2) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float e = __builtin_amdgcn_exp2f(s[t][j] * zc);
-          s[t][j] = __builtin_amdgcn_exp2f(fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2));
-        }
-      if (j0 + TK > kvn) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = 0.f;
-      }
-    } else {
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v;
-          if constexpr (CLAMP == 1) {
-            const float e = __builtin_amdgcn_exp2f(s[t][j] * zc);
-            v = fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2);
-          } else {
-            v = s[t][j] * zc;
-          }
-          s[t][j] = v;
-        }
-      if (j0 + TK > kvn) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = -INFINITY;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tmax = fmaxf(tmax, s[t][j]);
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float mn = fmaxf(m, tmax);
-      const float alpha = __builtin_amdgcn_exp2f(m - mn);
-      m = mn;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[dt][j] *= alpha;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[t][j] = __builtin_amdgcn_exp2f(s[t][j] - mn);
-    }
-    // fp32 weights -> row sum, hi | lo operand planes
-    bf16x8 pfh[2], pfl[2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float pv = s[t][j];
-        l += pv;
-        const bf16_t hv = (bf16_t)pv;
-        pfh[t >> 1][(t & 1) * 4 + j] = hv;
-        pfl[t >> 1][(t & 1) * 4 + j] = (bf16_t)(pv - (float)hv);
-      }
+    // ---- fp32 weights -> row sum, hi | lo operand planes
+    attn_weights<CLAMP, true>(s, m, l, o, (jt * NG + grp) * TK, kvn, g, sc);
+    bf16x8 pf[2][2];                 // hi | lo
+    attn_pack_weights(s, l, pf);
     // ---- O^T += V^T P^T in three passes
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
       for (int ks2 = 0; ks2 < 2; ++ks2) {
-        bf16x8 vfh, vfl;
-        {
-          const bf16x4 lo = vt_read(vth, 32 * ks2, dt), hi = vt_read(vth, 32 * ks2 + 16, dt);
-          const bf16x4 lo2 = vt_read(vtl, 32 * ks2, dt), hi2 = vt_read(vtl, 32 * ks2 + 16, dt);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vfh[j] = lo[j];
-            vfh[4 + j] = hi[j];
-            vfl[j] = lo2[j];
-            vfl[4 + j] = hi2[j];
-          }
+        const bf16x8 vfh = attn_vt_frag(vth, ks2, dt, g, lr), vfl = attn_vt_frag(vtl, ks2, dt, g, lr);
+        if (small_terms) {
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfl, pf[0][ks2], o[dt], 0, 0, 0);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfh, pf[1][ks2], o[dt], 0, 0, 0);
         }
-#ifdef V2A_GEMM_PROBE
-        if (!(p.dbg & 32)) {
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfl, pfh[ks2], o[dt], 0, 0, 0);
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfh, pfl[ks2], o[dt], 0, 0, 0);
-        }
-#else
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfl, pfh[ks2], o[dt], 0, 0, 0);
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfh, pfl[ks2], o[dt], 0, 0, 0);
-#endif
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfh, pfh[ks2], o[dt], 0, 0, 0);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfh, pf[0][ks2], o[dt], 0, 0, 0);
       }
     }
     __syncthreads();
@@ -622,55 +404,15 @@ __global__ __launch_bounds__(256 * NG * QG) void attn_mfma_split_kernel(const At
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if constexpr (NG == 2) {
-    float* xch = reinterpret_cast<float*>(lds_dyn + RING);          // 18 floats x 256 lanes = 18 KB, group 1's dead ring
-    __syncthreads();
-    if (grp == 1) {
-      float* dst = xch + tid;
-      dst[0] = m;
-      dst[256] = l;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[(2 + dt * 4 + j) * 256] = o[dt][j];
-    }
-    __syncthreads();
-    if (grp == 1) return;
-    const float* src = xch + tid;
-    const float m2 = src[0], l2 = src[256];
-    const float mn = fmaxf(m, m2);
-    const float a1 = __builtin_amdgcn_exp2f(m - mn), a2 = (m2 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
-    l = l * a1 + l2 * a2;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[dt][j] = o[dt][j] * a1 + src[(2 + dt * 4 + j) * 256] * a2;
+    if (!attn_merge_key_groups(reinterpret_cast<float*>(lds_dyn + RING), grp, tid, m, l, o)) return;
   }
   if (query >= p.Nq) return;
-  const int qn = p.q_len ? min(p.q_len[b], p.Nq) : p.Nq;
-  float gt = 1.f;
-  if (p.gate) gt = sigmoid_f(reinterpret_cast<const float*>(p.gate)[b * p.gbs + (int64_t)query * p.grs + h]);
-  const float f = (query < qn && l > 0.f) ? gt / l : 0.f;
-  if (p.out_split) {
-    // the operand of the out-projection's split GEMM directly: hi | lo planes of the gated fp32 result, no v2a_split_bf16 pass
-    bf16_t* ob = reinterpret_cast<bf16_t*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g;
-    const int lo_off = p.H * 64;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      const f32x4 v = o[dt] * f;
-      bf16x4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (bf16_t)v[e];
-        lo[e] = (bf16_t)(v[e] - (float)hi[e]);
-      }
-      *reinterpret_cast<bf16x4*>(ob + 16 * dt) = hi;
-      *reinterpret_cast<bf16x4*>(ob + lo_off + 16 * dt) = lo;
-    }
+  const float f = attn_out_factor(p.q_len, b, p.Nq, query, l, attn_gate<float>(p, b, query, h));
+  if (p.out_split) {     // the operand of the out-projection's split GEMM directly, no v2a_split_bf16 pass
+    attn_store_split(reinterpret_cast<bf16_t*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g, p.H * 64, o, f);
     return;
   }
-  float* op = reinterpret_cast<float*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt] * f;
+  attn_store(reinterpret_cast<float*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g, o, f);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -709,9 +451,7 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_f32_kernel(AttnParams p) {
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = CLAMP == 2 ? 0.f : -INFINITY, l = 0.f;
-  constexpr float LOG2E = 1.4426950408889634f;
-  const float zc = p.clamp > 0.f ? 2.0f * LOG2E * p.scale / p.clamp : p.scale * LOG2E;
-  const float c2 = p.clamp * LOG2E;
+  const AttnLogitScale sc = attn_logit_scale(p.scale, p.clamp);
 
   struct Raw {
     f32x4 a, b;
@@ -783,63 +523,7 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_f32_kernel(AttnParams p) {
         for (int e = 0; e < 4; ++e) s[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[e], qf[c4][e], s[t], 0, 0, 0);
       }
     }
-    const int j0 = (jt * NG + grp) * TK;
-    if constexpr (CLAMP == 2) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float e = __builtin_amdgcn_exp2f(s[t][j] * zc);
-          s[t][j] = __builtin_amdgcn_exp2f(fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2));
-        }
-      if (j0 + TK > kvn) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = 0.f;
-      }
-    } else {
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v;
-          if constexpr (CLAMP == 1) {
-            const float e = __builtin_amdgcn_exp2f(s[t][j] * zc);
-            v = fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2);
-          } else {
-            v = s[t][j] * zc;
-          }
-          s[t][j] = v;
-        }
-      if (j0 + TK > kvn) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = -INFINITY;
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tmax = fmaxf(tmax, s[t][j]);
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float mn = fmaxf(m, tmax);
-      const float alpha = __builtin_amdgcn_exp2f(m - mn);
-      m = mn;
-      l *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[dt][j] *= alpha;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[t][j] = __builtin_amdgcn_exp2f(s[t][j] - mn);
-    }
+    attn_weights<CLAMP, true>(s, m, l, o, (jt * NG + grp) * TK, kvn, g, sc);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -860,37 +544,17 @@ __global__ __launch_bounds__(256 * NG) void attn_mfma_f32_kernel(AttnParams p) {
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if constexpr (NG == 2) {
-    float* xch = lds_f32 + RING;                                    // 18 floats x 256 lanes = 18 KB, group 1's dead ring
-    __syncthreads();
-    if (grp == 1) {
-      float* dst = xch + tid;
-      dst[0] = m;
-      dst[256] = l;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[(2 + dt * 4 + j) * 256] = o[dt][j];
-    }
-    __syncthreads();
-    if (grp == 1) return;
-    const float* src = xch + tid;
-    const float m2 = src[0], l2 = src[256];
-    const float mn = fmaxf(m, m2);
-    const float a1 = __builtin_amdgcn_exp2f(m - mn), a2 = (m2 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
-    l = l * a1 + l2 * a2;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[dt][j] = o[dt][j] * a1 + src[(2 + dt * 4 + j) * 256] * a2;
+    if (!attn_merge_key_groups(lds_f32 + RING, grp, tid, m, l, o)) return;
   }
   if (query >= p.Nq) return;
-  const int qn = p.q_len ? min(p.q_len[b], p.Nq) : p.Nq;
-  float gt = 1.f;
-  if (p.gate) gt = sigmoid_f(reinterpret_cast<const float*>(p.gate)[b * p.gbs + (int64_t)query * p.grs + h]);
-  const float f = (query < qn && l > 0.f) ? gt / l : 0.f;
-  float* op = reinterpret_cast<float*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt] * f;
+  const float f = attn_out_factor(p.q_len, b, p.Nq, query, l, attn_gate<float>(p, b, query, h));
+  attn_store(reinterpret_cast<float*>(p.out) + b * p.obs + (int64_t)query * p.ors + h * 64 + 4 * g, o, f);
+}
+
+template <int NG, int CLAMP>
+int launch_attn_bf16(const AttnParams& p, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((attn_mfma_kernel<NG, CLAMP>), grid, dim3(256 * NG), 0, s, p);
+  return V2A_OK;
 }
 
 template <int NG, int CLAMP>
@@ -916,15 +580,6 @@ int launch_attn_split(const AttnParams& p, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
-// 0 = no soft clamp, 1 = soft clamp with the running maximum, 2 = soft clamp with BOUNDED weights: logits lie in +-clamp, so
-// p = 2^(logit * log2 e) lies in 2^(+-clamp * log2 e) and no maximum has to be tracked -- as long as the fp32 sums l = sum p
-// and O = sum p v stay finite: Nk * max|v| * 2^(clamp * log2 e) < 2^128.  Mode 2 is taken while clamp * log2 e + log2 Nk <= 90
-// (the shipped clamp 50 with 782 keys: 72.1 + 9.6), which leaves |v| up to 2^38; beyond that the running-maximum kernel runs.
-static int attn_clamp_mode(float softclamp, int Nk) {
-  if (!(softclamp > 0.f)) return 0;
-  return softclamp * 1.4426950408889634f + log2f((float)(Nk > 1 ? Nk : 1)) <= 90.f ? 2 : 1;
-}
-
 extern "C" int v2a_attention(const v2a_attn_args* a, v2a_stream_t stream) {
   V2A_REQUIRE(a != nullptr, "v2a_attention: null args");
   V2A_REQUIRE(a->q && a->k && a->v && a->out, "v2a_attention: null tensor");
@@ -942,77 +597,45 @@ extern "C" int v2a_attention(const v2a_attn_args* a, v2a_stream_t stream) {
   V2A_REQUIRE(!a->out_split || a->dtype == V2A_BF16_SPLIT, "v2a_attention: out_split goes with dtype V2A_BF16_SPLIT");
   hipStream_t s = (hipStream_t)stream;
   int rc = V2A_OK;
-  dim3 grid((a->Nq + 63) / 64, a->H, a->B), block(64);
+  const dim3 grid((a->Nq + 63) / 64, a->H, a->B);      // 64 queries per workgroup (the split launch folds two of them for QG = 2)
+  const int64_t nwg = (int64_t)grid.x * grid.y * grid.z;
+  const int cl = attn_clamp_mode(a->softclamp, a->Nk);
+  // The MFMA kernels need 16-byte aligned head slices for their vector loads and whole vector stores per output piece: fp32
+  // tensors 16-byte aligned throughout; bf16 tensors 16-byte aligned q / k / v, 8-byte aligned output rows.  Else the VALU kernel.
+  const uintptr_t qkv = (uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v;
+  const bool aligned =
+      a->dtype == V2A_BF16
+          ? (qkv & 15) == 0 && ((uintptr_t)a->out & 7) == 0 && a->q_row_stride % 8 == 0 && a->k_row_stride % 8 == 0 && a->v_row_stride % 8 == 0 &&
+                a->q_batch_stride % 8 == 0 && a->k_batch_stride % 8 == 0 && a->v_batch_stride % 8 == 0 && a->out_row_stride % 4 == 0 &&
+                a->out_batch_stride % 4 == 0
+          : ((qkv | (uintptr_t)a->out) & 15) == 0 && a->q_row_stride % 4 == 0 && a->k_row_stride % 4 == 0 && a->v_row_stride % 4 == 0 &&
+                a->out_row_stride % 4 == 0 && a->q_batch_stride % 4 == 0 && a->k_batch_stride % 4 == 0 && a->v_batch_stride % 4 == 0 &&
+                a->out_batch_stride % 4 == 0;
   if (a->dtype == V2A_BF16_SPLIT) {
-    // fp32 tensors, split-bf16 MFMA arithmetic (bf16x3 mode); 16-byte aligned head slices and output rows, else the VALU kernel
-    const bool aligned = (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) & 15) == 0 && a->q_row_stride % 4 == 0 &&
-                         a->k_row_stride % 4 == 0 && a->v_row_stride % 4 == 0 && a->out_row_stride % 4 == 0 && a->q_batch_stride % 4 == 0 &&
-                         a->k_batch_stride % 4 == 0 && a->v_batch_stride % 4 == 0 && a->out_batch_stride % 4 == 0;
-    const dim3 g64((a->Nq + 63) / 64, a->H, a->B);
-    const int cl = attn_clamp_mode(a->softclamp, a->Nk);
+    // fp32 tensors, split-bf16 MFMA arithmetic (bf16x3 mode)
     V2A_REQUIRE(aligned || !a->out_split, "v2a_attention: out_split needs 16-byte aligned head slices");
     if (a->out_split) V2A_REQUIRE(((uintptr_t)a->out & 7) == 0 && a->out_row_stride >= 2 * (int64_t)a->H * 64, "v2a_attention: split output rows hold 2 * H * 64 bf16");
     // two wave groups split the key tiles of a workgroup's 64 queries only while the launch is short of workgroups (< 200, or the
     // v2a_tuning.attn_one_group_from override): one group per workgroup -- 64 KB of LDS, two workgroups per CU, no merge -- measured +1.3 % end to
     // end at 8 clips per GPU (3328 workgroups) and +0.7 % at one clip (416 / 208), profiles/r05_bf16x3_8clips_ab.txt
     const int one_from = v2a_detail::g_attn_one_group_from != 1536 ? v2a_detail::g_attn_one_group_from : 200;
-    const bool two_groups = a->Nk > 128 && (int64_t)g64.x * g64.y * g64.z < one_from;
-    if (!aligned) {
-      hipLaunchKernelGGL((attn_rowlane_kernel<float>), grid, block, 0, s, p);
-    } else if (two_groups) {
-      if (cl == 2) rc = launch_attn_split<2, 2>(p, g64, s);
-      else if (cl == 1) rc = launch_attn_split<2, 1>(p, g64, s);
-      else rc = launch_attn_split<2, 0>(p, g64, s);
-    } else if (a->Nq > 64 && a->Nk > 128 && !(v2a_detail::g_probe_dbg & 256)) {
-      // one key group, two query groups per workgroup (128 queries share every K / V tile); v2a_tuning.reserved[0] bit 8: the 64-query form (A/B)
-      if (cl == 2) rc = launch_attn_split<1, 2, 2>(p, g64, s);
-      else if (cl == 1) rc = launch_attn_split<1, 1, 2>(p, g64, s);
-      else rc = launch_attn_split<1, 0, 2>(p, g64, s);
-    } else {
-      if (cl == 2) rc = launch_attn_split<1, 2>(p, g64, s);
-      else if (cl == 1) rc = launch_attn_split<1, 1>(p, g64, s);
-      else rc = launch_attn_split<1, 0>(p, g64, s);
-    }
+    // else one key group, and two query groups per workgroup (128 queries share every K / V tile) where there are that many
+    // queries and keys to share; v2a_tuning.reserved[0] bit 8: the 64-query form (A/B)
+    const bool two_query_groups = a->Nq > 64 && a->Nk > 128 && !(v2a_detail::g_probe_dbg & 256);
+    if (!aligned) hipLaunchKernelGGL((attn_rowlane_kernel<float>), grid, dim3(64), 0, s, p);
+    else if (a->Nk > 128 && nwg < one_from) rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_split<2, decltype(c)::value>(p, grid, s); });
+    else if (two_query_groups) rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_split<1, decltype(c)::value, 2>(p, grid, s); });
+    else rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_split<1, decltype(c)::value>(p, grid, s); });
   } else if (a->dtype == V2A_F32) {
-    const bool aligned = (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) & 15) == 0 && a->q_row_stride % 4 == 0 &&
-                         a->k_row_stride % 4 == 0 && a->v_row_stride % 4 == 0 && a->out_row_stride % 4 == 0 && a->q_batch_stride % 4 == 0 &&
-                         a->k_batch_stride % 4 == 0 && a->v_batch_stride % 4 == 0 && a->out_batch_stride % 4 == 0;
-    const dim3 g64((a->Nq + 63) / 64, a->H, a->B);
-    const int cl = attn_clamp_mode(a->softclamp, a->Nk);
-    if (!aligned) {
-      hipLaunchKernelGGL((attn_rowlane_kernel<float>), grid, block, 0, s, p);
-    } else if (a->Nk > 128) {
-      if (cl == 2) rc = launch_attn_f32<2, 2>(p, g64, s);
-      else if (cl == 1) rc = launch_attn_f32<2, 1>(p, g64, s);
-      else rc = launch_attn_f32<2, 0>(p, g64, s);
-    } else {
-      if (cl == 2) rc = launch_attn_f32<1, 2>(p, g64, s);
-      else if (cl == 1) rc = launch_attn_f32<1, 1>(p, g64, s);
-      else rc = launch_attn_f32<1, 0>(p, g64, s);
-    }
+    if (!aligned) hipLaunchKernelGGL((attn_rowlane_kernel<float>), grid, dim3(64), 0, s, p);
+    else if (a->Nk > 128) rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_f32<2, decltype(c)::value>(p, grid, s); });
+    else rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_f32<1, decltype(c)::value>(p, grid, s); });
   } else {
-    // MFMA path needs 16-byte aligned head slices for its vector loads and 8-byte aligned output rows
-    const bool aligned = (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v) & 15) == 0 && ((uintptr_t)a->out & 7) == 0 &&
-                         a->q_row_stride % 8 == 0 && a->k_row_stride % 8 == 0 && a->v_row_stride % 8 == 0 &&
-                         a->q_batch_stride % 8 == 0 && a->k_batch_stride % 8 == 0 && a->v_batch_stride % 8 == 0 &&
-                         a->out_row_stride % 4 == 0 && a->out_batch_stride % 4 == 0;
-    const dim3 g64((a->Nq + 63) / 64, a->H, a->B);
-    // soft clamp with bounded weights (no running maximum) while 2^(clamp * log2 e) stays far inside fp32: clamp <= 69
-    const int cl = attn_clamp_mode(a->softclamp, a->Nk);
     // two wave groups split the key tiles of a workgroup's 64 queries (merged at the end) while the launch is short of
     // workgroups; from ~6 workgroups per CU on, one group per workgroup: no merge, 4-wave barriers
-    const bool split_kv = a->Nk > 128 && (int64_t)g64.x * g64.y * g64.z < v2a_detail::g_attn_one_group_from;
-    if (aligned && split_kv) {
-      if (cl == 2) hipLaunchKernelGGL((attn_mfma_kernel<2, 2>), g64, dim3(512), 0, s, p);
-      else if (cl == 1) hipLaunchKernelGGL((attn_mfma_kernel<2, 1>), g64, dim3(512), 0, s, p);
-      else hipLaunchKernelGGL((attn_mfma_kernel<2, 0>), g64, dim3(512), 0, s, p);
-    } else if (aligned) {
-      if (cl == 2) hipLaunchKernelGGL((attn_mfma_kernel<1, 2>), g64, dim3(256), 0, s, p);
-      else if (cl == 1) hipLaunchKernelGGL((attn_mfma_kernel<1, 1>), g64, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((attn_mfma_kernel<1, 0>), g64, dim3(256), 0, s, p);
-    }
-    else
-      hipLaunchKernelGGL((attn_rowlane_kernel<bf16_t>), grid, block, 0, s, p);
+    if (!aligned) hipLaunchKernelGGL((attn_rowlane_kernel<bf16_t>), grid, dim3(64), 0, s, p);
+    else if (a->Nk > 128 && nwg < v2a_detail::g_attn_one_group_from) rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_bf16<2, decltype(c)::value>(p, grid, s); });
+    else rc = attn_with_clamp(cl, [&](auto c) { return launch_attn_bf16<1, decltype(c)::value>(p, grid, s); });
   }
   if (rc != V2A_OK) return rc;
   return v2a_check_launch("v2a_attention");

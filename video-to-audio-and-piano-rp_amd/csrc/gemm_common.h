@@ -363,6 +363,17 @@ __device__ __forceinline__ float rowscale_finish(const GemmParams& p, const RowS
   return p.rnorm / fmaxf(sqrtf(s), 1e-12f);
 }
 
+// Interleaved RoPE of four columns (two pairs) by cs = (cos, sin, cos, sin) of the pairs.  One fixed contraction: left to
+// -ffp-contract the kernels' instantiations picked different multiply-add pairings and the rotated columns differed in the
+// last bit between tile shapes.
+__device__ __forceinline__ void rope_rotate4(f32x4& v, const f32x4& cs) {
+  const float a0 = v[0], b0 = v[1], a1 = v[2], b1 = v[3];
+  v[0] = fmaf(a0, cs[0], -(b0 * cs[1]));
+  v[1] = fmaf(b0, cs[0], a0 * cs[1]);
+  v[2] = fmaf(a1, cs[2], -(b1 * cs[3]));
+  v[3] = fmaf(b1, cs[2], a1 * cs[3]);
+}
+
 template <int EPI, typename OutT, int TM, int TN, int WM, int WN, bool PF>
 __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&acc)[TM][TN], float* tile /* wave-private, 16 x (WN+4) floats */,
                                                   int m_base, int n_base, int lane, const EpiPrefetch<EPI, TM, WN, PF>& pf,
@@ -550,13 +561,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
             f32x4 cs;
             if constexpr (PF) cs = pf.cs[i][q];
             else cs = *reinterpret_cast<const f32x4*>(p.rope + ((int64_t)(p.rope_pos_off + m % p.rpb) * 32 + ((n & 63) >> 1)) * 2);
-            const float a0 = v[0], b0 = v[1], a1 = v[2], b1 = v[3];
-            // one fixed contraction: left to -ffp-contract the two kernels' instantiations picked different multiply-add
-            // pairings and the rotated columns differed in the last bit between tile shapes
-            v[0] = fmaf(a0, cs[0], -(b0 * cs[1]));
-            v[1] = fmaf(b0, cs[0], a0 * cs[1]);
-            v[2] = fmaf(a1, cs[2], -(b1 * cs[3]));
-            v[3] = fmaf(b1, cs[2], a1 * cs[3]);
+            rope_rotate4(v, cs);
           }
         }
         if constexpr (EPI == V2A_EPI_RESID || EPI == V2A_EPI_GATE_RESID) {

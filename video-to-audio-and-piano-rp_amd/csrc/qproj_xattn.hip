@@ -9,13 +9,17 @@
 //              extra MFMA per 32-k step for the head's gate logit: the gate row of W (row H*64 + h) is preloaded into LDS
 //              (2 KB, by LDS-DMA ahead of the ring) and read as a B fragment whose 16 columns all hold that row -- the
 //              accumulator then carries the logit of each of the wave's 16 tokens with the arithmetic of the plain GEMM.
-//   epilogue   acc -> wave-private fp32 slab -> row pieces: x row scale, + bias, RoPE, bf16 (the expressions of
-//              gemm_epilogue_lds, so q equals the unfused launch's bit for bit) -> wave-private swizzled q tile in LDS;
-//              K / V rows of the head (requested when the kernel starts) -> shared swizzled tiles; then the single-tile body of
-//              attn_mfma_kernel (swapped product: the query sits on the lane) and 8-byte stores of O * sigmoid(gate) / l.
+//   epilogue   acc -> wave-private fp32 slab -> row pieces: x row scale, + bias, RoPE (rope_rotate4 of gemm_common.h, as
+//              gemm_epilogue_lds applies it), bf16, so q equals the unfused launch's bit for bit -> wave-private swizzled q tile in
+//              LDS; K / V rows of the head (requested when the kernel starts) -> shared swizzled tiles; then one key tile of
+//              attn_mfma_kernel (swapped product: the query sits on the lane) through the functions of attn_core.h that the kernels
+//              of attention.hip call -- attn_weights, attn_pack_weights, attn_vt_frag, attn_out_factor, attn_store -- and 8-byte
+//              stores of O * sigmoid(gate) / l.
 // Results equal the two-launch path bit for bit (tests/test_kernels_gpu.py::test_qproj_xattn_equals_two_launches).
-// S3 = the bf16x3 mode's arithmetic: hi | lo bf16 planes of A, W, q, K, V and P, three MFMAs per product (the split ring of gemm.hip,
-// the body of attn_mfma_split_kernel), fp32 K / V rows and gate logit, output rows as hi | lo planes for the out-projection's split GEMM.
+// S3 = the bf16x3 mode's arithmetic: hi | lo bf16 planes of A, W, q, K, V and P, three MFMAs per product (the split ring of gemm.hip;
+// split8, the three-product order and attn_store_split of attn_mfma_split_kernel), fp32 K / V rows and gate logit, output rows as
+// hi | lo planes for the out-projection's split GEMM.
+#include "attn_core.h"
 #include "gemm_common.h"
 
 namespace {
@@ -39,17 +43,6 @@ __device__ __forceinline__ void qx_ring_wait(int younger) {
   } else {
     if (younger >= J) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(J * LPW) : "memory");
     else qx_ring_wait<J - 1, LPW>(younger);
-  }
-}
-
-__device__ __forceinline__ void qx_split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const bf16_t ha = (bf16_t)a[e], hb = (bf16_t)b[e];
-    hi[e] = ha;
-    hi[4 + e] = hb;
-    lo[e] = (bf16_t)(a[e] - (float)ha);
-    lo[4 + e] = (bf16_t)(b[e] - (float)hb);
   }
 }
 
@@ -249,10 +242,10 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
     const int off = row * 64 + ((kchunk ^ (row & 7)) << 3);
     if constexpr (S3) {
       bf16x8 hi, lo;
-      qx_split8(kraw[i].a, kraw[i].b, hi, lo);
+      split8(kraw[i].a, kraw[i].b, hi, lo);
       *reinterpret_cast<bf16x8*>(ks + off) = hi;
       *reinterpret_cast<bf16x8*>(ks + 64 * 64 + off) = lo;
-      qx_split8(vraw[i].a, vraw[i].b, hi, lo);
+      split8(vraw[i].a, vraw[i].b, hi, lo);
       *reinterpret_cast<bf16x8*>(vt + off) = hi;
       *reinterpret_cast<bf16x8*>(vt + 64 * 64 + off) = lo;
     } else {
@@ -289,14 +282,7 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
       if (scaled) v *= rs_lds[row];
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] += bv[e];
-      if (rope) {
-        const f32x4 cs = *reinterpret_cast<const f32x4*>(p.rope + ((int64_t)(p.rope_pos_off + m % rpb) * 32 + ((n & 63) >> 1)) * 2);
-        const float a0 = v[0], b0 = v[1], a1 = v[2], b1 = v[3];
-        v[0] = fmaf(a0, cs[0], -(b0 * cs[1]));
-        v[1] = fmaf(b0, cs[0], a0 * cs[1]);
-        v[2] = fmaf(a1, cs[2], -(b1 * cs[3]));
-        v[3] = fmaf(b1, cs[2], a1 * cs[3]);
-      }
+      if (rope) rope_rotate4(v, *reinterpret_cast<const f32x4*>(p.rope + ((int64_t)(p.rope_pos_off + m % rpb) * 32 + ((n & 63) >> 1)) * 2));
       bf16x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
@@ -324,13 +310,11 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
     if constexpr (S3) ql[kk] = *reinterpret_cast<const bf16x8*>(qt + 64 * 64 + off);
   }
   const int kvn = P.kv_len ? min(P.kv_len[b], P.Nk) : P.Nk;
-  constexpr float LOG2E = 1.4426950408889634f;
-  const float zc = P.clamp > 0.f ? 2.0f * LOG2E * P.scale / P.clamp : P.scale * LOG2E;
-  const float c2 = P.clamp * LOG2E;
+  const AttnLogitScale sc = attn_logit_scale(P.scale, P.clamp);
   f32x4 o[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float l = 0.f;
+  float l = 0.f, m = 0.f;                          // one key tile: no running maximum, attn_weights<.., false> leaves m, l and o alone
   if (kvn > 0) {
     f32x4 s[4];
 #pragma unroll
@@ -349,98 +333,22 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
         s[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], s[tt], 0, 0, 0);
       }
     }
-    // soft clamp, key mask, softmax weights (fp32) in s
-    if constexpr (CLAMP == 2) {
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float e = __builtin_amdgcn_exp2f(s[tt][j] * zc);
-          s[tt][j] = __builtin_amdgcn_exp2f(fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2));
-        }
-      if (64 > kvn) {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (16 * tt + 4 * g + j >= kvn) s[tt][j] = 0.f;
-      }
-    } else {
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v;
-          if constexpr (CLAMP == 1) {
-            const float e = __builtin_amdgcn_exp2f(s[tt][j] * zc);
-            v = fmaf(__builtin_amdgcn_rcpf(e + 1.0f), -2.0f * c2, c2);
-          } else {
-            v = s[tt][j] * zc;
-          }
-          s[tt][j] = v;
-        }
-      if (64 > kvn) {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (16 * tt + 4 * g + j >= kvn) s[tt][j] = -INFINITY;
-      }
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tmax = fmaxf(tmax, s[tt][j]);
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[tt][j] = __builtin_amdgcn_exp2f(s[tt][j] - tmax);
-    }
-    // row sum and the P^T operand (S3: hi | lo planes of the fp32 weights)
-    bf16x8 pf[2], pl[S3 ? 2 : 1];
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float pv = s[tt][j];
-        l += pv;
-        const bf16_t hv = (bf16_t)pv;
-        pf[tt >> 1][(tt & 1) * 4 + j] = hv;
-        if constexpr (S3) pl[tt >> 1][(tt & 1) * 4 + j] = (bf16_t)(pv - (float)hv);
-      }
-    // O^T += V^T P^T, V^T fragments by the transposing LDS read (see attn_mfma_kernel)
-    const int vq = lr >> 2, vp = lr & 3;
-    auto vt_read = [&](const bf16_t* vs, int key0, int dt) {
-      const int key = key0 + 4 * g + vq;
-      const int chunk = 2 * dt + (vp >> 1);
-      const bf16_t* ad = vs + key * 64 + ((chunk ^ (key & 7)) << 3) + 4 * (vp & 1);
-      return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)ad);
-    };
+    // soft clamp, key mask, softmax weights (fp32) in s; row sum and the P^T operand (S3: hi | lo planes of the fp32 weights)
+    attn_weights<CLAMP, false>(s, m, l, o, 0, kvn, g, sc);
+    bf16x8 pf[NPL][2];
+    attn_pack_weights(s, l, pf);
+    // O^T += V^T P^T
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
 #pragma unroll
       for (int ks2 = 0; ks2 < 2; ++ks2) {
-        const bf16x4 lo = vt_read(vt, 32 * ks2, dt), hi = vt_read(vt, 32 * ks2 + 16, dt);
-        bf16x8 vf;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          vf[j] = lo[j];
-          vf[4 + j] = hi[j];
-        }
+        const bf16x8 vf = attn_vt_frag(vt, ks2, dt, g, lr);
         if constexpr (S3) {
-          const bf16x4 lo2 = vt_read(vt + 64 * 64, 32 * ks2, dt), hi2 = vt_read(vt + 64 * 64, 32 * ks2 + 16, dt);
-          bf16x8 vfl;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            vfl[j] = lo2[j];
-            vfl[4 + j] = hi2[j];
-          }
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfl, pf[ks2], o[dt], 0, 0, 0);
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pl[ks2], o[dt], 0, 0, 0);
+          const bf16x8 vfl = attn_vt_frag(vt + 64 * 64, ks2, dt, g, lr);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfl, pf[0][ks2], o[dt], 0, 0, 0);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[1][ks2], o[dt], 0, 0, 0);
         }
-        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ks2], o[dt], 0, 0, 0);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[0][ks2], o[dt], 0, 0, 0);
       }
     }
   }
@@ -452,28 +360,10 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
   if (scaled) gv *= rs_lds[qrow];
   if (p.bias) gv += p.bias[P.H * 64 + h];
   const float gt = S3 ? sigmoid_f(gv) : sigmoid_f((float)(bf16_t)gv);
-  const int qn = P.q_len ? min(P.q_len[b], rpb) : rpb;
-  const float f = (qi < qn && l > 0.f) ? gt / l : 0.f;
+  const float f = attn_out_factor(P.q_len, b, rpb, qi, l, gt);
   bf16_t* op = P.out + b * P.obs + (int64_t)qi * P.ors + h * 64 + 4 * g;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    if constexpr (S3) {
-      const f32x4 v = o[dt] * f;
-      bf16x4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (bf16_t)v[e];
-        lo[e] = (bf16_t)(v[e] - (float)hi[e]);
-      }
-      *reinterpret_cast<bf16x4*>(op + 16 * dt) = hi;
-      *reinterpret_cast<bf16x4*>(op + P.H * 64 + 16 * dt) = lo;
-    } else {
-      bf16x4 ov;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ov[j] = (bf16_t)(o[dt][j] * f);
-      *reinterpret_cast<bf16x4*>(op + 16 * dt) = ov;
-    }
-  }
+  if constexpr (S3) attn_store_split(op, P.H * 64, o, f);
+  else attn_store(op, o, f);
 }
 
 template <int CLAMP, bool S3>
@@ -556,15 +446,8 @@ extern "C" int v2a_qproj_xattn(const v2a_gemm_args* a, const v2a_attn_args* at, 
   P.nseq = at->B;
   P.tiles_per_seq = (at->Nq + 63) / 64;
   hipStream_t s = (hipStream_t)stream;
-  // the clamp mode v2a_attention would pick for these keys (attention.hip: bounded weights while clamp * log2 e + log2 Nk <= 90)
-  int cl = 0;
-  if (at->softclamp > 0.f) cl = at->softclamp * 1.4426950408889634f + log2f((float)(at->Nk > 1 ? at->Nk : 1)) <= 90.f ? 2 : 1;
-  if (s3) {
-    if (cl == 2) return launch_qx<2, true>(P, s);
-    if (cl == 1) return launch_qx<1, true>(P, s);
-    return launch_qx<0, true>(P, s);
-  }
-  if (cl == 2) return launch_qx<2, false>(P, s);
-  if (cl == 1) return launch_qx<1, false>(P, s);
-  return launch_qx<0, false>(P, s);
+  // the clamp mode v2a_attention would pick for these keys
+  return attn_with_clamp(attn_clamp_mode(at->softclamp, at->Nk), [&](auto c) {
+    return s3 ? launch_qx<decltype(c)::value, true>(P, s) : launch_qx<decltype(c)::value, false>(P, s);
+  });
 }
