@@ -73,11 +73,17 @@ enum {
   V2A_EPI_GATE_RESID = 4, /* out = resid + gate[n] * (acc + bias) (AdaLNZero x3:546-551 + residual x3:1128) */
   V2A_EPI_GEGLU_TANH = 5, /* v2a_gemm_skinny_f32 only (v2a_gemm rejects it): the GEGLU row packing with value = wi_1, gate = wi_0,
                              out[m][j] = (acc_v + b_v) * gelu_new(acc_g + b_g), gelu_new(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) */
-  V2A_EPI_GELU = 6        /* ABI 8, additive: out = gelu_erf(acc + bias), gelu_erf(x) = 0.5 x (1 + erf(x / sqrt(2))) -- CLIPMLP.fc1 + activation_fn
+  V2A_EPI_GELU = 6,       /* ABI 8, additive: out = gelu_erf(acc + bias), gelu_erf(x) = 0.5 x (1 + erf(x / sqrt(2))) -- CLIPMLP.fc1 + activation_fn
                              of the CLIP image encoder (transformers CLIPEncoderLayer, reached from x3:1714, 1733-1735).  fp32 compute (exact erff,
                              fp32 output) or split operands (the bf16x3 mode; output fp32 with exact erff, or out_dtype V2A_BF16_SPLIT: row m =
                              [hi of the N outputs | lo of them], ldo >= 2N, erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7, the fc2 operand
                              written directly).  Plain bf16 compute refuses it. */
+  V2A_EPI_SWIGLU = 7      /* ABI 8, additive: the GEGLU row packing [16 value | 16 gate] per 16 outputs with silu on the gate,
+                             out[m][j] = (acc_v + b_v) * silu(acc_g + b_g), silu(x) = x / (1 + exp(-x)); out has N/2 cols -- Dinov2SwiGLUFFN of the
+                             DINOv2 image encoder (`video_encoder="dinov2"`, x3:1432-1433, 1714, 1742-1744): gate = rows [0, Hf) of weights_in (x1),
+                             value = rows [Hf, 2Hf) (x2).  fp32 compute (exact expf and division, fp32 output) or split operands (the bf16x3 mode;
+                             output fp32 with exact expf, or out_dtype V2A_BF16_SPLIT: row m = [hi of the N/2 outputs | lo of them], ldo >= N, silu
+                             on v_exp_f32, the weights_out operand written directly).  Plain bf16 compute refuses it. */
 };
 
 typedef struct v2a_gemm_args {

@@ -14,9 +14,10 @@ from .video2roll import Video2RollEngine  # noqa: F401
 from .encodec import EncodecDecoder, EncodecEncoder  # noqa: F401
 from .t5 import T5Encoder  # noqa: F401
 from .clip import CLIPImageEncoder  # noqa: F401
+from .dinov2 import DINOv2ImageEncoder  # noqa: F401
 from .piano_frames import PianoFramePlan, PianoFramePreprocessor  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
            "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "expected_state_dict_shapes", "NOTES",
-           "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "T5Encoder", "CLIPImageEncoder", "PianoFramePlan", "PianoFramePreprocessor"]
+           "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor"]

@@ -22,6 +22,7 @@ F32, BF16, BF16_SPLIT = 0, 1, 2
 EPI_STORE, EPI_SIGMOID, EPI_GEGLU, EPI_RESID, EPI_GATE_RESID = 0, 1, 2, 3, 4
 EPI_GEGLU_TANH = 5           # v2a_gemm_skinny_f32 only
 EPI_GELU = 6                 # fp32 compute or split operands (CLIP's MLP)
+EPI_SWIGLU = 7               # fp32 compute or split operands (DINOv2's feed-forward): the GEGLU packing, silu on the gate
 
 _lib = None
 
@@ -327,7 +328,7 @@ def _launch(key, flops, nbytes, call):
         _prof.launch(key, flops, nbytes, lambda: check(call()))
 
 
-_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh", 6: "gelu"}
+_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh", 6: "gelu", 7: "swiglu"}
 
 
 # ------------------------------------------------------------------------------------------
@@ -396,7 +397,7 @@ def gemm_args(a_segs, w, out, *, M, N, compute, epilogue=EPI_STORE, bias=None, r
     key = "gemm<%s,%s,%s,%s>" % ("bf16" if compute == BF16 else "f32", "a_f32" if g.a_dtype == F32 else ("a_split" if a_split else "a_bf16"),
                                  _EPI_NAMES[epilogue], "f32" if g.out_dtype == F32 else "bf16")
     esz = 2 if compute == BF16 else 4
-    nbytes = M * K * (4 if g.a_dtype == F32 else 2) + N * K * esz + M * (N // 2 if epilogue == EPI_GEGLU else N) * out.element_size()
+    nbytes = M * K * (4 if g.a_dtype == F32 else 2) + N * K * esz + M * (N // 2 if epilogue in (EPI_GEGLU, EPI_SWIGLU) else N) * out.element_size()
     nbytes += (M * N * 4 if resid is not None else 0) + (M * N * 2 if out_bf16 is not None else 0)      # residual rows read, bf16 shadow written
     if g.tile_hint:
         key = key[:-1] + ",tile%d>" % (g.tile_hint - 1)        # side-stream launches: tile shape chosen for running beside others

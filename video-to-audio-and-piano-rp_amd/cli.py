@@ -12,6 +12,8 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
 `vocos.decode` (src/inference_v2a.py / predict.py:277-278).
 
   --clip DIR         encode the videos that have no CLIP feature cache (moviepy decode, HIP CLIP encoder of this rank's GPU)
+  --video-encoder {clip_vit,dinov2}   which frame encoder the checkpoint was trained on: selects the class --clip DIR loads (the HIP
+                     CLIP ViT-bigG or DINOv2 encoder) and the cache name (`<video>.generated.npz` / `<video>.generated.dinov2.npz`)
   --t5-engine hip    run --t5 on the HIP FLAN-T5 encoder (t5.py) of this rank's GPU instead of transformers on the CPU
   --piano            V2P (src/inference_v2p.py): the grey frames `<video>.generated_frames_raw.2.npz` (features.py; made on the GPU
                      by piano_frames.py from a moviepy decode when the cache is missing) go
@@ -75,13 +77,14 @@ def read_audio_prompt(video_path: str, seconds: float) -> torch.Tensor:
     return wav[:nw].float().contiguous()
 
 
-def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None):
-    """clip_encode: optional `video_path -> (image_embeds, duration)` that makes a missing `<video>.generated.npz` (--clip)."""
+def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None, video_encoder: str = "clip_vit"):
+    """clip_encode: optional `video_path -> (image_embeds, duration)` that makes a missing `<video>.generated.npz` (--clip);
+    video_encoder: which cache name is read and written (--video-encoder)."""
     from .collate import ClipRequest
     from .features import feature_cache_path, load_clip_cache, resample_clip_features, save_clip_cache
     reqs = []
     for vp, cap in items:
-        fp = feature_cache_path(vp)
+        fp = feature_cache_path(vp, video_encoder)
         if not os.path.exists(fp):
             if clip_encode is None:
                 raise FileNotFoundError(f"{fp}: no cached CLIP features for {vp}; pass --clip DIR (with moviepy installed) to encode it")
@@ -141,6 +144,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="what runs --t5: stock transformers on the CPU (torch) or the HIP T5Encoder on this rank's GPU (hip)")
     ap.add_argument("--clip", default=None, help="local CLIP image encoder directory (IP-Adapter sdxl_models/image_encoder): videos "
                     "without <video>.generated.npz are decoded with moviepy and encoded on this rank's GPU, and the cache is written")
+    ap.add_argument("--video-encoder", default="clip_vit", choices=["clip_vit", "dinov2"],
+                    help="the frame encoder of the checkpoint: which class --clip DIR loads (CLIP ViT-bigG or DINOv2) and which feature cache is used")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the piano frames through the Video2Roll encoder; a video without "
@@ -174,7 +179,7 @@ def main(argv=None):
     model = E2TTS(transformer=dict(if_text_modules=True, if_cross_attn=True, if_audio_conv=True, if_text_conv=True, **tk),
                   num_channels=channels, sampling_rate=24000, if_cond_proj_in=a.audio_prompt_seconds > 0, tokenizer="phoneme_zh",
                   compute_dtype=a.dtype, device=torch.device("cuda", local), bucket_frames=a.bucket_frames, bucket_ctx=a.bucket_ctx,
-                  frames_compute_dtype=a.frames_dtype)
+                  frames_compute_dtype=a.frames_dtype, video_encoder=a.video_encoder)
     ck = torch.load(a.ckpt, map_location="cpu")
     res = model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # predict.py:161-168
     if res.missing_keys:
@@ -201,8 +206,11 @@ def main(argv=None):
 
     clip_encode = None
     if a.clip:
-        from .clip import CLIPImageEncoder
-        cenc = CLIPImageEncoder.from_pretrained(a.clip, torch.device("cuda", local))
+        if a.video_encoder == "dinov2":
+            from .dinov2 import DINOv2ImageEncoder as ImageEncoder
+        else:
+            from .clip import CLIPImageEncoder as ImageEncoder
+        cenc = ImageEncoder.from_pretrained(a.clip, torch.device("cuda", local))
         def clip_encode(vp):
             try:
                 frames, duration = decode(vp)
@@ -224,7 +232,7 @@ def main(argv=None):
         s, e, per = shard_range(len(chunk), rank, world)
         mine = chunk[s:e]
         if mine:
-            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode), channels, gen)
+            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder), channels, gen)
             frames = None
             if a.piano:
                 # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
@@ -251,7 +259,7 @@ def main(argv=None):
                 if vocoder is not None:
                     from scipy.io import wavfile
                     from .features import load_clip_cache, feature_cache_path
-                    n = min(a.frames, int(load_clip_cache(feature_cache_path(vp))[1] * 24000) // 320) if a.frames > 0 else one.shape[0]
+                    n = min(a.frames, int(load_clip_cache(feature_cache_path(vp, a.video_encoder))[1] * 24000) // 320) if a.frames > 0 else one.shape[0]
                     wav = vocoder.decode(one[:n].t()[None].float())[0]                     # predict.py:277-278
                     wavfile.write(os.path.join(a.out_dir, name + ".wav"), 24000, wav.cpu().numpy())
     if world > 1:

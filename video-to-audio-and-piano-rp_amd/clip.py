@@ -79,11 +79,15 @@ def resize_output_size(h: int, w: int, size: int) -> tuple[int, int]:
 
 class ResizePlan:
     """Host tables of one input size: the crop columns of the horizontal pass, the input rows it covers and the crop rows of the
-    vertical pass (bounds relative to the first covered row)."""
+    vertical pass (bounds relative to the first covered row).  `resize`: the shortest-edge target when it differs from the crop S
+    (DINOv2's processor resizes to 256 and crops 224; CLIP's resizes to the crop size, the default)."""
 
-    def __init__(self, H: int, W: int, S: int):
+    def __init__(self, H: int, W: int, S: int, resize: int | None = None):
         self.H, self.W, self.S = H, W, S
-        oh, ow = resize_output_size(H, W, S)
+        self.resize = S if resize is None else int(resize)
+        if self.resize < S:
+            raise ValueError(f"ResizePlan: resize {self.resize} below the crop {S} (the processor would pad)")
+        oh, ow = resize_output_size(H, W, self.resize)
         self.out_hw = (oh, ow)
         self.top, self.left = (oh - S) // 2, (ow - S) // 2
         hb, hk = resample_coeffs(W, ow)

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
   constexpr int LR = TileCfg<T>::LDS_ROW;
   constexpr int WM = BM / 2, WN = BN / 2;   // wave tile
   constexpr int TM = WM / 16, TN = WN / 16; // MFMA tiles per wave
-  static_assert(EPI != V2A_EPI_GEGLU || (TN % 2 == 0), "GEGLU needs value/gate tile pairs");
+  static_assert(!is_glu(EPI) || (TN % 2 == 0), "GEGLU / SWIGLU need value/gate tile pairs");
 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* smem = reinterpret_cast<T*>(smem_raw);
@@ -158,6 +158,11 @@ int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
         if constexpr (sizeof(T) == 2) return launch<T, A_F32, V2A_EPI_GEGLU, bf16_t, BM, BN>(p, s);
       }
       break;
+    case V2A_EPI_SWIGLU:   // exact-fp32 compute only (gemm_prepare refuses plain bf16 compute)
+      if constexpr (sizeof(T) == 4) {
+        if (out_f32) return launch<T, A_F32, V2A_EPI_SWIGLU, float, BM, BN>(p, s);
+      }
+      break;
     case V2A_EPI_RESID:
       if (out_f32) return launch<T, A_F32, V2A_EPI_RESID, float, BM, BN>(p, s);
       break;
@@ -217,7 +222,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_dma_kernel(const Gem
   static_assert((GA + GW) % NW == 0, "DMA groups must divide evenly over the waves");
   // chunk swizzle of a row inside its DMA group (applied to the DMA source address and to the fragment reads)
   auto swz = [](int row) { return BK == 64 ? (row & 7) : (((row >> 3) & 1) * 3); };
-  static_assert(EPI != V2A_EPI_GEGLU || (TN % 2 == 0), "GEGLU needs value/gate tile pairs");
+  static_assert(!is_glu(EPI) || (TN % 2 == 0), "GEGLU / SWIGLU need value/gate tile pairs");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 
   const int tid = threadIdx.x;
@@ -518,6 +523,12 @@ int dispatch_s3(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
         if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GEGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
       }
       break;
+    case V2A_EPI_SWIGLU:
+      if constexpr ((BN / WGN / 16) % 2 == 0) {
+        if (out_f32) return launch_dma<V2A_EPI_SWIGLU, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+        if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_SWIGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      }
+      break;
     case V2A_EPI_GELU:
       if (out_f32) return launch_dma<V2A_EPI_GELU, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
       if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GELU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
@@ -614,7 +625,8 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   p.ldo = a->ldo;
   p.out2 = reinterpret_cast<bf16_t*>(a->out_bf16);
   p.ldo2 = a->ld_out_bf16;
-  if (a->out_bf16) V2A_REQUIRE(a->out_dtype == V2A_F32 && a->epilogue != V2A_EPI_GEGLU, "v2a_gemm: out_bf16 shadows an fp32 output only");
+  const bool glu = is_glu(a->epilogue);
+  if (a->out_bf16) V2A_REQUIRE(a->out_dtype == V2A_F32 && !glu, "v2a_gemm: out_bf16 shadows an fp32 output only");
   p.out2_split = a->out_bf16 && a->out_bf16_split ? 1 : 0;
   p.out2_lo = a->out_bf16_lo_offset > 0 ? a->out_bf16_lo_offset : a->N;
   if (p.out2_split && a->out_row_offset)      // scattered rows (a bordered map): the lo plane is a whole map further, not a row part
@@ -640,13 +652,21 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   }
   p.out_split = a->out_dtype == V2A_BF16_SPLIT ? 1 : 0;
   if (p.out_split)
-    V2A_REQUIRE((a->epilogue == V2A_EPI_GEGLU && a->ldo >= a->N) || (a->epilogue == V2A_EPI_GELU && split_in && a->ldo >= 2 * (int64_t)a->N),
-                "v2a_gemm: out_dtype V2A_BF16_SPLIT goes with the GEGLU epilogue and ldo >= N, or GELU on split operands and ldo >= 2N");
+    V2A_REQUIRE((a->epilogue == V2A_EPI_GEGLU && a->ldo >= a->N) || (a->epilogue == V2A_EPI_SWIGLU && split_in && a->ldo >= a->N) ||
+                    (a->epilogue == V2A_EPI_GELU && split_in && a->ldo >= 2 * (int64_t)a->N),
+                "v2a_gemm: out_dtype V2A_BF16_SPLIT goes with the GEGLU epilogue and ldo >= N, SWIGLU on split operands and ldo >= N, or GELU on split "
+                "operands and ldo >= 2N");
   // GELU (CLIP's MLP): the exact-fp32 kernel and the split-operand kernels carry it; plain bf16 compute has no GELU instantiation
   if (a->epilogue == V2A_EPI_GELU)
     V2A_REQUIRE((a->compute_dtype == V2A_F32 || split_in) && !a->out_bf16 && !a->relu && !a->rope_table && !a->a_row_offset && !a->out_row_offset &&
                     !a->norm_gamma && !a->norm_ssq && !a->row_ssq,
                 "v2a_gemm: the GELU epilogue needs fp32 compute or split operands, dense rows, and none of out_bf16 / relu / rope / norm folding");
+  // SWIGLU (DINOv2's feed-forward): as GELU, built for the exact-fp32 kernel and the split-operand kernels only
+  if (a->epilogue == V2A_EPI_SWIGLU)
+    V2A_REQUIRE((a->compute_dtype == V2A_F32 || split_in) && !a->relu && !a->rope_table && !a->a_row_offset && !a->out_row_offset && !a->norm_gamma &&
+                    !a->norm_ssq && !a->row_ssq && a->ldo >= a->N / 2,
+                "v2a_gemm: the SWIGLU epilogue needs fp32 compute or split operands (plain bf16 compute has no SWIGLU instantiation), dense rows, "
+                "ldo >= N / 2 and none of relu / rope / norm folding");
   p.resid = a->resid;
   p.ldr = a->ldr;
   p.gate = a->gate;
@@ -657,7 +677,7 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   {
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     const int osz = a->out_dtype == V2A_F32 ? 4 : 2;      // V2A_BF16 and V2A_BF16_SPLIT: bf16 elements
-    const int ncols = a->epilogue == V2A_EPI_GEGLU ? a->N / 2 : a->N;
+    const int ncols = glu ? a->N / 2 : a->N;
     bool ok = a->N % 4 == 0 && ncols % 4 == 0 && ((uintptr_t)a->out % (4 * osz)) == 0 && (a->ldo * osz) % (4 * osz) == 0;
     if (a->bias) ok = ok && al16(a->bias);
     if (a->resid) ok = ok && al16(a->resid) && a->ldr % 4 == 0;
@@ -697,7 +717,7 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
                     (a->epilogue == V2A_EPI_STORE || a->epilogue == V2A_EPI_RESID) && !a->rope_table,
                 "v2a_gemm: row/K-tile offset tables need one bf16 (or split bf16) segment, bf16 compute, STORE/RESID and 16-byte aligned rows");
   }
-  V2A_REQUIRE(!a->relu || a->epilogue != V2A_EPI_GEGLU, "v2a_gemm: relu with GEGLU");
+  V2A_REQUIRE(!a->relu || !glu, "v2a_gemm: relu with GEGLU / SWIGLU");
   p.ngam = a->norm_gamma;
   p.ngss = a->norm_step_stride;
   p.ngbs = a->norm_batch_stride;
@@ -735,7 +755,7 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   if (a->epilogue == V2A_EPI_RESID || a->epilogue == V2A_EPI_GATE_RESID)
     V2A_REQUIRE(a->resid != nullptr, "v2a_gemm: epilogue %d needs resid", a->epilogue);
   if (a->epilogue == V2A_EPI_GATE_RESID) V2A_REQUIRE(a->gate != nullptr, "v2a_gemm: GATE_RESID needs gate");
-  if (a->epilogue == V2A_EPI_GEGLU) V2A_REQUIRE(a->N % 32 == 0, "v2a_gemm: GEGLU needs N %% 32 == 0 (N=%d)", a->N);
+  if (glu) V2A_REQUIRE(a->N % 32 == 0, "v2a_gemm: GEGLU / SWIGLU need N %% 32 == 0 (N=%d)", a->N);
   return V2A_OK;
 }
 
@@ -792,7 +812,7 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
       cfg = a->N <= 64 ? 2 : (nt(128, 128) >= 256 ? 3 : 4);
     } else if (cfg == 0) {
       // (stand-alone, scripts/split_probe.py, profiles/r05_split_probe.txt)
-      if (a->epilogue == V2A_EPI_GEGLU || a->N >= 2048) cfg = nt(128, 128) >= 200 ? 3 : 4;
+      if (is_glu(a->epilogue) || a->N >= 2048) cfg = nt(128, 128) >= 200 ? 3 : 4;
       // N <= 512 with many rows (the frames stream at 8 clips per GPU: 98 tiles of 256x256 cannot fill the chip on the 8-phase kernel):
       // 128x256 tiles on 32-wide K stages, 960 against 721 TF/s (64x128) at 12512x512x2048
       else if (a->N <= 512 && nt(128, 256) >= 128) cfg = 6;

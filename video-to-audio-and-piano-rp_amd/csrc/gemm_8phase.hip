@@ -51,7 +51,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
   constexpr int BM = 256, BN = 256, WM = 128, WN = 64, TM = 8, TN = 4;
   constexpr int HALF = 128 * 128;               // bytes of a half tile
   constexpr int BUF = 4 * HALF;                 // AH0 | AH1 | BH0 | BH1
-  static_assert(EPI != V2A_EPI_GEGLU || (TN % 2 == 0), "GEGLU needs value/gate tile pairs");
+  static_assert(!is_glu(EPI) || (TN % 2 == 0), "GEGLU / SWIGLU need value/gate tile pairs");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 
   const int tid = threadIdx.x;
@@ -320,8 +320,8 @@ int launch_8ph(const GemmParams& p_in, hipStream_t s) {
   if (p.s3_kl != 0) {
     if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2, true>);
     else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1, true>);
-  } else if constexpr (EPI == V2A_EPI_GELU) {
-    return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): GELU needs split operands");
+  } else if constexpr (EPI == V2A_EPI_GELU || EPI == V2A_EPI_SWIGLU) {
+    return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): GELU / SWIGLU need split operands");
   } else {
     if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2, false>);
     else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1, false>);
@@ -341,6 +341,9 @@ int v2a_detail::launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dt
       return out_f32 ? launch_8ph<V2A_EPI_GEGLU, float>(p, s) : launch_8ph<V2A_EPI_GEGLU, bf16_t>(p, s);
     case V2A_EPI_GELU:     // v2a_gemm admits it here with split operands only (fp32 output, or hi | lo planes through bf16_t + out_split)
       if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_GELU, float>(p, s) : launch_8ph<V2A_EPI_GELU, bf16_t>(p, s);
+      break;
+    case V2A_EPI_SWIGLU:   // likewise: split operands only
+      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_SWIGLU, float>(p, s) : launch_8ph<V2A_EPI_SWIGLU, bf16_t>(p, s);
       break;
     case V2A_EPI_RESID:
       if (out_f32) return launch_8ph<V2A_EPI_RESID, float>(p, s);

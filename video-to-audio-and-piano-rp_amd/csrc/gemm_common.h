@@ -143,6 +143,14 @@ __device__ __forceinline__ void tile_of_block(const GemmParams& p, int bid, int&
   tile_of_index(p, L, tm, tn);
 }
 
+// the gated-linear-unit epilogues share the [16 value | 16 gate] row packing and the N / 2 output columns; they differ in the gate's activation
+__host__ __device__ constexpr bool is_glu(int epi) { return epi == V2A_EPI_GEGLU || epi == V2A_EPI_SWIGLU; }
+// FAST: the forms whose result is rounded to bf16 planes anyway (Abramowitz-Stegun erf; v_exp based silu); otherwise exact erff / expf and division
+template <int EPI, bool FAST> __device__ __forceinline__ float glu_act(float g) {
+  if constexpr (EPI == V2A_EPI_SWIGLU) return FAST ? silu_f(g) : silu_exact_f(g);
+  else return FAST ? gelu_fast_f(g) : gelu_erf_f(g);
+}
+
 template <typename T> struct TileCfg;
 template <> struct TileCfg<bf16_t> {
   static constexpr int BK = 64;
@@ -232,7 +240,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
       if (m >= p.M) continue;
       const float* gvec = nullptr;
       if constexpr (EPI == V2A_EPI_GATE_RESID) gvec = step_vec(p.gate, p.step, p.gss, p.gbs, p.gbs ? m / p.rpb : 0);
-      if constexpr (EPI == V2A_EPI_GEGLU) {
+      if constexpr (is_glu(EPI)) {
 #pragma unroll
         for (int j = 0; j < TN; j += 2) {
           const int n = n0 + wn * WN + j * 16 + lr;  // packed row index of the value
@@ -240,7 +248,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
           float v = acc[i][j][jj], g = acc[i][j + 1][jj];
           if (p.bias) { v += p.bias[n]; g += p.bias[n + 16]; }
           const int oc = ((n0 + wn * WN) >> 1) + (j >> 1) * 16 + lr;
-          const float ge = sizeof(OutT) == 2 ? gelu_fast_f(g) : gelu_erf_f(g);
+          const float ge = glu_act<EPI, sizeof(OutT) == 2>(g);
           out[(int64_t)m * p.ldo + oc] = from_f32<OutT>(v * ge);
         }
       } else {
@@ -389,7 +397,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
   bf16_t* out2 = p.out2;
   const float* resid = p.resid;
   // folded RMSNorm, consumer side: one scale per row this lane touches, all requested before the first slab is staged
-  constexpr int LPRX = (EPI == V2A_EPI_GEGLU ? WN / 2 : WN) / 4;   // lanes per row of the store loops below
+  constexpr int LPRX = (is_glu(EPI) ? WN / 2 : WN) / 4;   // lanes per row of the store loops below
   constexpr int RPSX = 16 / (64 / LPRX);                           // rows per lane per slab
   // folded RMSNorm, producer side: the gamma pieces of this lane's four columns, loaded once (they depend on the row only through
   // the switch row, or through the batch when every clip has its own time -- then they are fetched per row below)
@@ -405,7 +413,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
   float rsc[TM][RPSX];
   const bool scaled = rs_row != nullptr;                           // wave-uniform
   // GEGLU with 16-byte stores (below): needs 16-byte aligned output rows and planes
-  const bool geglu_wide = EPI == V2A_EPI_GEGLU && sizeof(OutT) == 2 && ((uintptr_t)p.out & 15) == 0 && (p.ldo & 7) == 0 && ((p.N >> 1) & 7) == 0 &&
+  const bool geglu_wide = is_glu(EPI) && sizeof(OutT) == 2 && ((uintptr_t)p.out & 15) == 0 && (p.ldo & 7) == 0 && ((p.N >> 1) & 7) == 0 &&
                           !(p.dbg & 128);       // v2a_tuning.reserved[0] bit 7: the four-column form (A/B)
   if (scaled) {
 #pragma unroll
@@ -422,7 +430,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) tile[(lq * 4 + jj) * LD + j * 16 + lr] = acc[i][j][jj];
     // same wave wrote and reads: LDS operations of one wave complete in order, no barrier needed
-    if constexpr (EPI == V2A_EPI_GEGLU && sizeof(OutT) == 2 && (WN / 2) % 32 == 0) {
+    if constexpr (is_glu(EPI) && sizeof(OutT) == 2 && (WN / 2) % 32 == 0) {
       // bf16 / hi | lo outputs of a wave tile with >= 32 output columns: EIGHT columns per lane, so that every global store is 16 bytes (the
       // 8-byte pieces of the four-column form below made the 128 KB of a 256x256 tile's planes a store-issue-bound tail); taken when the
       // rows allow it (wave-uniform test), the four-column form otherwise
@@ -456,7 +464,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float o32 = (v[e] + bv[h2][e]) * gelu_fast_f(g[e] + bg[h2][e]);
+              const float o32 = (v[e] + bv[h2][e]) * glu_act<EPI, true>(g[e] + bg[h2][e]);
               hi[4 * h2 + e] = (bf16_t)o32;
               lo[4 * h2 + e] = (bf16_t)(o32 - (float)hi[4 * h2 + e]);
             }
@@ -468,7 +476,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
         continue;
       }
     }
-    if constexpr (EPI == V2A_EPI_GEGLU) {
+    if constexpr (is_glu(EPI)) {
       constexpr int OC = WN / 2;                 // output columns of this wave
       constexpr int LPR = OC / 4;                // lanes per row
       constexpr int RPI = 64 / LPR;              // rows per pass
@@ -494,13 +502,14 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
         OutT* dst = out + (int64_t)m * p.ldo + (n_base >> 1) + c4;
         if constexpr (sizeof(OutT) == 2) {
           if (p.out_split) {
-            // bf16x3 mode: fp32 GELU stored as hi | lo planes (lo plane N / 2 columns further).  erf by Abramowitz-Stegun 7.1.26
+            // bf16x3 mode: the fp32 product stored as hi | lo planes (lo plane N / 2 columns further).  SWIGLU: silu on v_exp_f32 (a few ulp, below the
+            // 2^-17 the planes keep).  GEGLU: erf by Abramowitz-Stegun 7.1.26
             // (|error| <= 1.5e-7, two orders below the 2^-17 the planes keep): libm's branchy erff cost ~20 us per 256x256 tile round
             // here against ~6 (64 values per lane), a fifth of a feed-forward launch at 8 clips per GPU
             bf16x4 hi, lo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float o32 = (v[e] + bv[e]) * gelu_fast_f(g[e] + bg[e]);
+              const float o32 = (v[e] + bv[e]) * glu_act<EPI, true>(g[e] + bg[e]);
               hi[e] = (bf16_t)o32;
               lo[e] = (bf16_t)(o32 - (float)hi[e]);
             }
@@ -509,13 +518,13 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&a
           } else {
             bf16x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)((v[e] + bv[e]) * gelu_fast_f(g[e] + bg[e]));
+            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)((v[e] + bv[e]) * glu_act<EPI, true>(g[e] + bg[e]));
             *reinterpret_cast<bf16x4*>(dst) = o;
           }
         } else {
           f32x4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (v[e] + bv[e]) * gelu_erf_f(g[e] + bg[e]);
+          for (int e = 0; e < 4; ++e) o[e] = (v[e] + bv[e]) * glu_act<EPI, false>(g[e] + bg[e]);
           *reinterpret_cast<f32x4*>(dst) = o;
         }
       }

@@ -64,6 +64,7 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float silu_exact_f(float x) { return x / (1.0f + expf(-x)); }   // libm expf, IEEE division: the fp32 parity form
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7): one v_exp + one v_rcp instead of libm erff's
 // branchy polynomial; used where the result is rounded to bf16 anyway.

@@ -212,7 +212,7 @@ class E2TTS:
         self._engine: DiTEngine | None = None
         self._v2r_sd, self._v2r = None, None      # optional Video2Roll frame encoder (video2roll_net.*, x3:1523)
         self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
-        self._clip = None                         # optional CLIP image encoder (load_image_encoder, x3:1423-1425)
+        self._clip = None                         # optional image encoder (load_image_encoder: CLIP x3:1423-1425 or DINOv2 x3:1432-1433)
         self._audio_encoder = None                # optional Encodec encoder behind a raw-wave cond (load_audio_encoder, x3:1350)
         self._piano_pre = None                    # piano-frame preprocessor of this device (piano_frame_preprocessor, x3:1877-1891)
         L.lib()  # no library -> no sampler
@@ -369,12 +369,28 @@ class E2TTS:
         return enc
 
     def load_image_encoder(self, src, **kw):
-        """The CLIP image encoder behind `video_frames=` and uncached `video_paths` (x3:1423-1425, 1714, 1733-1735): a
-        `CLIPImageEncoder`, a local HF directory (IP-Adapter sdxl_models/image_encoder) or a state dict (CLIPVisionModelWithProjection
-        keys, or a reference checkpoint with `image_encoder.*`).  `kw` go to the CLIPImageEncoder constructor (compute, chunk,
-        config).  Only video_encoder="clip_vit" has this encoder."""
+        """The image encoder behind `video_frames=` and uncached `video_paths`.  video_encoder="clip_vit" (x3:1423-1425, 1714,
+        1733-1735): a `CLIPImageEncoder`, a local HF directory (IP-Adapter sdxl_models/image_encoder) or a state dict
+        (CLIPVisionModelWithProjection keys, or a reference checkpoint with `image_encoder.*`).  video_encoder="dinov2"
+        (x3:1432-1433, 1714, 1742-1744): a `DINOv2ImageEncoder`, a local HF directory (dinov2-giant) or a state dict (Dinov2Model keys,
+        or `image_encoder.*`); its hidden_size must equal dim_text.  `kw` go to the encoder's constructor (compute, chunk, config).
+        The other choices of the reference have no encoder here."""
+        if self.video_encoder == "dinov2":
+            from .dinov2 import DINOv2ImageEncoder
+            if isinstance(src, DINOv2ImageEncoder):
+                enc = src
+            elif isinstance(src, (str, Path)):
+                enc = DINOv2ImageEncoder.from_pretrained(str(src), self._device, **kw)
+            elif isinstance(src, dict):
+                enc = DINOv2ImageEncoder(src, self._device, **kw)
+            else:
+                raise TypeError(f"load_image_encoder: a DINOv2ImageEncoder, a directory or a state dict, got {type(src).__name__}")
+            if enc.d != self.dim_text:
+                raise ValueError(f"load_image_encoder: the DINOv2 encoder's hidden_size {enc.d} is not the model's dim_text {self.dim_text}")
+            self._clip = enc
+            return enc
         if self.video_encoder != "clip_vit":
-            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit' has the HIP CLIP encoder)")
+            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit' and 'dinov2' have a HIP encoder)")
         from .clip import CLIPImageEncoder
         if isinstance(src, CLIPImageEncoder):
             enc = src

@@ -264,6 +264,63 @@ def random_clip_vision_state_dict(config: dict, seed: int = 0, outlier: float = 
     return sd
 
 
+# facebook/dinov2-giant as Dinov2Model (ViT-g/14, stored at 518 px = 37 x 37 positions): the reference's "dinov2" (x3:1432-1433)
+DINOV2_GIANT = dict(hidden_size=1536, num_hidden_layers=40, num_attention_heads=24, mlp_ratio=4, image_size=518, patch_size=14,
+                    layer_norm_eps=1e-6, use_swiglu_ffn=True, num_channels=3, layerscale_value=1.0)
+
+
+def dinov2_ffn_width(config: dict) -> int:
+    """Hidden values of the feed-forward: Dinov2SwiGLUFFN rounds 2/3 of hidden_size * mlp_ratio up to a multiple of 8, Dinov2MLP takes all."""
+    hf = int(config["hidden_size"] * config.get("mlp_ratio", 4))
+    return (int(hf * 2 / 3) + 7) // 8 * 8 if config.get("use_swiglu_ffn", False) else hf
+
+
+def random_dinov2_state_dict(config: dict, seed: int = 0, outlier: float = 0.0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `Dinov2Model(Dinov2Config(**config))` (dinov2-giant is not reachable offline), by the
+    rules of random_clip_vision_state_dict: numpy PCG64 float32 normals, matrices ~ N(0, 1/fan_in), biases and LayerNorm beta ~ 0.1 N,
+    gamma ~ 1 + 0.1 N.  LayerScale is drawn uniformly from 0.05 .. 1 (trained values, not the init value 1, so its fold is exercised).
+    `outlier > 0` scales the `dense` and `weights_out` / `fc2` rows (and biases) of a few residual channels by `outlier`, which
+    drives those channels to |h| ~ 1e2 over the layers."""
+    import numpy as np
+
+    c = dict(config)
+    d, nl, P, S, ch = c["hidden_size"], c["num_hidden_layers"], c["patch_size"], c["image_size"], c.get("num_channels", 3)
+    swiglu, hf = bool(c.get("use_swiglu_ffn", False)), dinov2_ffn_width(c)
+    T = 1 + (S // P) ** 2
+    rng = np.random.default_rng(seed)
+    nrm = lambda shp, s: torch.from_numpy(rng.standard_normal(shp, dtype=np.float32) * np.float32(s))
+    hot = torch.from_numpy(rng.choice(d, size=4, replace=False)) if outlier > 0 else None
+
+    def boost(w, b):
+        if hot is not None:
+            w[hot] *= outlier
+            b[hot] *= outlier
+        return w, b
+
+    E = "embeddings."
+    sd = {E + "cls_token": nrm((1, 1, d), 0.5), E + "mask_token": torch.zeros(1, d), E + "position_embeddings": nrm((1, T, d), 0.2),
+          E + "patch_embeddings.projection.weight": nrm((d, ch, P, P), 1.0 / math.sqrt(ch * P * P)),
+          E + "patch_embeddings.projection.bias": nrm((d,), 0.1)}
+    for i in range(nl):
+        p = f"encoder.layer.{i}."
+        for n in ("query", "key", "value"):
+            sd[p + f"attention.attention.{n}.weight"] = nrm((d, d), 1.0 / math.sqrt(d))
+            sd[p + f"attention.attention.{n}.bias"] = nrm((d,), 0.1)
+        sd[p + "attention.output.dense.weight"], sd[p + "attention.output.dense.bias"] = boost(nrm((d, d), 1.0 / math.sqrt(d)), nrm((d,), 0.1))
+        sd[p + "norm1.weight"], sd[p + "norm1.bias"] = 1.0 + nrm((d,), 0.1), nrm((d,), 0.1)
+        sd[p + "norm2.weight"], sd[p + "norm2.bias"] = 1.0 + nrm((d,), 0.1), nrm((d,), 0.1)
+        sd[p + "layer_scale1.lambda1"] = torch.from_numpy(rng.uniform(0.05, 1.0, d).astype(np.float32))
+        sd[p + "layer_scale2.lambda1"] = torch.from_numpy(rng.uniform(0.05, 1.0, d).astype(np.float32))
+        if swiglu:
+            sd[p + "mlp.weights_in.weight"], sd[p + "mlp.weights_in.bias"] = nrm((2 * hf, d), 1.0 / math.sqrt(d)), nrm((2 * hf,), 0.1)
+            sd[p + "mlp.weights_out.weight"], sd[p + "mlp.weights_out.bias"] = boost(nrm((d, hf), 1.0 / math.sqrt(hf)), nrm((d,), 0.1))
+        else:
+            sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = nrm((hf, d), 1.0 / math.sqrt(d)), nrm((hf,), 0.1)
+            sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = boost(nrm((d, hf), 1.0 / math.sqrt(hf)), nrm((d,), 0.1))
+    sd["layernorm.weight"], sd["layernorm.bias"] = 1.0 + nrm((d,), 0.1), nrm((d,), 0.1)
+    return sd
+
+
 def synthetic_video_frames(n: int, h: int, w: int, seed: int = 0) -> "np.ndarray":
     """(n, h, w, 3) uint8 RGB test frames: smooth per-frame colour gradients plus noise, so the resize filters really average."""
     import numpy as np
