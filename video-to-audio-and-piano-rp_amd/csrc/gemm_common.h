@@ -382,253 +382,429 @@ __device__ __forceinline__ void rope_rotate4(f32x4& v, const f32x4& cs) {
   v[3] = fmaf(b1, cs[2], a1 * cs[3]);
 }
 
-template <int EPI, typename OutT, int TM, int TN, int WM, int WN, bool PF>
-__device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&acc)[TM][TN], float* tile /* wave-private, 16 x (WN+4) floats */,
-                                                  int m_base, int n_base, int lane, const EpiPrefetch<EPI, TM, WN, PF>& pf,
-                                                  const float* rs_row = nullptr /* LDS: row scales of this wave's rows, or null */) {
+// Position of a row inside its batch element (m % rpb) and the batch elements it lies behind the wave's first row, from the position of the wave's
+// first row (one division per wave, gemm_epilogue_lds) and the row's distance d from it: one compare-and-subtract, since rpb need not be a multiple of
+// anything here.  A batch element shorter than the wave tile (no shape the engines launch) can be wrapped more than once: the loop behind the test.
+__device__ __forceinline__ void row_pos(int p0, int d, int rpb, bool multi, int& pos, int& nb) {
+  pos = p0 + d;
+  nb = 0;
+  if (pos >= rpb) { pos -= rpb; nb = 1; }
+  if (multi) {
+    while (pos >= rpb) { pos -= rpb; ++nb; }
+  }
+}
+
+// Epilogue operands and the chain they once formed (PF = false: the 8-phase kernel and the ring tiles whose registers do not allow a prefetch at
+// kernel start).  gfx950 counts loads and stores in ONE in-order vmcnt, so a load requested between two rows' stores is waited for with vmcnt(0),
+// which also waits for every store before it: with the cos/sin or residual row requested per row, a wave paid one L2 round trip and one store
+// drain per row, 32 times in a row (profiles/r07_8phase_epilogue_ab.txt).  Now:
+//   * what does not depend on the slab -- the bias pieces of the lane's columns, the device step counter (one wave-uniform load, turned into base
+//     pointers of the gate / gamma step vectors), and the gate / gamma pieces of the lane's columns for the one or two batch elements the wave's rows
+//     lie in -- is requested once, ahead of the slab loop: in the 8-phase kernel right behind the barrier that ends the K loop, into the registers
+//     the fragments free.  It is waited for once, behind the first slab's LDS writes;
+//   * what depends on the row -- cos/sin rows (STORE), residual rows (RESID, GATE_RESID) -- runs in a two-slab pipeline: slab i + 1's rows are
+//     requested before slab i's stores are issued, so the wait for them can count past those stores.  A wave whose tile lies wholly inside the
+//     problem (all but the last row band / a 16-column last tile) and whose rows are dense runs a form of the loop without row or column
+//     predicates (ALL): the compiler's counts take the lower bound over every branch, and a row block that may be skipped counts for nothing;
+//   * a row's position in its batch element comes from one division per wave (its first row) and a compare-and-subtract per row;
+//   * slabs behind the last row end the loop (they are a suffix of the wave's slabs), so nothing is requested for them.
+// A batch element shorter than the wave tile (more than two elements under a wave) keeps per-row gate / gamma loads, without the step counter.
+// The arithmetic of every element is what it was: same expressions, same order.
+// (The two forms are two instantiations of a function, not two calls of a generic lambda: a select between variables a lambda captures by
+// reference becomes a load through a selected address and puts the accumulators on the stack.)
+template <int EPI, bool PF> constexpr bool epi_pipelined() { return !PF && (EPI == V2A_EPI_STORE || EPI == V2A_EPI_RESID || EPI == V2A_EPI_GATE_RESID); }
+
+template <int EPI, typename OutT, int TM, int TN, int WM, int WN, bool PF, bool ALL>
+__device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmParams& p, f32x4 (&acc)[TM][TN], float* tile, int m_base, int n_base, int lane,
+                                                       const EpiPrefetch<EPI, TM, WN, PF>& pf, const float* rs_row) {
   constexpr int LD = WN + 4;                   // 16-B aligned rows, <= 2-way write conflicts
   const int lr = lane & 15, lq = lane >> 4;
   OutT* out = reinterpret_cast<OutT*>(p.out);
   // kernel arguments copied once (the slab loops below otherwise re-load them from the argument segment per row)
-  const int M = p.M;
+  const int M = p.M, N = p.N;
   const bool relu = p.relu != 0;
-  const int32_t* orow = p.o_rowoff;           // scattered rows (implicit-GEMM convolution into a bordered map) or null
+  const int32_t* orow = ALL ? nullptr : p.o_rowoff;   // scattered rows (implicit-GEMM convolution into a bordered map) or null; never in the ALL form
   const int64_t ldo = p.ldo, ldr = p.ldr, ldo2 = p.ldo2;
   bf16_t* out2 = p.out2;
   const float* resid = p.resid;
+  const float* bias = p.bias;
   // folded RMSNorm, consumer side: one scale per row this lane touches, all requested before the first slab is staged
   constexpr int LPRX = (is_glu(EPI) ? WN / 2 : WN) / 4;   // lanes per row of the store loops below
   constexpr int RPSX = 16 / (64 / LPRX);                           // rows per lane per slab
-  // folded RMSNorm, producer side: the gamma pieces of this lane's four columns, loaded once (they depend on the row only through
-  // the switch row, or through the batch when every clip has its own time -- then they are fetched per row below)
-  f32x4 gmA = {1.f, 1.f, 1.f, 1.f}, gmB = gmA;
-  if constexpr ((EPI == V2A_EPI_RESID || EPI == V2A_EPI_GATE_RESID) && sizeof(OutT) == 4) {
-    const int nn = n_base + (lane % (WN / 4)) * 4;
-    if (out2 && p.ngam && p.ngbs == 0 && nn + 3 < p.N) {
-      const float* gb = step_vec(p.ngam, p.step, p.ngss, 0, 0) + nn;
-      gmA = *reinterpret_cast<const f32x4*>(gb);
-      gmB = *reinterpret_cast<const f32x4*>(gb + p.nsw_off);
-    }
-  }
-  float rsc[TM][RPSX];
+  constexpr bool RESF = EPI == V2A_EPI_RESID || EPI == V2A_EPI_GATE_RESID;
+  constexpr bool GAMF = RESF && sizeof(OutT) == 4;                 // folded RMSNorm, producer side: the shadow carries the norm's gamma
+  constexpr bool PIPE = epi_pipelined<EPI, PF>();                  // row operands in the two-slab pipeline
+  static_assert(PIPE || !ALL, "the unpredicated form belongs to the pipeline");
+  // lane -> (row, 4 columns) map of the plain store form
+  constexpr int LPRV = WN / 4, RPIV = 64 / LPRV, RPSV = 16 / RPIV;
+  const int c4v = (lane % LPRV) * 4, r0v = lane / LPRV;
+  const int nv = n_base + c4v;
+  const bool fullv = nv + 3 < N;               // N is a multiple of 4 for every vector-eligible call (checked on the host)
   const bool scaled = rs_row != nullptr;                           // wave-uniform
   // GEGLU with 16-byte stores (below): needs 16-byte aligned output rows and planes
-  const bool geglu_wide = is_glu(EPI) && sizeof(OutT) == 2 && ((uintptr_t)p.out & 15) == 0 && (p.ldo & 7) == 0 && ((p.N >> 1) & 7) == 0 &&
-                          !(p.dbg & 128);       // v2a_tuning.reserved[0] bit 7: the four-column form (A/B)
-  if (scaled) {
+  const bool geglu_wide = is_glu(EPI) && sizeof(OutT) == 2 && (WN / 2) % 32 == 0 && ((uintptr_t)p.out & 15) == 0 && (p.ldo & 7) == 0 &&
+                          ((p.N >> 1) & 7) == 0 && !(p.dbg & 128);       // v2a_tuning.reserved[0] bit 7: the four-column form (A/B)
+
+  // ---- slab-invariant operands -------------------------------------------------------------------------------------------------
+  // bias pieces of the lane's columns, by store form: GLU eight-column (value 0-3, 4-7, gate 0-3, 4-7), GLU four-column (value, -, gate, -), plain
+  f32x4 bb[is_glu(EPI) ? 4 : 1];
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int q = 0; q < RPSX; ++q) rsc[i][q] = rs_row[i * 16 + lane / LPRX + q * (64 / LPRX)];
+  for (int k = 0; k < (is_glu(EPI) ? 4 : 1); ++k) bb[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (is_glu(EPI)) {
+    if (geglu_wide) {
+      const int c8 = (lane % (WN / 16)) * 8;
+      const int n = n_base + (c8 >> 4) * 32 + (c8 & 15);
+      if (bias && n < N) {
+        bb[0] = *reinterpret_cast<const f32x4*>(bias + n);
+        bb[1] = *reinterpret_cast<const f32x4*>(bias + n + 4);
+        bb[2] = *reinterpret_cast<const f32x4*>(bias + n + 16);
+        bb[3] = *reinterpret_cast<const f32x4*>(bias + n + 20);
+      }
+    } else {
+      const int c4 = (lane % (WN / 8)) * 4;
+      const int n = n_base + (c4 >> 4) * 32 + (c4 & 15);
+      if (bias && n < N) {
+        bb[0] = *reinterpret_cast<const f32x4*>(bias + n);
+        bb[2] = *reinterpret_cast<const f32x4*>(bias + n + 16);
+      }
+    }
+  } else {
+    if (bias && fullv) bb[0] = *reinterpret_cast<const f32x4*>(bias + nv);
   }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    if (m_base + i * 16 >= M) continue;          // a slab wholly behind the last row (wave-uniform): nothing to stage or store
-    // one 16-row slab of the wave tile at a time: the staging area of a workgroup is a few KB of one ring stage
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) tile[(lq * 4 + jj) * LD + j * 16 + lr] = acc[i][j][jj];
-    // same wave wrote and reads: LDS operations of one wave complete in order, no barrier needed
-    if constexpr (is_glu(EPI) && sizeof(OutT) == 2 && (WN / 2) % 32 == 0) {
-      // bf16 / hi | lo outputs of a wave tile with >= 32 output columns: EIGHT columns per lane, so that every global store is 16 bytes (the
-      // 8-byte pieces of the four-column form below made the 128 KB of a 256x256 tile's planes a store-issue-bound tail); taken when the
-      // rows allow it (wave-uniform test), the four-column form otherwise
-      if (geglu_wide) {
-        constexpr int OC = WN / 2, LPR = OC / 8, RPI = 64 / LPR;
-        static_assert(RPI <= 16, "one slab holds 16 rows");
-        const int c8 = (lane % LPR) * 8, r0 = lane / LPR;
-        const int lc = (c8 >> 4) * 32 + (c8 & 15);            // LDS column of the first value; the gates lie 16 further
-        const int n = n_base + lc;
-        f32x4 bv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, bg[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        if (p.bias && n < p.N) {
-          bv[0] = *reinterpret_cast<const f32x4*>(p.bias + n);
-          bv[1] = *reinterpret_cast<const f32x4*>(p.bias + n + 4);
-          bg[0] = *reinterpret_cast<const f32x4*>(p.bias + n + 16);
-          bg[1] = *reinterpret_cast<const f32x4*>(p.bias + n + 20);
+  // the device step counter, read once per wave (a wave-uniform address: a scalar load), as base pointers of the gate / gamma step vectors
+  const float* gate_b = nullptr;
+  const float* ngam_b = nullptr;
+  if constexpr (RESF) {
+    const int64_t stepv = p.step ? (int64_t)p.step[0] : 0;
+    if (p.gate) gate_b = p.gate + stepv * p.gss;
+    if (p.ngam) ngam_b = p.ngam + stepv * p.ngss;
+  }
+  // the wave's first row inside its batch element: the one division
+  const int rpb = p.rpb;
+  const bool rope_on = PIPE && EPI == V2A_EPI_STORE && p.rope != nullptr && n_base < p.rope_cols;   // rope_cols % 64 == 0 and the wave's
+  static_assert(64 % WN == 0 || EPI != V2A_EPI_STORE || PF, "a wave's columns lie in one 64-column head");   // columns lie in one head: wave-uniform
+  const bool gate_pb = PIPE && EPI == V2A_EPI_GATE_RESID && gate_b != nullptr && p.gbs != 0;
+  const bool gam_on = GAMF && out2 != nullptr && ngam_b != nullptr;
+  const bool gam_pb = gam_on && p.ngbs != 0;
+  int b0 = 0, p0 = 0;
+  bool onebatch = true, twobatch = true;
+  if (rope_on || gate_pb || (PIPE && gam_pb)) {
+    const int mb = __builtin_amdgcn_readfirstlane(m_base);
+    b0 = mb / rpb;
+    p0 = mb - b0 * rpb;
+    const int last = p0 + ((mb + WM < M ? mb + WM : M) - 1 - mb);      // the wave's last row, counted from the start of the first row's batch element
+    onebatch = last < rpb;
+    twobatch = last < 2 * rpb;
+  }
+  const int m_sw = m_base - p0 + rpb;          // first row of the next batch element
+  const bool multi = rpb < WM;                 // a wave tile can span more than two batch elements
+  // gate / gamma pieces of the lane's columns, once per wave: shared over the batch, or per batch for the (at most two, unless a batch element is
+  // shorter than the wave tile) elements the wave's rows lie in -- the second set is read only when rows of a second element exist.  Then the row picks
+  // its set by a compare, as at the switch row.  Waves that span more elements load per row (gate_row / gam_row), without the step counter.
+  // PF = true kernels keep their form: shared gamma once, per-batch gamma per row.
+  const bool gate_row = gate_pb && !twobatch, gam_row = gam_pb && !(PIPE && twobatch);
+  const bool gate_two = gate_pb && !onebatch && !gate_row, gam_two = PIPE && gam_pb && !onebatch && !gam_row;   // rows from m_sw on take the second set
+  f32x4 gmA = {1.f, 1.f, 1.f, 1.f}, gmB = gmA, gmC = gmA, gmD = gmA, gt1 = gmA, gt2 = gmA;
+  if constexpr (GAMF) {
+    if (gam_on && !gam_row && fullv && m_base < M) {
+      const float* gb = ngam_b + (gam_pb ? (int64_t)b0 * p.ngbs : 0) + nv;
+      gmA = *reinterpret_cast<const f32x4*>(gb);
+      gmB = *reinterpret_cast<const f32x4*>(gb + p.nsw_off);
+      if constexpr (PIPE) {
+        if (gam_two) {
+          gmC = *reinterpret_cast<const f32x4*>(gb + p.ngbs);
+          gmD = *reinterpret_cast<const f32x4*>(gb + p.ngbs + p.nsw_off);
         }
+      }
+    }
+  }
+  if constexpr (PIPE && EPI == V2A_EPI_GATE_RESID) {
+    if (gate_b && !gate_row && fullv && m_base < M) {
+      const float* gp = gate_b + (gate_pb ? (int64_t)b0 * p.gbs : 0) + nv;
+      gt1 = *reinterpret_cast<const f32x4*>(gp);
+      if (gate_two) gt2 = *reinterpret_cast<const f32x4*>(gp + p.gbs);
+    }
+  }
+  // (the pipelined form reads a row's scale from LDS when it comes to the row: 32 registers it needs for the rows in flight)
+  float rsc[PIPE ? 1 : TM][PIPE ? 1 : RPSX];
+  if constexpr (!PIPE) {
+    if (scaled) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int q = 0; q < RPSX; ++q) rsc[i][q] = rs_row[i * 16 + lane / LPRX + q * (64 / LPRX)];
+    }
+  }
+
+  // ---- slab-variant operands: two sets, slab i reads set i & 1 while set (i + 1) & 1 is in flight -----------------------------------
+  f32x4 q_a[PIPE ? 2 : 1][PIPE ? RPSV : 1];                                                  // STORE: (cos, sin) pairs; RESID / GATE_RESID: residual pieces
+  {
+    // (the trip i = -1 only requests slab 0: one copy of the request code, in line -- as a lambda called from two places it made the compiler keep
+    // both sets in one 32-register tuple, copied whole after every load)
+#pragma unroll
+    for (int i = -1; i < TM; ++i) {
+      // a slab wholly behind the last row (wave-uniform): nothing to stage or store, and so for every slab after it -- nothing was requested for it either
+      if (!ALL && m_base + (i < 0 ? 0 : i) * 16 >= M) break;
+      if constexpr (PIPE) {
+        // slab i + 1's rows go out before slab i's stores (none for a slab behind the last row); the fence keeps them there
+        if (i + 1 < TM && (ALL || m_base + (i + 1) * 16 < M)) {
+#pragma unroll
+          for (int q = 0; q < RPSV; ++q) {
+            const int m = m_base + (i + 1) * 16 + r0v + q * RPIV;
+            const bool ok = ALL || (m < M && fullv);
+            if constexpr (EPI == V2A_EPI_STORE) {
+              if (rope_on && ok) {
+                int pos, nb;
+                row_pos(p0, m - m_base, rpb, multi, pos, nb);
+                q_a[(i + 1) & 1][q] = *reinterpret_cast<const f32x4*>(p.rope + ((int64_t)(p.rope_pos_off + pos) * 32 + ((nv & 63) >> 1)) * 2);
+              }
+            }
+            if constexpr (RESF) {
+              if (ok) {
+                int64_t o_res = (int64_t)m * ldr;
+                if constexpr (EPI == V2A_EPI_RESID) { if (orow) o_res = orow[m]; }
+                q_a[(i + 1) & 1][q] = *reinterpret_cast<const f32x4*>(resid + o_res + nv);       // (the host requires resid with these epilogues)
+              }
+            }
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (i < 0) continue;
+      // one 16-row slab of the wave tile at a time: the staging area of a workgroup is a few KB of one ring stage
+      // (fences around slabs and rows of the pipelined form: its unpredicated loop is one basic block of eight slabs, and left alone the scheduler
+      // lifts addresses and LDS reads of later rows over earlier ones until the accumulators spill)
+      if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) tile[(lq * 4 + jj) * LD + j * 16 + lr] = acc[i][j][jj];
+      // same wave wrote and reads: LDS operations of one wave complete in order, no barrier needed
+      if (i == 0) {
+        // the one wait for the slab-invariant operands, behind the first slab's LDS writes: a use here, so that the compiler waits here once.  Left to
+        // the first real use it repeats the wait in every row block (each can be entered past the others) as vmcnt(0), which drains the row's stores
+#pragma unroll
+        for (int k = 0; k < (is_glu(EPI) ? 4 : 1); ++k) asm volatile("" : "+v"(bb[k]));
+        if constexpr (GAMF) asm volatile("" : "+v"(gmA), "+v"(gmB), "+v"(gmC), "+v"(gmD));
+        if constexpr (PIPE && EPI == V2A_EPI_GATE_RESID) asm volatile("" : "+v"(gt1), "+v"(gt2));
+      }
+      if constexpr (is_glu(EPI) && sizeof(OutT) == 2 && (WN / 2) % 32 == 0) {
+        // bf16 / hi | lo outputs of a wave tile with >= 32 output columns: EIGHT columns per lane, so that every global store is 16 bytes (the
+        // 8-byte pieces of the four-column form below made the 128 KB of a 256x256 tile's planes a store-issue-bound tail); taken when the
+        // rows allow it (wave-uniform test), the four-column form otherwise
+        if (geglu_wide) {
+          constexpr int OC = WN / 2, LPR = OC / 8, RPI = 64 / LPR;
+          static_assert(RPI <= 16, "one slab holds 16 rows");
+          const int c8 = (lane % LPR) * 8, r0 = lane / LPR;
+          const int lc = (c8 >> 4) * 32 + (c8 & 15);            // LDS column of the first value; the gates lie 16 further
+          const int n = n_base + lc;
+#pragma unroll
+          for (int q = 0; q < 16 / RPI; ++q) {
+            const int r = r0 + q * RPI;
+            const int m = m_base + i * 16 + r;
+            if (m >= M || n >= N) continue;
+            const float rs = scaled ? rs_row[i * 16 + r] : 1.f;
+            bf16x8 hi, lo;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2) {
+              f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * LD + lc + 4 * h2);
+              f32x4 g = *reinterpret_cast<const f32x4*>(tile + r * LD + lc + 16 + 4 * h2);
+              if (scaled) {          // (the same expressions as the four-column form: equal bit for bit)
+                v *= rs;
+                g *= rs;
+              }
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float o32 = (v[e] + bb[h2][e]) * glu_act<EPI, true>(g[e] + bb[2 + h2][e]);
+                hi[4 * h2 + e] = (bf16_t)o32;
+                lo[4 * h2 + e] = (bf16_t)(o32 - (float)hi[4 * h2 + e]);
+              }
+            }
+            OutT* dst = out + (int64_t)m * ldo + (n_base >> 1) + c8;
+            *reinterpret_cast<bf16x8*>(dst) = hi;
+            if (p.out_split) *reinterpret_cast<bf16x8*>(dst + (N >> 1)) = lo;
+          }
+          continue;
+        }
+      }
+      if constexpr (is_glu(EPI)) {
+        constexpr int OC = WN / 2;                 // output columns of this wave
+        constexpr int LPR = OC / 4;                // lanes per row
+        constexpr int RPI = 64 / LPR;              // rows per pass
+        const int c4 = (lane % LPR) * 4, r0 = lane / LPR;
+        const int lc = (c4 >> 4) * 32 + (c4 & 15); // LDS column of the value; gate is 16 further
+        const int n = n_base + lc;                 // packed W row of the value
+        const f32x4 bv = bb[0], bg = bb[2];
 #pragma unroll
         for (int q = 0; q < 16 / RPI; ++q) {
           const int r = r0 + q * RPI;
           const int m = m_base + i * 16 + r;
-          if (m >= p.M || n >= p.N) continue;
-          const float rs = scaled ? rs_row[i * 16 + r] : 1.f;
-          bf16x8 hi, lo;
-#pragma unroll
-          for (int h2 = 0; h2 < 2; ++h2) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * LD + lc + 4 * h2);
-            f32x4 g = *reinterpret_cast<const f32x4*>(tile + r * LD + lc + 16 + 4 * h2);
-            if (scaled) {          // (the same expressions as the four-column form: equal bit for bit)
-              v *= rs;
-              g *= rs;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float o32 = (v[e] + bv[h2][e]) * glu_act<EPI, true>(g[e] + bg[h2][e]);
-              hi[4 * h2 + e] = (bf16_t)o32;
-              lo[4 * h2 + e] = (bf16_t)(o32 - (float)hi[4 * h2 + e]);
-            }
+          if (m >= M || n >= N) continue;
+          f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * LD + lc);
+          f32x4 g = *reinterpret_cast<const f32x4*>(tile + r * LD + lc + 16);
+          if (scaled) {
+            v *= rsc[i][q];
+            g *= rsc[i][q];
           }
-          OutT* dst = out + (int64_t)m * p.ldo + (n_base >> 1) + c8;
-          *reinterpret_cast<bf16x8*>(dst) = hi;
-          if (p.out_split) *reinterpret_cast<bf16x8*>(dst + (p.N >> 1)) = lo;
-        }
-        continue;
-      }
-    }
-    if constexpr (is_glu(EPI)) {
-      constexpr int OC = WN / 2;                 // output columns of this wave
-      constexpr int LPR = OC / 4;                // lanes per row
-      constexpr int RPI = 64 / LPR;              // rows per pass
-      const int c4 = (lane % LPR) * 4, r0 = lane / LPR;
-      const int lc = (c4 >> 4) * 32 + (c4 & 15); // LDS column of the value; gate is 16 further
-      const int n = n_base + lc;                 // packed W row of the value
-      f32x4 bv = {0.f, 0.f, 0.f, 0.f}, bg = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias && n < p.N) {
-        bv = *reinterpret_cast<const f32x4*>(p.bias + n);
-        bg = *reinterpret_cast<const f32x4*>(p.bias + n + 16);
-      }
+          OutT* dst = out + (int64_t)m * ldo + (n_base >> 1) + c4;
+          if constexpr (sizeof(OutT) == 2) {
+            if (p.out_split) {
+              // bf16x3 mode: the fp32 product stored as hi | lo planes (lo plane N / 2 columns further).  SWIGLU: silu on v_exp_f32 (a few ulp, below the
+              // 2^-17 the planes keep).  GEGLU: erf by Abramowitz-Stegun 7.1.26
+              // (|error| <= 1.5e-7, two orders below the 2^-17 the planes keep): libm's branchy erff cost ~20 us per 256x256 tile round
+              // here against ~6 (64 values per lane), a fifth of a feed-forward launch at 8 clips per GPU
+              bf16x4 hi, lo;
 #pragma unroll
-      for (int q = 0; q < 16 / RPI; ++q) {
-        const int r = r0 + q * RPI;
-        const int m = m_base + i * 16 + r;
-        if (m >= p.M || n >= p.N) continue;
-        f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * LD + lc);
-        f32x4 g = *reinterpret_cast<const f32x4*>(tile + r * LD + lc + 16);
-        if (scaled) {
-          v *= rsc[i][q];
-          g *= rsc[i][q];
-        }
-        OutT* dst = out + (int64_t)m * p.ldo + (n_base >> 1) + c4;
-        if constexpr (sizeof(OutT) == 2) {
-          if (p.out_split) {
-            // bf16x3 mode: the fp32 product stored as hi | lo planes (lo plane N / 2 columns further).  SWIGLU: silu on v_exp_f32 (a few ulp, below the
-            // 2^-17 the planes keep).  GEGLU: erf by Abramowitz-Stegun 7.1.26
-            // (|error| <= 1.5e-7, two orders below the 2^-17 the planes keep): libm's branchy erff cost ~20 us per 256x256 tile round
-            // here against ~6 (64 values per lane), a fifth of a feed-forward launch at 8 clips per GPU
-            bf16x4 hi, lo;
+              for (int e = 0; e < 4; ++e) {
+                const float o32 = (v[e] + bv[e]) * glu_act<EPI, true>(g[e] + bg[e]);
+                hi[e] = (bf16_t)o32;
+                lo[e] = (bf16_t)(o32 - (float)hi[e]);
+              }
+              *reinterpret_cast<bf16x4*>(dst) = hi;
+              *reinterpret_cast<bf16x4*>(dst + (N >> 1)) = lo;
+            } else {
+              bf16x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float o32 = (v[e] + bv[e]) * glu_act<EPI, true>(g[e] + bg[e]);
-              hi[e] = (bf16_t)o32;
-              lo[e] = (bf16_t)(o32 - (float)hi[e]);
+              for (int e = 0; e < 4; ++e) o[e] = (bf16_t)((v[e] + bv[e]) * glu_act<EPI, true>(g[e] + bg[e]));
+              *reinterpret_cast<bf16x4*>(dst) = o;
             }
-            *reinterpret_cast<bf16x4*>(dst) = hi;
-            *reinterpret_cast<bf16x4*>(dst + (p.N >> 1)) = lo;
           } else {
-            bf16x4 o;
+            f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)((v[e] + bv[e]) * glu_act<EPI, true>(g[e] + bg[e]));
-            *reinterpret_cast<bf16x4*>(dst) = o;
-          }
-        } else {
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (v[e] + bv[e]) * glu_act<EPI, false>(g[e] + bg[e]);
-          *reinterpret_cast<f32x4*>(dst) = o;
-        }
-      }
-    } else {
-      constexpr int LPR = WN / 4;
-      constexpr int RPI = 64 / LPR;
-      const int c4 = (lane % LPR) * 4, r0 = lane / LPR;
-      const int n = n_base + c4;
-      const bool full = n + 3 < p.N;             // N is a multiple of 4 for every vector-eligible call (checked on the host)
-      f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias && full) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
-#pragma unroll
-      for (int q = 0; q < 16 / RPI; ++q) {
-        const int r = r0 + q * RPI;
-        const int m = m_base + i * 16 + r;
-        if (m >= M || !full) continue;
-        int64_t o_out = (int64_t)m * ldo, o_res = (int64_t)m * ldr, o_out2 = (int64_t)m * ldo2;
-        if constexpr (EPI == V2A_EPI_STORE || EPI == V2A_EPI_RESID) {     // offset tables come with STORE / RESID only
-          if (orow) {
-            int64_t ro;
-            if constexpr (PF && EPI == V2A_EPI_RESID) ro = pf.ro[i][q];
-            else ro = orow[m];
-            o_out = o_res = o_out2 = ro;
+            for (int e = 0; e < 4; ++e) o[e] = (v[e] + bv[e]) * glu_act<EPI, false>(g[e] + bg[e]);
+            *reinterpret_cast<f32x4*>(dst) = o;
           }
         }
-        f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * LD + c4);
-        if (scaled) v *= rsc[i][q];
+      } else {
+        constexpr int RPI = RPIV;
+        const int c4 = c4v, r0 = r0v, n = nv;
+        const bool full = fullv;
+        const f32x4 bv = bb[0];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += bv[e];
-        if constexpr (EPI == V2A_EPI_SIGMOID) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = sigmoid_f(v[e]);
-        }
-        if constexpr (EPI == V2A_EPI_GELU) {
-          // fp32 output: exact erff (fp32 parity of CLIPMLP); hi | lo planes: Abramowitz-Stegun erf (|error| <= 1.5e-7, below the
-          // 2^-17 the planes keep), as the GEGLU epilogue's split form
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = sizeof(OutT) == 2 ? gelu_fast_f(v[e]) : gelu_erf_f(v[e]);
-        }
-        if constexpr (EPI == V2A_EPI_STORE) {
-          if (p.rope && n < p.rope_cols) {
-            // interleaved RoPE (A6): columns (n, n+1) and (n+2, n+3) are pairs (n & 63) / 2 and +1 of this head
-            f32x4 cs;
-            if constexpr (PF) cs = pf.cs[i][q];
-            else cs = *reinterpret_cast<const f32x4*>(p.rope + ((int64_t)(p.rope_pos_off + m % p.rpb) * 32 + ((n & 63) >> 1)) * 2);
-            rope_rotate4(v, cs);
-          }
-        }
-        if constexpr (EPI == V2A_EPI_RESID || EPI == V2A_EPI_GATE_RESID) {
-          f32x4 rs, gt = {1.f, 1.f, 1.f, 1.f};
-          if constexpr (PF) {
-            rs = pf.rs[i][q];
-            if constexpr (EPI == V2A_EPI_GATE_RESID) gt = pf.gt[i][q];
-          } else {
-            rs = resid ? *reinterpret_cast<const f32x4*>(resid + o_res + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (EPI == V2A_EPI_GATE_RESID) {
-              if (p.gate) gt = *reinterpret_cast<const f32x4*>(step_vec(p.gate, p.step, p.gss, p.gbs, p.gbs ? m / p.rpb : 0) + n);
+        for (int q = 0; q < 16 / RPI; ++q) {
+          const int r = r0 + q * RPI;
+          const int m = m_base + i * 16 + r;
+          if (!ALL && (m >= M || !full)) continue;
+          int64_t o_out = (int64_t)m * ldo, o_res = (int64_t)m * ldr, o_out2 = (int64_t)m * ldo2;
+          if constexpr (EPI == V2A_EPI_STORE || EPI == V2A_EPI_RESID) {     // offset tables come with STORE / RESID only
+            if (orow) {
+              int64_t ro;
+              if constexpr (PF && EPI == V2A_EPI_RESID) ro = pf.ro[i][q];
+              else ro = orow[m];
+              o_out = o_res = o_out2 = ro;
             }
           }
+          f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * LD + c4);
+          if (scaled) v *= PIPE ? rs_row[i * 16 + r] : rsc[PIPE ? 0 : i][PIPE ? 0 : q];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rs[e] + gt[e] * v[e];
-        }
-        if (relu) {
+          for (int e = 0; e < 4; ++e) v[e] += bv[e];
+          if constexpr (EPI == V2A_EPI_SIGMOID) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if constexpr (sizeof(OutT) == 2) {
-          bf16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
-          *reinterpret_cast<bf16x4*>(out + o_out + n) = o;
+            for (int e = 0; e < 4; ++e) v[e] = sigmoid_f(v[e]);
+          }
           if constexpr (EPI == V2A_EPI_GELU) {
-            if (p.out_split) {       // bf16x3 mode: the lo plane, N columns after the hi plane (the next GEMM's split operand)
-              bf16x4 lo;
+            // fp32 output: exact erff (fp32 parity of CLIPMLP); hi | lo planes: Abramowitz-Stegun erf (|error| <= 1.5e-7, below the
+            // 2^-17 the planes keep), as the GEGLU epilogue's split form
 #pragma unroll
-              for (int e = 0; e < 4; ++e) lo[e] = (bf16_t)(v[e] - (float)o[e]);
-              *reinterpret_cast<bf16x4*>(out + o_out + p.N + n) = lo;
+            for (int e = 0; e < 4; ++e) v[e] = sizeof(OutT) == 2 ? gelu_fast_f(v[e]) : gelu_erf_f(v[e]);
+          }
+          if constexpr (EPI == V2A_EPI_STORE) {
+            // interleaved RoPE (A6): columns (n, n+1) and (n+2, n+3) are pairs (n & 63) / 2 and +1 of this head
+            if constexpr (PF) {
+              if (p.rope && n < p.rope_cols) rope_rotate4(v, pf.cs[i][q]);
+            } else {
+              if (rope_on) rope_rotate4(v, q_a[i & 1][q]);
             }
           }
-        } else {
-          *reinterpret_cast<f32x4*>(out + o_out + n) = v;
-          if (out2) {
-            // folded RMSNorm, producer side: the shadow carries the norm's gamma (the consumer applies 1 / rms per row) and
-            // the row's sum of squares is left per 32 columns (8 lanes x 4 columns: a butterfly inside the lane octet)
-            f32x4 gm = m >= p.nsw_row ? gmB : gmA;
-            if (p.ngam && p.ngbs) gm = *reinterpret_cast<const f32x4*>(step_vec(p.ngam, p.step, p.ngss, p.ngbs, m / p.rpb) + (m >= p.nsw_row ? p.nsw_off : 0) + n);
+          if constexpr (RESF) {
+            f32x4 rs, gt = {1.f, 1.f, 1.f, 1.f};
+            if constexpr (PF) {
+              rs = pf.rs[i][q];
+              if constexpr (EPI == V2A_EPI_GATE_RESID) gt = pf.gt[i][q];
+            } else {
+              rs = q_a[i & 1][q];
+              if constexpr (EPI == V2A_EPI_GATE_RESID) {
+                gt = gate_two && m >= m_sw ? gt2 : gt1;
+                if (gate_row) {
+                  int pos, nb;
+                  row_pos(p0, m - m_base, rpb, true, pos, nb);
+                  gt = *reinterpret_cast<const f32x4*>(gate_b + (int64_t)(b0 + nb) * p.gbs + n);
+                  asm volatile("" : "+v"(gt));      // a use inside the branch: the wait for this load stays in here, off the path that does not load
+                }
+              }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = rs[e] + gt[e] * v[e];
+          }
+          if (relu) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+          }
+          if constexpr (sizeof(OutT) == 2) {
             bf16x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)(v[e] * gm[e]);
-            *reinterpret_cast<bf16x4*>(out2 + o_out2 + n) = o;
-            if (p.out2_split) {      // bf16x3 mode: the lo plane of the (gamma-scaled) row, N columns further
-              bf16x4 lo;
+            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
+            *reinterpret_cast<bf16x4*>(out + o_out + n) = o;
+            if constexpr (EPI == V2A_EPI_GELU) {
+              if (p.out_split) {       // bf16x3 mode: the lo plane, N columns after the hi plane (the next GEMM's split operand)
+                bf16x4 lo;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) lo[e] = (bf16_t)(v[e] * gm[e] - (float)o[e]);
-              *reinterpret_cast<bf16x4*>(out2 + o_out2 + p.out2_lo + n) = lo;
+                for (int e = 0; e < 4; ++e) lo[e] = (bf16_t)(v[e] - (float)o[e]);
+                *reinterpret_cast<bf16x4*>(out + o_out + N + n) = lo;
+              }
             }
-            if (p.ssq) {
-              const float ss = octet_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
-              if ((lane & 7) == 0) p.ssq[(int64_t)m * p.ssq_ld + (n >> 5)] = ss;
+          } else {
+            *reinterpret_cast<f32x4*>(out + o_out + n) = v;
+            if (out2) {
+              // folded RMSNorm, producer side: the shadow carries the norm's gamma (the consumer applies 1 / rms per row) and
+              // the row's sum of squares is left per 32 columns (8 lanes x 4 columns: a butterfly inside the lane octet)
+              f32x4 gm = m >= p.nsw_row ? gmB : gmA;
+              if constexpr (GAMF) {
+                if constexpr (PIPE) {
+                  if (gam_two && m >= m_sw) gm = m >= p.nsw_row ? gmD : gmC;
+                }
+                if (gam_row) {       // per-batch gamma, by row
+                  int pos, nb = 0;
+                  if constexpr (PIPE) row_pos(p0, m - m_base, rpb, true, pos, nb);
+                  gm = *reinterpret_cast<const f32x4*>(ngam_b + (int64_t)(PIPE ? b0 + nb : m / rpb) * p.ngbs + (m >= p.nsw_row ? p.nsw_off : 0) + n);
+                  if constexpr (PIPE) asm volatile("" : "+v"(gm));      // (as for the gate)
+                }
+              }
+              bf16x4 o;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) o[e] = (bf16_t)(v[e] * gm[e]);
+              *reinterpret_cast<bf16x4*>(out2 + o_out2 + n) = o;
+              if (p.out2_split) {      // bf16x3 mode: the lo plane of the (gamma-scaled) row, N columns further
+                bf16x4 lo;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) lo[e] = (bf16_t)(v[e] * gm[e] - (float)o[e]);
+                *reinterpret_cast<bf16x4*>(out2 + o_out2 + p.out2_lo + n) = lo;
+              }
+              if (p.ssq) {
+                const float ss = octet_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+                if ((lane & 7) == 0) p.ssq[(int64_t)m * p.ssq_ld + (n >> 5)] = ss;
+              }
             }
           }
+          if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
+  }
+}
+
+template <int EPI, typename OutT, int TM, int TN, int WM, int WN, bool PF>
+__device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, f32x4 (&acc)[TM][TN], float* tile /* wave-private, 16 x (WN+4) floats */,
+                                                  int m_base, int n_base, int lane, const EpiPrefetch<EPI, TM, WN, PF>& pf,
+                                                  const float* rs_row = nullptr /* LDS: row scales of this wave's rows, or null */) {
+  if constexpr (epi_pipelined<EPI, PF>()) {
+    // wave-uniform: the wave tile lies wholly inside the problem, rows are dense
+    if (__builtin_amdgcn_readfirstlane((int)(m_base + WM <= p.M && n_base + WN <= p.N)) && p.o_rowoff == nullptr)
+      gemm_epilogue_lds_impl<EPI, OutT, TM, TN, WM, WN, PF, true>(p, acc, tile, m_base, n_base, lane, pf, rs_row);
+    else
+      gemm_epilogue_lds_impl<EPI, OutT, TM, TN, WM, WN, PF, false>(p, acc, tile, m_base, n_base, lane, pf, rs_row);
+  } else {
+    gemm_epilogue_lds_impl<EPI, OutT, TM, TN, WM, WN, PF, false>(p, acc, tile, m_base, n_base, lane, pf, rs_row);
   }
 }
 
