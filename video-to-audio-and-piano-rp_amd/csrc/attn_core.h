@@ -151,7 +151,8 @@ __device__ __forceinline__ bool attn_merge_key_groups(float* xch, int grp, int t
   const float* src = xch + tid;
   const float m2 = src[0], l2 = src[256];
   const float mn = fmaxf(m, m2);
-  const float a1 = __builtin_amdgcn_exp2f(m - mn), a2 = (m2 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
+  // a group without a key (its tiles all at or beyond kv_len; both groups when kv_len is 0) has m = -inf: weight 0, not 2^(-inf + inf)
+  const float a1 = (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mn), a2 = (m2 == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m2 - mn);
   l = l * a1 + l2 * a2;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -185,12 +186,15 @@ __device__ __forceinline__ void attn_store(T* op, const f32x4 (&o)[4], float f) 
 __device__ __forceinline__ void attn_store_split(bf16_t* op, int lo_off, const f32x4 (&o)[4], float f) {
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
-    const f32x4 v = o[dt] * f;
     bf16x4 hi, lo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      hi[e] = (bf16_t)v[e];
-      lo[e] = (bf16_t)(v[e] - (float)hi[e]);
+      // the split of the fp32 value attn_store would have stored: without the barrier -ffp-contract=fast fuses the multiplication
+      // by f into the subtraction, and lo then splits the unrounded product (it differs where v - hi is a bf16 rounding tie)
+      float v = o[dt][e] * f;
+      asm volatile("" : "+v"(v));
+      hi[e] = (bf16_t)v;
+      lo[e] = (bf16_t)(v - (float)hi[e]);
     }
     *reinterpret_cast<bf16x4*>(op + 16 * dt) = hi;
     *reinterpret_cast<bf16x4*>(op + lo_off + 16 * dt) = lo;
