@@ -593,6 +593,32 @@ int v2a_piano_resize_h(const uint8_t* frames, int32_t F, int32_t H, int32_t W, c
 int v2a_piano_resize_v(const uint8_t* tmp, int32_t n, int32_t rows, int32_t ldt, int32_t Ho, int32_t Wo, const int32_t* bounds,
                        const int32_t* coef, int32_t ksize, const float* lut, float* out, v2a_stream_t stream);
 
+/* =======================================================================================
+ * Encodec residual vector quantizer: the part of `EncodecModel.encode` / `.decode` between the encoder (v2a_encodec_stage0 and the
+ * GEMM stack) and the vocoder.  Additive to ABI 8.
+ * ===================================================================================== */
+
+/* Latents -> codes, all n_q stages in one launch.  With r_0 = x[frame] (D = 128 floats), for s = 0 .. n_q - 1:
+ *   codes[s][frame] = arg-max_j (2 r_s . e^s_j - norms[s][j])      (lowest j among equal scores)
+ *   r_{s+1}         = r_s - e^s_{codes[s][frame]}                  (fp32, one rounding per element and stage)
+ * The products are exact fp32 (fp32-input MFMA, one rounding per product, accumulated in a fixed order that does not depend on the
+ * other frames of the launch).  x is read in place as x[b * batch_stride + t * frame_stride + c * chan_stride] (strides in floats,
+ * >= 0), b < B, t < T: both (b, 128, t) and (b, t, 128) tensors.  codebooks (S, Kc, D) fp32 contiguous, 16-byte aligned, of which
+ * the first n_q <= S stages are used; norms (S, Kc) = |e^s_j|^2, precomputed by the caller; D == 128, Kc a multiple of 512;
+ * codes (n_q, B * T) int64, frame = b * T + t; B * T <= 2^30.
+ * Replaces: `EncodecEuclideanCodebook.quantize` (the distance matrix and its arg-max) inside `EncodecResidualVectorQuantizer.encode`
+ * (the stage loop with `residual = residual - quantized`), transformers/models/encodec/modeling_encodec.py. */
+int v2a_encodec_rvq_encode(const float* x, int64_t batch_stride, int64_t frame_stride, int64_t chan_stride, int32_t B, int32_t T,
+                           const float* codebooks, const float* norms, int32_t S, int32_t Kc, int32_t D, int32_t n_q, int64_t* codes,
+                           v2a_stream_t stream);
+/* Codes -> latents: out[frame] = ((0 + e^0[codes[0][frame]]) + e^1[codes[1][frame]]) + ... in fp32, in stage order, written through
+ * the same three strides.  codes (n_q, B * T) int64, n_q <= S; the CALLER guarantees 0 <= codes < Kc (an index outside is clamped
+ * into the codebook, never followed).  D == 128.
+ * Replaces: `EncodecResidualVectorQuantizer.decode` (`quantized_out = quantized_out + layer.decode(indices)`) with
+ * `EncodecEuclideanCodebook.decode` (the embedding lookup), transformers/models/encodec/modeling_encodec.py. */
+int v2a_encodec_rvq_decode(const int64_t* codes, int32_t n_q, int32_t B, int32_t T, const float* codebooks, int32_t S, int32_t Kc, int32_t D,
+                           float* out, int64_t batch_stride, int64_t frame_stride, int64_t chan_stride, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

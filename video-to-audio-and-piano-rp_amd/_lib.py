@@ -114,6 +114,7 @@ EXPORTS = [
     "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2", "v2a_t5_rmsnorm", "v2a_t5_attention", "v2a_gemm_skinny_f32",
     "v2a_clip_resize_h", "v2a_clip_resize_v", "v2a_clip_embed_init", "v2a_clip_layernorm", "v2a_clip_attention",
     "v2a_elu_pad_lr", "v2a_encodec_stage0", "v2a_piano_resize_h", "v2a_piano_resize_v",
+    "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode",
 ]
 
 
@@ -177,6 +178,8 @@ def _declare(lib):
     lib.v2a_encodec_stage0.argtypes = [vp, vp, vp, i64, vp]
     lib.v2a_piano_resize_h.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp]
     lib.v2a_piano_resize_v.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    lib.v2a_encodec_rvq_encode.argtypes = [vp, i64, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.v2a_encodec_rvq_decode.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, i64, i64, i64, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -600,6 +603,22 @@ ENCODEC_STAGE0_PARAMS = 3376     # floats of the parameter block of v2a_encodec_
 def encodec_stage0(wave, params, out, *, n):
     _launch("encodec_stage0", 2.0 * n * 3744, 4.0 * n * 33,
             lambda: lib().v2a_encodec_stage0(wave.data_ptr(), params.data_ptr(), out.data_ptr(), n, stream_ptr()))
+
+
+def encodec_rvq_encode(x, strides, codebooks, norms, codes, *, B, T, n_q):
+    """x: fp32 tensor read as x[b * strides[0] + t * strides[1] + c * strides[2]]; codebooks (S, Kc, D), norms (S, Kc); codes (n_q, B * T) int64."""
+    S, Kc, D = codebooks.shape
+    _launch("encodec_rvq_encode", 2.0 * B * T * n_q * Kc * D, 4.0 * (B * T * D + n_q * Kc * D * -(-B * T // 16)) + 8.0 * n_q * B * T,
+            lambda: lib().v2a_encodec_rvq_encode(x.data_ptr(), strides[0], strides[1], strides[2], B, T, codebooks.data_ptr(), norms.data_ptr(),
+                                                 S, Kc, D, n_q, codes.data_ptr(), stream_ptr()))
+
+
+def encodec_rvq_decode(codes, codebooks, out, strides, *, B, T, n_q):
+    """codes (n_q, B * T) int64 -> out written as out[b * strides[0] + t * strides[1] + c * strides[2]]."""
+    S, Kc, D = codebooks.shape
+    _launch("encodec_rvq_decode", 1.0 * B * T * n_q * D, B * T * (4.0 * D * (n_q + 1) + 8.0 * n_q),
+            lambda: lib().v2a_encodec_rvq_decode(codes.data_ptr(), n_q, B, T, codebooks.data_ptr(), S, Kc, D, out.data_ptr(),
+                                                 strides[0], strides[1], strides[2], stream_ptr()))
 
 
 def lstm_layer(gates_x, w_hh, h, workspace, *, T, H, resid=None, y=None):

@@ -24,6 +24,10 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
   --audio-prompt-seconds S   (with --encodec, checkpoint built with if_cond_proj_in) the first S seconds of `<video>.wav` (24 kHz) are
                      encoded by the HIP Encodec encoder and given to the sampler as the audio prompt: `cond` = the raw waves,
                      `lens` = ceil(24000 S / 320) frames, which come back unchanged in front of the generated ones (x3:2196-2231).
+  --codes KBPS       (with --encodec, whose state dict holds the quantizer) also write `<name>.codes.npy`: int16 (n_q, n) Encodec codes
+                     of the clip's valid frames at 1.5 / 3 / 6 / 12 / 24 kbps (2 / 4 / 8 / 16 / 32 codebooks of 10 bits at 75 Hz), what
+                     `EncodecModel.encode(...).audio_codes[0][0]` holds and any Encodec decoder reads.  The `.wav` is still decoded from
+                     the continuous latents.
 The moviepy mux of audio and video stays outside (out of scope).
 """
 from __future__ import annotations
@@ -156,6 +160,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--encodec", default=None, help="state dict (.pt) of the Encodec model / decoder: also write <name>.wav")
     ap.add_argument("--audio-prompt-seconds", type=float, default=0.0, help="with --encodec and a checkpoint built with if_cond_proj_in: "
                     "prompt every clip with the first S seconds of <video>.wav, encoded by the HIP Encodec encoder")
+    ap.add_argument("--codes", type=float, default=None, choices=[1.5, 3.0, 6.0, 12.0, 24.0], metavar="KBPS",
+                    help="with --encodec: also write <name>.codes.npy, the int16 (n_q, n) Encodec codes of the clip at this bandwidth")
     return ap
 
 
@@ -164,6 +170,9 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.audio_prompt_seconds < 0 or (a.audio_prompt_seconds > 0 and not a.encodec):
         ap.error("--audio-prompt-seconds needs a positive S and --encodec (the state dict that holds the encoder)")
+
+    if a.codes is not None and not a.encodec:
+        ap.error("--codes needs --encodec (the state dict that holds the quantizer's codebooks)")
 
     import torch.distributed as dist
     from . import E2TTS, collate_clips, gather_latents, shard_range
@@ -222,7 +231,10 @@ def main(argv=None):
     vocoder = None
     if a.encodec and rank == 0:
         from .encodec import EncodecDecoder
-        vocoder = EncodecDecoder(torch.load(a.encodec, map_location="cpu"), torch.device("cuda", local))
+        esd = torch.load(a.encodec, map_location="cpu")
+        vocoder = EncodecDecoder(esd, torch.device("cuda", local))
+        if a.codes is not None:
+            model.load_audio_quantizer(esd)
     items = read_scp(a.test_scp, a.start, a.end)
     os.makedirs(a.out_dir, exist_ok=True)
     gen = torch.Generator().manual_seed(a.seed)
@@ -262,6 +274,9 @@ def main(argv=None):
                     n = min(a.frames, int(load_clip_cache(feature_cache_path(vp, a.video_encoder))[1] * 24000) // 320) if a.frames > 0 else one.shape[0]
                     wav = vocoder.decode(one[:n].t()[None].float())[0]                     # predict.py:277-278
                     wavfile.write(os.path.join(a.out_dir, name + ".wav"), 24000, wav.cpu().numpy())
+                    if a.codes is not None:
+                        codes = model.latents_to_codes(one[None, :n].float(), a.codes)[0]          # (n_q, n)
+                        np.save(os.path.join(a.out_dir, name + ".codes.npy"), codes.cpu().numpy().astype(np.int16))
     if world > 1:
         dist.destroy_process_group()
     return written

@@ -214,6 +214,7 @@ class E2TTS:
         self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
         self._clip = None                         # optional image encoder (load_image_encoder: CLIP x3:1423-1425 or DINOv2 x3:1432-1433)
         self._audio_encoder = None                # optional Encodec encoder behind a raw-wave cond (load_audio_encoder, x3:1350)
+        self._audio_quantizer = None              # optional Encodec quantizer behind an integer cond of codes (load_audio_quantizer)
         self._piano_pre = None                    # piano-frame preprocessor of this device (piano_frame_preprocessor, x3:1877-1891)
         L.lib()  # no library -> no sampler
 
@@ -368,6 +369,28 @@ class E2TTS:
         self.mel_spec = lambda wave: enc.encoder(wave.unsqueeze(1))
         return enc
 
+    def load_audio_quantizer(self, src):
+        """The Encodec quantizer behind an integer `cond` of codes (b, n_q, n) -- the layout of `EncodecModel.encode`'s audio_codes[0] --
+        and behind `latents_to_codes`: an `EncodecQuantizer`, or an EncodecModel / quantizer state dict."""
+        from .encodec import EncodecQuantizer
+        if isinstance(src, EncodecQuantizer):
+            q = src
+        elif isinstance(src, dict):
+            q = EncodecQuantizer(src, self._device)
+        else:
+            raise TypeError(f"load_audio_quantizer: an EncodecQuantizer or a state dict, got {type(src).__name__}")
+        if q.dim != self.num_channels:
+            raise ValueError(f"load_audio_quantizer: codebooks of dimension {q.dim}, the model has {self.num_channels} latent channels")
+        self._audio_quantizer = q
+        return q
+
+    def latents_to_codes(self, latents, bandwidth=None):
+        """Sampler output (b, n, C) -> Encodec codes (b, n_q, n) int64 at `bandwidth` kbps (None: every codebook), the layout of
+        `EncodecModel.encode`'s audio_codes[0], which `sample(cond=codes)` and any Encodec decoder take."""
+        if self._audio_quantizer is None:
+            raise NotImplementedError("latents_to_codes needs the Encodec quantizer: load_audio_quantizer(state_dict)")
+        return self._audio_quantizer.encode(latents, bandwidth, channels_last=True).transpose(0, 1)
+
     def load_image_encoder(self, src, **kw):
         """The image encoder behind `video_frames=` and uncached `video_paths`.  video_encoder="clip_vit" (x3:1423-1425, 1714,
         1733-1735): a `CLIPImageEncoder`, a local HF directory (IP-Adapter sdxl_models/image_encoder) or a state dict
@@ -517,6 +540,8 @@ class E2TTS:
         device.  With lens[0] != duration[0] it is the audio prompt of the infilling branch (x3:2196-2231, 2260-2261; needs
         if_cond_proj_in=True): zero-padded to the longest duration, masked to lens, added through cond_proj_in at every
         evaluation (dropped in the null pass), and returned unchanged in the first lens[b] frames.
+        An integer `cond` (b, n_q, n) is that prompt as Encodec codes (`EncodecModel.encode`'s audio_codes[0]): the quantizer of
+        load_audio_quantizer decodes it to (b, n, C) first.
         `trajectory_out`: optional list that receives a device copy of y at every grid point (the `trajectory` of
         x3:2255, of which the reference keeps only [-1]); test aid, adds a copy per step.
         `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) per clip (or None), encoded by the CLIP image encoder
@@ -527,6 +552,11 @@ class E2TTS:
         builds the grey (b, 1, t, 100, 900) stack on the GPU (frame caches next to `video_paths` honoured and written; without
         `video_paths` nothing is written) and hands it to `encode_frames` without leaving the device."""
         self.eval()
+        if cond.ndim == 3 and not (cond.is_floating_point() or cond.is_complex()):  # Encodec codes (b, n_q, n): the prompt, quantized
+            if self._audio_quantizer is None:
+                raise NotImplementedError("an integer `cond` is a prompt of Encodec codes (b, n_q, n) and needs the quantizer: "
+                                          "load_audio_quantizer(state_dict)")
+            cond = self._audio_quantizer.decode(cond.transpose(0, 1), channels_last=True).to(cond.device)      # (b, n, C)
         if cond.ndim == 2:                                                          # raw wave (x3:2157-2160)
             if self.mel_spec is None:
                 raise NotImplementedError("raw-wave `cond` needs mel_spec_module, which the shipped config does not set "

@@ -20,6 +20,11 @@ whose A rows overlap with lda = r*C (K = k*C, M = ceil(T/r)) over a buffer that 
 reflects k - r samples in front and, where the length is not a multiple of r, up to r - 1 behind (`encoder_padding_plan`).  The
 wide, thin end -- stem + the C = 32 block over 240 000 time steps -- is one fused VALU kernel (`v2a_encodec_stage0`);
 `fused_stem=False` keeps the generic composition of it reachable for A/B runs.
+
+`EncodecQuantizer` is the third part of `EncodecModel`, the residual vector quantizer between the two (`EncodecModel.encode` / `.decode`):
+`v2a_encodec_rvq_encode` searches every stage's codebook in one launch (exact-fp32 MFMA scores, the residual in registers) and
+`v2a_encodec_rvq_decode` sums the chosen codewords in the library's order; `rvq_encode_torch` / `rvq_decode_torch` restate the library for
+host tests.
 """
 from __future__ import annotations
 
@@ -399,3 +404,125 @@ class EncodecEncoder:
         return self.encoder(waveform[:1].unsqueeze(0))
 
     __call__ = forward
+
+
+# ---- residual vector quantizer -----------------------------------------------------------------------------------------
+FRAME_RATE = 75                                     # EncodecConfig().frame_rate: 24 000 / 320
+RVQ_CODEBOOK_MULTIPLE = 512                         # v2a_encodec_rvq_encode: 8 waves x 64 codewords per pass
+
+
+def quantizer_codebooks(state_dict) -> torch.Tensor:
+    """(S, codebook_size, dim) fp32 from an `EncodecModel` state dict (`quantizer.layers.{i}.codebook.embed`) or the quantizer's own
+    (`layers.{i}.codebook.embed`); `cluster_size`, `embed_avg` and `inited` (training statistics) are not read."""
+    sd = state_dict
+    if any(k.startswith("quantizer.layers.") for k in sd):
+        sd = {k[len("quantizer."):]: v for k, v in sd.items() if k.startswith("quantizer.")}
+    books = []
+    while f"layers.{len(books)}.codebook.embed" in sd:
+        books.append(sd[f"layers.{len(books)}.codebook.embed"].detach().cpu().float())
+    if not books:
+        raise KeyError("EncodecQuantizer: no `layers.0.codebook.embed` (or `quantizer.layers.0.codebook.embed`) in the state dict")
+    if any(b.ndim != 2 or b.shape != books[0].shape for b in books):
+        raise ValueError(f"EncodecQuantizer: codebooks of different shapes: {sorted({tuple(b.shape) for b in books})}")
+    return torch.stack(books).contiguous()
+
+
+def num_quantizers_for_bandwidth(bandwidth, codebook_size: int, num_quantizers: int, frame_rate: int = FRAME_RATE) -> int:
+    """`EncodecResidualVectorQuantizer.get_num_quantizers_for_bandwidth`: kbps -> stages; None or 0 means all of them.  As the
+    library's, the count is not capped at `num_quantizers`: slicing the layer list caps it there, the callers below do."""
+    if bandwidth is None or not bandwidth > 0.0:
+        return num_quantizers
+    return int(max(1, math.floor(bandwidth * 1000 / (math.log2(codebook_size) * frame_rate))))
+
+
+def rvq_encode_torch(codebooks, x, n_q=None):
+    """Plain-torch restatement of `EncodecResidualVectorQuantizer.encode`, operation for operation, in the dtype of `x`: codebooks
+    (S, Kc, D), x (b, D, t) -> int64 (n_q, b, t).  For host tests: the device path is `EncodecQuantizer.encode`."""
+    n_q = codebooks.shape[0] if n_q is None else n_q
+    residual = x
+    out = []
+    for s in range(n_q):
+        embed = codebooks[s].to(x.dtype)
+        h = residual.permute(0, 2, 1)
+        flat = h.reshape(-1, h.shape[-1])
+        et = embed.t()
+        dist = -(flat.pow(2).sum(1, keepdim=True) - 2 * flat @ et + et.pow(2).sum(0, keepdim=True))
+        ind = dist.max(dim=-1).indices.view(*h.shape[:-1])
+        residual = residual - F.embedding(ind, embed).permute(0, 2, 1)
+        out.append(ind)
+    return torch.stack(out)
+
+
+def rvq_decode_torch(codebooks, codes, dtype=torch.float32):
+    """Plain-torch restatement of `EncodecResidualVectorQuantizer.decode`: codes (n_q, b, t) -> (b, D, t), the stages summed in order
+    from 0.0 in `dtype`."""
+    out = torch.full((), 0.0, dtype=dtype)
+    for s, ind in enumerate(codes):
+        out = out + F.embedding(ind.long(), codebooks[s].to(dtype)).permute(0, 2, 1)
+    return out
+
+
+class EncodecQuantizer:
+    """HIP mirror of `EncodecModel.quantizer` (`EncodecResidualVectorQuantizer`): `encode` is the library's `quantizer.encode`
+    (latents -> codes), `decode` its `quantizer.decode` (codes -> latents).
+
+    state_dict: an `EncodecModel` state dict (keys `quantizer.layers.{i}.codebook.embed`) or the quantizer's own."""
+
+    def __init__(self, state_dict, device="cuda:0"):
+        cb = quantizer_codebooks(state_dict)
+        self.num_quantizers, self.codebook_size, self.dim = cb.shape
+        if self.dim != HIDDEN or self.codebook_size % RVQ_CODEBOOK_MULTIPLE:
+            raise ValueError(f"EncodecQuantizer: codebooks of {self.codebook_size} x {self.dim}; the kernel takes dimension {HIDDEN} and "
+                             f"a codebook size that is a multiple of {RVQ_CODEBOOK_MULTIPLE}")
+        L.lib()                                                   # fail loudly without the HIP library
+        self.dev = dev = torch.device(device)
+        self.codebooks = cb.to(dev)
+        self.norms = cb.double().pow(2).sum(-1).float().to(dev)   # |e_j|^2, summed in float64 and rounded once
+
+    def num_quantizers_for_bandwidth(self, bandwidth=None) -> int:
+        return min(self.num_quantizers, num_quantizers_for_bandwidth(bandwidth, self.codebook_size, self.num_quantizers))
+
+    def _frames(self, shape, strides, channels_last, what):
+        """(B, T, (batch, frame, channel) strides) of a 3-D tensor in either layout; the channel axis must be the codebook dimension."""
+        if len(shape) != 3 or shape[2 if channels_last else 1] != self.dim:
+            raise ValueError(f"EncodecQuantizer.{what}: expected {'(b, t, %d)' % self.dim if channels_last else '(b, %d, t)' % self.dim}, "
+                             f"got {tuple(shape)}")
+        b, c, t = (0, 2, 1) if channels_last else (0, 1, 2)
+        return shape[b], shape[t], (strides[b], strides[t], strides[c])
+
+    @torch.no_grad()
+    def encode(self, x, bandwidth=None, channels_last=False):
+        """x float32 (b, 128, t) -- or (b, t, 128) with channels_last -- read in place through its strides -> int64 (n_q, b, t) on the
+        device, `EncodecResidualVectorQuantizer.encode(x, bandwidth)`; `EncodecModel.encode`'s audio_codes[0] is its transpose(0, 1)."""
+        if not (torch.is_tensor(x) and x.is_floating_point()):
+            raise ValueError("EncodecQuantizer.encode: a float tensor of latents is expected")
+        B, T, _ = self._frames(x.shape, x.stride(), channels_last, "encode")
+        n_q = self.num_quantizers_for_bandwidth(bandwidth)
+        codes = torch.empty(n_q, B, T, dtype=torch.int64, device=self.dev)
+        if B * T == 0:
+            return codes
+        x = x.to(self.dev, torch.float32)
+        if any(s < 0 for s in x.stride()):
+            x = x.contiguous()
+        _, _, strides = self._frames(x.shape, x.stride(), channels_last, "encode")
+        L.encodec_rvq_encode(x, strides, self.codebooks, self.norms, codes, B=B, T=T, n_q=n_q)
+        return codes
+
+    @torch.no_grad()
+    def decode(self, codes, channels_last=False):
+        """codes integer (n_q, b, t), the first n_q stages -> float32 (b, 128, t), or (b, t, 128) with channels_last:
+        `EncodecResidualVectorQuantizer.decode(codes)`.  An index outside [0, codebook_size) is a ValueError before any launch."""
+        if not torch.is_tensor(codes) or codes.is_floating_point() or codes.is_complex() or codes.dtype == torch.bool or codes.ndim != 3:
+            raise ValueError("EncodecQuantizer.decode: an integer tensor (n_q, b, t) is expected")
+        n_q, B, T = codes.shape
+        if not 1 <= n_q <= self.num_quantizers:
+            raise ValueError(f"EncodecQuantizer.decode: {n_q} stages of codes, the quantizer has {self.num_quantizers}")
+        if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) >= self.codebook_size):
+            raise ValueError(f"EncodecQuantizer.decode: codes outside [0, {self.codebook_size})")
+        out = torch.empty((B, T, self.dim) if channels_last else (B, self.dim, T), dtype=torch.float32, device=self.dev)
+        if B * T == 0:
+            return out
+        codes = codes.to(self.dev, torch.int64).contiguous()
+        _, _, strides = self._frames(out.shape, out.stride(), channels_last, "decode")
+        L.encodec_rvq_decode(codes, self.codebooks, out, strides, B=B, T=T, n_q=n_q)
+        return out

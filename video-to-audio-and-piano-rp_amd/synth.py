@@ -165,6 +165,42 @@ def random_encodec_encoder_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
     return sd
 
 
+def random_encodec_quantizer_state_dict(seed: int = 0, num_quantizers: int = 32, codebook_size: int = 1024, dim: int = 128,
+                                        decay: float = 0.85) -> dict[str, torch.Tensor]:
+    """Seeded codebooks in the key layout of `EncodecModel(EncodecConfig(target_bandwidths=[..., 24.0])).quantizer.state_dict()`:
+    `layers.{s}.codebook.embed` (codebook_size, dim) standard normal scaled by decay^s -- each stage of a trained residual quantizer
+    codes what the stages before it left, so its codewords are shorter -- and the training statistics `inited`, `cluster_size`,
+    `embed_avg` beside it, which inference does not read.  numpy RandomState stream: same tensors on any machine."""
+    import numpy as np
+
+    rs = np.random.RandomState(seed)
+    sd = {}
+    for s in range(num_quantizers):
+        e = torch.from_numpy((rs.standard_normal((codebook_size, dim)) * decay ** s).astype(np.float32))
+        p = f"layers.{s}.codebook."
+        sd[p + "inited"] = torch.ones(1)
+        sd[p + "cluster_size"] = torch.zeros(codebook_size)
+        sd[p + "embed"] = e
+        sd[p + "embed_avg"] = e.clone()
+    return sd
+
+
+def synthetic_encodec_latents(codebooks: torch.Tensor, b: int, t: int, seed: int = 0, structured: bool = True) -> torch.Tensor:
+    """Seeded (b, dim, t) fp32 latents for the quantizer.  structured: one random codeword per stage, summed, plus noise of 30 % of
+    that sum's RMS -- what an encoder trained with the quantizer emits; otherwise standard normal scaled to the same RMS."""
+    import numpy as np
+
+    rs = np.random.RandomState(seed)
+    S, Kc, D = codebooks.shape
+    cb = codebooks.double().numpy()
+    idx = rs.randint(0, Kc, (S, b * t))
+    x = sum(cb[s][idx[s]] for s in range(S))                          # (b * t, D)
+    rms = float(np.sqrt((x ** 2).mean()))
+    noise = rs.standard_normal((b * t, D))
+    x = x + 0.3 * rms * noise if structured else rms * noise
+    return torch.from_numpy(x.reshape(b, t, D).transpose(0, 2, 1).astype(np.float32).copy())
+
+
 def synthetic_wave(n: int, seed: int = 0, rate: int = 24000) -> torch.Tensor:
     """A seeded (n,) fp32 test signal: 12 sines at 60 - 6000 Hz with random amplitude and phase plus 0.05 white noise, scaled to
     peak <= 1 (numpy RandomState: the same samples on any machine)."""
