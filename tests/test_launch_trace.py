@@ -1,11 +1,12 @@
-"""Launch-trace guard of the DiT and Video2Roll engines: what the GPU is asked to do, pinned on the CPU.
+"""Launch-trace guard of the DiT, Video2Roll and image-encoder (CLIP, DINOv2) engines: what the GPU is asked to do, pinned on the CPU.
 
 The real Python engines run on device="cpu" against a fake libv2a_cfm that records every entry-point call: its name, its
 scalars, every ctypes.Structure argument field by field, and the (key, flops, bytes) that `_lib._launch` hands to a
 profiler (bench.py's roofline accounting).  Device pointers are written as (allocation index, byte offset, allocation size):
 allocations are the storages reachable from the engine (plans, packed weights, Video2Roll maps and tables) and the case's own
 inputs, numbered in the order they first appear in the trace; any other pointer is "tmp" (the CPU allocator reuses freed
-addresses, so temporaries have no stable identity).  Weights are zeros: nothing is computed.
+addresses, so temporaries have no stable identity).  Nothing is computed: the DiT and Video2Roll weights are zeros, the image
+encoders' are the seeded ones of synth.py (their host-side weight preparation runs).
 
 tests/golden/launch_trace.json.gz holds the trace of every case below and the tile-hint decisions of the DiT engine.  A change
 that means to alter the launch sequence regenerates it with `python tests/test_launch_trace.py --write [PATH]` and says so."""
@@ -25,7 +26,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import v2a_amd  # noqa: E402
-from v2a_amd import _lib as L  # noqa: E402
+from v2a_amd import _lib as L, synth  # noqa: E402
+from v2a_amd.clip import CLIPImageEncoder  # noqa: E402
+from v2a_amd.dinov2 import DINOv2ImageEncoder  # noqa: E402
 from v2a_amd.dit import DiTConfig, DiTEngine  # noqa: E402
 from v2a_amd.video2roll import Video2RollEngine, expected_state_dict_shapes as v2r_shapes  # noqa: E402
 
@@ -209,7 +212,51 @@ def _v2r_case(mode, t=5, chunk=None):
     return lambda: _traced(run)
 
 
+# the small configs of test_clip_host.py (dp = 256 > d = 208 and kp = 640 > 588: both K paddings live) and test_dinov2_host.py
+CLIP_SMALL = dict(hidden_size=208, intermediate_size=832, num_hidden_layers=2, num_attention_heads=2, image_size=56, patch_size=14,
+                  projection_dim=128, layer_norm_eps=1e-5, hidden_act="gelu", num_channels=3)
+DINOV2_SMALL = dict(hidden_size=192, num_hidden_layers=2, num_attention_heads=3, mlp_ratio=4, image_size=70, patch_size=14,
+                    layer_norm_eps=1e-6, use_swiglu_ffn=True, num_channels=3)
+
+
+def _vit_case(kind, mode, n, h, w, *, cfg=None, ctor=None, attrs=None, crop=False, moved=False):
+    """One image encoder, chunk 2, over n seeded h x w frames: enc(frames), so n = 3 runs a chunk of 2 and a chunk of 1 (the
+    buffers are rebuilt for the second size).  crop: one encode_chunk call with a tap and a uint8 crop buffer instead.  moved:
+    enc.to("cpu") and a second enc(frames), for which plans and buffers are rebuilt."""
+    def run(roots):
+        if kind == "clip":
+            c = dict(CLIP_SMALL, **(cfg or {}))
+            enc = CLIPImageEncoder(synth.random_clip_vision_state_dict(c, 3), "cpu", config=c, compute=mode, chunk=2)
+        else:
+            c = dict(DINOV2_SMALL, **(cfg or {}))
+            enc = DINOv2ImageEncoder(synth.random_dinov2_state_dict(c, 3), "cpu", config=c, compute=mode, chunk=2,
+                                     **{**dict(resize=64, crop=56), **(ctor or {})})
+        for k, v in (attrs or {}).items():
+            setattr(enc, k, v)
+        fr = torch.from_numpy(synth.synthetic_video_frames(n, h, w, 1))
+        roots += [enc, fr]
+        if crop:
+            buf = torch.zeros(n, enc.S, enc.S, 3, dtype=torch.uint8)
+            roots.append(buf)
+            enc.encode_chunk(fr, taps={1: None}, crop=buf)
+            return
+        enc(fr)
+        if moved:
+            enc.to("cpu")
+            enc(fr)
+    return lambda: _traced(run)
+
+
 CASES = {}
+for _m in ("fp32", "bf16x3"):
+    CASES[f"clip/{_m}"] = _vit_case("clip", _m, 3, 40, 72)                      # landscape, upscaled
+    CASES[f"dinov2/{_m}"] = _vit_case("dinov2", _m, 3, 200, 300)                # SWIGLU
+CASES["clip/bf16x3/crop"] = _vit_case("clip", "bf16x3", 2, 120, 90, crop=True)  # portrait, downscaled: the wider filter
+CASES["dinov2/bf16x3/gelu"] = _vit_case("dinov2", "bf16x3", 3, 200, 300, cfg=dict(use_swiglu_ffn=False))
+# T = 197 > 128: attention launches and the qkv / ao buffers are padded to _attn_frames(1) = _attn_frames(2) = 17 frames
+CASES["dinov2/bf16x3/T197"] = _vit_case("dinov2", "bf16x3", 3, 200, 300, ctor=dict(resize=200, crop=196))
+CASES["dinov2/fp32/clip_attention"] = _vit_case("dinov2", "fp32", 3, 200, 300, attrs=dict(f32_attention="v2a_clip_attention"))
+CASES["dinov2/fp32/moved"] = _vit_case("dinov2", "fp32", 3, 200, 300, moved=True)
 for _m in MODES:
     for _b in (1, 2, 4):                              # regimes 0, 1, 2
         CASES[f"dit/{_m}/B{_b}"] = _dit_case(SHIPPED, _m, _b)

@@ -215,11 +215,8 @@ def main(argv=None):
 
     clip_encode = None
     if a.clip:
-        if a.video_encoder == "dinov2":
-            from .dinov2 import DINOv2ImageEncoder as ImageEncoder
-        else:
-            from .clip import CLIPImageEncoder as ImageEncoder
-        cenc = ImageEncoder.from_pretrained(a.clip, torch.device("cuda", local))
+        from .e2tts import IMAGE_ENCODERS
+        cenc = IMAGE_ENCODERS.get(a.video_encoder, IMAGE_ENCODERS["clip_vit"]).from_pretrained(a.clip, torch.device("cuda", local))
         def clip_encode(vp):
             try:
                 frames, duration = decode(vp)

@@ -25,7 +25,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .clip import CLIPImageEncoder
+from .dinov2 import DINOv2ImageEncoder
 from .dit import DiTConfig, DiTEngine, NOTES, process_streams
+
+IMAGE_ENCODERS = {"clip_vit": CLIPImageEncoder, "dinov2": DINOv2ImageEncoder}     # video_encoder -> its HIP encoder
 
 _IncompatibleKeys = namedtuple("_IncompatibleKeys", ["missing_keys", "unexpected_keys"])
 _V2R_PREFIX = "video2roll_net."
@@ -398,31 +402,19 @@ class E2TTS:
         (x3:1432-1433, 1714, 1742-1744): a `DINOv2ImageEncoder`, a local HF directory (dinov2-giant) or a state dict (Dinov2Model keys,
         or `image_encoder.*`); its hidden_size must equal dim_text.  `kw` go to the encoder's constructor (compute, chunk, config).
         The other choices of the reference have no encoder here."""
-        if self.video_encoder == "dinov2":
-            from .dinov2 import DINOv2ImageEncoder
-            if isinstance(src, DINOv2ImageEncoder):
-                enc = src
-            elif isinstance(src, (str, Path)):
-                enc = DINOv2ImageEncoder.from_pretrained(str(src), self._device, **kw)
-            elif isinstance(src, dict):
-                enc = DINOv2ImageEncoder(src, self._device, **kw)
-            else:
-                raise TypeError(f"load_image_encoder: a DINOv2ImageEncoder, a directory or a state dict, got {type(src).__name__}")
-            if enc.d != self.dim_text:
-                raise ValueError(f"load_image_encoder: the DINOv2 encoder's hidden_size {enc.d} is not the model's dim_text {self.dim_text}")
-            self._clip = enc
-            return enc
-        if self.video_encoder != "clip_vit":
+        cls = IMAGE_ENCODERS.get(self.video_encoder)
+        if cls is None:
             raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit' and 'dinov2' have a HIP encoder)")
-        from .clip import CLIPImageEncoder
-        if isinstance(src, CLIPImageEncoder):
+        if isinstance(src, cls):
             enc = src
         elif isinstance(src, (str, Path)):
-            enc = CLIPImageEncoder.from_pretrained(str(src), self._device, **kw)
+            enc = cls.from_pretrained(str(src), self._device, **kw)
         elif isinstance(src, dict):
-            enc = CLIPImageEncoder(src, self._device, **kw)
+            enc = cls(src, self._device, **kw)
         else:
-            raise TypeError(f"load_image_encoder: a CLIPImageEncoder, a directory or a state dict, got {type(src).__name__}")
+            raise TypeError(f"load_image_encoder: a {cls.__name__}, a directory or a state dict, got {type(src).__name__}")
+        if self.video_encoder == "dinov2" and enc.d != self.dim_text:
+            raise ValueError(f"load_image_encoder: the DINOv2 encoder's hidden_size {enc.d} is not the model's dim_text {self.dim_text}")
         self._clip = enc
         return enc
 

@@ -7,7 +7,7 @@ The result equals Pillow's bit for bit.  In Pillow's order: the grey byte `(1959
 every pixel; a horizontal pass of 22-bit fixed-point integer sums over those grey bytes, clipped to uint8, for the input rows
 the vertical pass reads; the vertical pass, clipped again; and a 256-entry host table of `float32(float64(u) / 255.0)` (the
 reference divides a uint8 array by a Python float and casts afterwards).  Rounding the grey value to a byte before filtering is
-part of the result: the three channels are never filtered separately.  The coefficient tables are `clip.resample_coeffs`
+part of the result: the three channels are never filtered separately.  The coefficient tables are `resample.resample_coeffs`
 (Pillow's `precompute_coeffs` + `normalize_coeffs_8bpc`); a pass Pillow skips (equal sizes) has identity tables here, which give
 the same bytes.
 """
@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .clip import PRECISION_BITS, resample_coeffs
+from .resample import PRECISION_BITS, resample_coeffs, vertical_window
 
 PIANO_HW = (100, 900)          # x3:60: `x.resize((900, 100))`
 _HALF = 1 << (PRECISION_BITS - 1)
@@ -42,11 +42,7 @@ class PianoFramePlan:
         self.H, self.W, self.Ho, self.Wo = int(H), int(W), int(Ho), int(Wo)
         self.hb, self.hk = resample_coeffs(self.W, self.Wo)
         vb, self.vk = resample_coeffs(self.H, self.Ho)
-        self.y0 = int(vb[:, 0].min())
-        self.rows = int((vb[:, 0] + vb[:, 1]).max()) - self.y0
-        vb = vb.copy()
-        vb[:, 0] -= self.y0
-        self.vb = vb
+        self.y0, self.rows, self.vb = vertical_window(vb)
         self.lut = scale_table()
         # the kernels read what the tables say: every tap must lie inside the image (checked here, the device cannot)
         assert (self.hb[:, 0] >= 0).all() and (self.hb[:, 1] > 0).all() and (self.hb[:, 0] + self.hb[:, 1] <= self.W).all()

@@ -9,12 +9,12 @@ log is truncated, a device logf could land on the other side of a boundary) and 
 from __future__ import annotations
 
 import math
-import os
 import re
 
 import torch
 
 from . import _lib as L
+from .weights import read_hf_dir, strip_keys
 
 MAX_LEN = 512
 
@@ -34,21 +34,6 @@ def relative_position_bucket_table(n: int, num_buckets: int = 32, max_distance: 
 
 
 _PREFIXES = ("text_encoder2.",)
-
-
-def _strip(state_dict) -> dict[str, torch.Tensor]:
-    """Plain T5EncoderModel keys from a T5EncoderModel state dict or a reference checkpoint (`text_encoder2.*`)."""
-    sd = state_dict.get("model_state_dict", state_dict) if isinstance(state_dict, dict) else state_dict
-    out = {}
-    has_prefixed = any(k.startswith(_PREFIXES) for k in sd)
-    for k, v in sd.items():
-        if has_prefixed:
-            for p in _PREFIXES:
-                if k.startswith(p):
-                    out[k[len(p):]] = v
-        else:
-            out[k] = v
-    return out
 
 
 def infer_config(sd: dict[str, torch.Tensor]) -> dict:
@@ -79,7 +64,7 @@ class T5Encoder:
     given (a dict of T5Config fields)."""
 
     def __init__(self, state_dict, device, tokenizer=None, config: dict | None = None):
-        sd = _strip(state_dict)
+        sd = strip_keys(state_dict, _PREFIXES)
         cfg = infer_config(sd)
         if config is not None:
             cfg.update({k: v for k, v in dict(config).items() if k in cfg})
@@ -115,16 +100,8 @@ class T5Encoder:
     @classmethod
     def from_pretrained(cls, path: str, device):
         """A local HF directory (the reference's ./ckpts/flan-t5-large): config.json, weights, tokenizer."""
-        import json
         from transformers import AutoTokenizer
-        with open(os.path.join(path, "config.json")) as f:
-            hc = json.load(f)
-        st = os.path.join(path, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
+        hc, sd = read_hf_dir(path)
         if hc.get("feed_forward_proj", "gated-gelu") != "gated-gelu":
             raise NotImplementedError(f"T5Encoder: feed_forward_proj {hc.get('feed_forward_proj')!r} (gated-gelu only)")
         config = {k: hc[k] for k in ("relative_attention_max_distance", "layer_norm_epsilon") if k in hc}
