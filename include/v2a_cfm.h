@@ -135,6 +135,16 @@ typedef struct v2a_gemm_args {
    * v2a_tuning.gemm_force_tile for THIS call (bf16 x bf16 only).  The sampler passes 1 (128x256 tiles, one workgroup per CU) for
    * the text / frames streams: their GEMMs run beside the audio stream's, and few fat workgroups that own whole CUs disturb
    * the critical path less than many small ones spread over every CU (+3.5 % end to end, measured).
+   * Plain bf16 x bf16 operands, 0 = by shape or 1..16 (any other value is rejected); tile, waves (rows x columns), ring depth, wave tile:
+   *    1 = 128x256, 2x4, 3-deep, 64x64         2 = 128x128, 2x2, 3-deep, 64x64         3 = 128x64, 2x2, 3-deep, 64x32
+   *    4 = 5 = 64x64, 2x2, 3-deep, 32x32       6 = 256x256, 2x4, 2-deep, 128x64        8 = 64x128, 2x2, 6-deep, 32x64
+   *    9 = 64x64, 2x2, 6-deep, 32x32          10 = 64x64, 2x2, 4-deep, 32x32          11 = 64x64, 2x2, 5-deep, 32x32
+   *   12 = 128x128, 2x2, 4-deep, 64x64        13 = 128x128, 2x4, 3-deep, 64x32        14 = 64x64, 2x4, 3-deep, 32x16
+   *   15 = 128x64, 4x2, 3-deep, 32x32         16 = 64x128, 2x4, 3-deep, 32x32
+   *    7 = the 256x256 phase-interleaved (8-phase) kernel: dense rows and 16-byte aligned epilogue operands only
+   * 14 has no GEGLU form (value / gate groups of 16 columns need wave tiles of 32) and is refused together with norm_ssq (V2A_ERR_ARG: the
+   * partial sums per 32 columns need wave tiles of at least 32 columns); norm_gamma alone, the shadow without sums, runs on it.  The K order
+   * of an output element is the same on every ring shape: STORE / RESID / GATE_RESID results of hints 1..6 and 8..16 are equal bit for bit.
    * Split operands (a_dtype V2A_BF16_SPLIT) have tile shapes of their own, 0 = by shape or 1..7 (any other value is rejected):
    *   1 = 64x64, 2 = 128x64, 3 = 128x128 (8 waves, 2-deep ring), 4 = 64x128 (8 waves): LDS-DMA ring, a stage = 64 k of the four planes;
    *   5 = the 256x256 phase-interleaved (8-phase) kernel: a stage = 32 logical k, staged as rows [32 k hi | 32 k lo] of both operands,

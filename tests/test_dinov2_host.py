@@ -78,9 +78,12 @@ def test_swiglu_row_packing_gate_is_x1_value_is_x2():
         assert torch.equal(pb[32 * g:32 * g + 16], b_in[hf + 16 * g:hf + 16 * g + 16])
         assert torch.equal(pb[32 * g + 16:32 * g + 32], b_in[16 * g:16 * g + 16])
     # what the epilogue computes on the packed rows is what Dinov2SwiGLUFFN computes on the module's
+    # (every output element as its own 192-term sum: a BLAS product may sum a row of W in an order that depends on where the row sits in the
+    # matrix -- MKL does on some CPUs -- and the comparison below is bit for bit between two row orders)
     x = torch.randn(5, 192, dtype=torch.float64)
-    x1, x2 = (x @ w_in.double().t() + b_in.double()).chunk(2, -1)
-    acc = (x @ pw.double().t() + pb.double()).view(5, hf // 16, 2, 16)
+    lin = lambda w, b: (x[:, None, :] * w.double()[None]).sum(-1) + b.double()
+    x1, x2 = lin(w_in, b_in).chunk(2, -1)
+    acc = lin(pw, pb).view(5, hf // 16, 2, 16)
     assert torch.equal(acc[:, :, 0].reshape(5, hf) * torch.nn.functional.silu(acc[:, :, 1].reshape(5, hf)), torch.nn.functional.silu(x1) * x2)
 
 

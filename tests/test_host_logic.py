@@ -146,3 +146,39 @@ def test_tuned_tiles_table_names_existing_ab_logs():
                 assert os.path.isfile(os.path.join(root, fn)), fn
     assert tuned_tiles("bf16", 0, (64, 64, 64, 4)) == {}            # unmeasured widths: policy tiles only
     assert tuned_tiles("bf16", 0, SHIPPED_WIDTHS)[("t", "ff1")] == 6
+
+
+def test_engine_surfaces_refused_main_tile_with_folded_norms():
+    """main_tile = 13 is tile_hint 14 (64x64 tiles, wave tile 32x16), which cannot leave the sums of squares a folded RMSNorm's producer owes its
+    consumer: v2a_gemm refuses the pair on the host, before any launch, and the engine hands the error on instead of sampling with wrong scales.
+    The engine runs on the CPU against a stand-in library that answers 0 to everything except that one call, which goes to the real argument check."""
+    from v2a_amd import _lib as L
+    from v2a_amd.dit import DiTEngine
+    real, refused = L.lib(), []
+
+    class _StandIn:
+        def __getattr__(self, name):
+            def call(*args):
+                if name == "v2a_last_error":
+                    return real.v2a_last_error()
+                if name == "v2a_gemm" and args[0]._obj.tile_hint == 14 and args[0]._obj.norm_ssq:
+                    refused.append(real.v2a_gemm(*args))
+                    return refused[-1]
+                return 0
+            return call
+
+    cfg = DiTConfig(depth=4)                                  # the shipped widths: the tuned tile table, and with it main_tile, applies
+    sd = {k: torch.zeros(s) for k, s in v2a_amd.expected_state_dict_shapes(cfg).items()}
+    B, T, nc, S = 1, 778, 64, 4
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(L, "_lib", _StandIn())
+        mp.setattr(L, "stream_ptr", lambda: 0)
+        eng = DiTEngine(cfg, sd, device="cpu", compute="bf16")
+        assert eng.main_tile == 14 and eng.fold_norm
+        eng.main_tile = 13
+        eng.setup(B, T, nc, S)
+        eng.prepare(torch.zeros(B, T, cfg.dim_text), torch.zeros(B, T, cfg.notes), torch.zeros(B, nc, cfg.ctx_dim),
+                    torch.ones(B, nc, dtype=torch.bool), torch.linspace(0, 0.75, S), dt=torch.full((S,), 0.25))
+        with pytest.raises(L.V2AError, match="tile_hint 14.*32x16"):
+            eng.euler_step(torch.zeros(B, T, cfg.num_channels), 2.0)
+    assert refused == [-1]                                   # V2A_ERR_ARG, at the first such launch

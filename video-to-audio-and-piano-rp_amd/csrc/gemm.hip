@@ -833,6 +833,11 @@ extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
   auto ntiles = [&](int bm, int bn) { return (int64_t)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
   // wide outputs: 256x256 tile with the phase-interleaved K loop (gemm_8phase.hip) once the problem yields enough tiles
   V2A_REQUIRE(a->tile_hint >= 0 && a->tile_hint <= 16, "v2a_gemm: tile_hint %d", a->tile_hint);
+  // the producer's partial sums are butterflies over the 8 lanes that hold 32 columns of ONE row: with 16-column wave tiles a row has 4 lanes,
+  // an octet would add 16 columns each of two rows, and the two waves of a 32-column group would write the same entry
+  V2A_REQUIRE(a->tile_hint != 14 || !a->norm_ssq,
+              "v2a_gemm: tile_hint 14 (64x64 tiles, wave tile 32x16) cannot write norm_ssq: the partial sums per 32 columns need wave tiles of "
+              "at least 32 columns");
   const bool dense = !a->a_row_offset && !a->out_row_offset && p.vec_epi;
   if (a->tile_hint > 0 && tune.force_tile < 0) {
     if (a->tile_hint == 7) {
