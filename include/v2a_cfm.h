@@ -629,6 +629,37 @@ int v2a_encodec_rvq_encode(const float* x, int64_t batch_stride, int64_t frame_s
 int v2a_encodec_rvq_decode(const int64_t* codes, int32_t n_q, int32_t B, int32_t T, const float* codebooks, int32_t S, int32_t Kc, int32_t D,
                            float* out, int64_t batch_stride, int64_t frame_stride, int64_t chan_stride, v2a_stream_t stream);
 
+/* =====================================================================================
+ * Validation pass of E2TTS.forward(val=True) (e2_tts_crossatt3.py:2307-2588): the interpolation in front of the DiT and the two
+ * losses behind it.  Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+/* Workgroup partials of v2a_masked_sqerr / v2a_roll_metrics: `scratch` holds V2A_LOSS_MAX_PARTS * 2 (resp. * 6) doubles. */
+#define V2A_LOSS_MAX_PARTS 256
+
+/* One pass over the (B, T, C) fp32 latents, t (B) fp32:
+ *   w    = (1 - t[b]) * x0 + t[b] * x1     two rounded products and a rounded sum (no FMA): torch's fp32 result bit for bit
+ *   flow = x1 - x0
+ *   cond = span[b * T + n] ? 0 : x1        only when cond != NULL; span (B * T) bytes, NULL = no frame is in the span
+ * C a multiple of 4, the five tensors contiguous and 16-byte aligned.
+ * Replaces: `w = (1. - t) * x0 + t * x1`, `flow = x1 - x0` and the `einx.where` of x3:2394-2407. */
+int v2a_cfm_interp(const float* x0, const float* x1, const float* t, const uint8_t* span, float* w, float* flow, float* cond, int32_t B,
+                   int32_t T, int32_t C, v2a_stream_t stream);
+/* out[0] = sum of (double(pred) - double(target))^2 over the elements of the frames with mask[b * T + n] != 0, out[1] = their number.
+ * pred, target (B, T, C) fp32 contiguous, 16-byte aligned, C a multiple of 4; mask (B * T) bytes.  The sums are taken in double in
+ * an order fixed by the shape (workgroup partials in `scratch`, then one workgroup over them; no atomics): two calls give the same bits.
+ * Replaces: `F.mse_loss(pred, flow, reduction = 'none')[rand_span_mask].mean()` (x3:2542-2547) up to the final division. */
+int v2a_masked_sqerr(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t T, int32_t C, double* scratch,
+                     double* out, v2a_stream_t stream);
+/* roll, midis (B, T, notes) fp32 contiguous, mask (B * T) bytes.
+ *   out[0] = sum of (roll - midis)^2 * |midis - 0.10| in double over the elements of the masked frames, out[1] = their number
+ *   out[2..5] = tp, fp, fn, tn over the (clip, g < T / 3, note) cells whose frames 3g, 3g + 1, 3g + 2 are all masked in, on the fp32
+ *               means ((a + b) + c) / 3 of the three frames: roll mean >= 0.4f against midis mean >= 0.5f
+ * Same fixed-order reduction as v2a_masked_sqerr.
+ * Replaces: the roll loss and the pooled confusion counts of x3:2429-2443. */
+int v2a_roll_metrics(const float* roll, const float* midis, const uint8_t* mask, int32_t B, int32_t T, int32_t notes, double* scratch,
+                     double* out, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,12 +4,12 @@ Import name: `v2a_amd` (the directory name contains hyphens; the repo-root shim 
 registers this package under that name).
 """
 from .dit import DiTConfig, DiTEngine, PackedWeights, NOTES  # noqa: F401
-from .e2tts import E2TTS, sway_grid, lens_to_mask, expected_state_dict_shapes  # noqa: F401
+from .e2tts import E2TTS, E2TTSReturn, LossBreakdown, sway_grid, lens_to_mask, val_span_mask, expected_state_dict_shapes  # noqa: F401
 from .collate import collate_clips, ClipRequest  # noqa: F401
 from .dist import shard_range, gather_latents  # noqa: F401
 from .features import (feature_cache_path, save_clip_cache, load_clip_cache, resample_indices,  # noqa: F401
                        resample_clip_features, encode_video_cached, piano_frames_cache_path, save_piano_frames_cache,
-                       piano_frame_indices, load_piano_frames, piano_frames_from_video)
+                       piano_frame_indices, load_piano_frames, piano_frames_from_video, load_midi_ground_truth)
 from .video2roll import Video2RollEngine  # noqa: F401
 from .encodec import EncodecDecoder, EncodecEncoder, EncodecQuantizer  # noqa: F401
 from .t5 import T5Encoder  # noqa: F401
@@ -19,5 +19,5 @@ from .piano_frames import PianoFramePlan, PianoFramePreprocessor  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
-           "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "expected_state_dict_shapes", "NOTES",
+           "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "val_span_mask", "E2TTSReturn", "LossBreakdown", "load_midi_ground_truth", "expected_state_dict_shapes", "NOTES",
            "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor"]

@@ -114,7 +114,7 @@ EXPORTS = [
     "v2a_elu_pad", "v2a_lstm_layer", "v2a_lstm2", "v2a_t5_rmsnorm", "v2a_t5_attention", "v2a_gemm_skinny_f32",
     "v2a_clip_resize_h", "v2a_clip_resize_v", "v2a_clip_embed_init", "v2a_clip_layernorm", "v2a_clip_attention",
     "v2a_elu_pad_lr", "v2a_encodec_stage0", "v2a_piano_resize_h", "v2a_piano_resize_v",
-    "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode",
+    "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode", "v2a_cfm_interp", "v2a_masked_sqerr", "v2a_roll_metrics",
 ]
 
 
@@ -180,6 +180,9 @@ def _declare(lib):
     lib.v2a_piano_resize_v.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     lib.v2a_encodec_rvq_encode.argtypes = [vp, i64, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     lib.v2a_encodec_rvq_decode.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, i64, i64, i64, vp]
+    lib.v2a_cfm_interp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.v2a_masked_sqerr.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.v2a_roll_metrics.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -619,6 +622,37 @@ def encodec_rvq_decode(codes, codebooks, out, strides, *, B, T, n_q):
     _launch("encodec_rvq_decode", 1.0 * B * T * n_q * D, B * T * (4.0 * D * (n_q + 1) + 8.0 * n_q),
             lambda: lib().v2a_encodec_rvq_decode(codes.data_ptr(), n_q, B, T, codebooks.data_ptr(), S, Kc, D, out.data_ptr(),
                                                  strides[0], strides[1], strides[2], stream_ptr()))
+
+
+# ---- validation pass (E2TTS.forward(val=True)) ---------------------------------------------------
+LOSS_MAX_PARTS = 256             # V2A_LOSS_MAX_PARTS: workgroup partials of the two loss reductions
+
+
+def cfm_interp(x0, x1, t, span, w, flow, cond=None):
+    """w = (1 - t) x0 + t x1, flow = x1 - x0, cond = span ? 0 : x1 (cond None: not written; span None: no frame in the span).
+    x0, x1, w, flow, cond (B, T, C) fp32 contiguous, t (B,) fp32, span (B, T) uint8."""
+    B, T, C_ = x1.shape
+    _launch("cfm_interp", 4.0 * B * T * C_, 4.0 * B * T * C_ * (4 if cond is None else 5),
+            lambda: lib().v2a_cfm_interp(x0.data_ptr(), x1.data_ptr(), t.data_ptr(), _p(span), w.data_ptr(), flow.data_ptr(), _p(cond),
+                                         B, T, C_, stream_ptr()))
+
+
+def masked_sqerr(pred, target, mask, out):
+    """out (2,) float64 <- (sum of (pred - target)^2 in double over the frames of mask (B, T) uint8, number of elements)."""
+    B, T, C_ = pred.shape
+    scratch = torch.empty(LOSS_MAX_PARTS * 2, dtype=torch.float64, device=pred.device)
+    _launch("masked_sqerr", 3.0 * B * T * C_, 8.0 * B * T * C_,
+            lambda: lib().v2a_masked_sqerr(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), B, T, C_, scratch.data_ptr(), out.data_ptr(),
+                                           stream_ptr()))
+
+
+def roll_metrics(roll, midis, mask, out):
+    """out (6,) float64 <- (sum of (roll - midis)^2 |midis - 0.10|, number of elements, tp, fp, fn, tn); roll, midis (B, T, notes)."""
+    B, T, notes = roll.shape
+    scratch = torch.empty(LOSS_MAX_PARTS * 6, dtype=torch.float64, device=roll.device)
+    _launch("roll_metrics", 5.0 * B * T * notes, 16.0 * B * T * notes,
+            lambda: lib().v2a_roll_metrics(roll.data_ptr(), midis.data_ptr(), mask.data_ptr(), B, T, notes, scratch.data_ptr(), out.data_ptr(),
+                                           stream_ptr()))
 
 
 def lstm_layer(gates_x, w_hh, h, workspace, *, T, H, resid=None, y=None):

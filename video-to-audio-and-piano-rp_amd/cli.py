@@ -28,6 +28,10 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
                      of the clip's valid frames at 1.5 / 3 / 6 / 12 / 24 kbps (2 / 4 / 8 / 16 / 32 codebooks of 10 bits at 75 Hz), what
                      `EncodecModel.encode(...).audio_codes[0][0]` holds and any Encodec decoder reads.  The `.wav` is still decoded from
                      the continuous latents.
+  --validate         no sampling: the reference's validation pass, `E2TTS.forward(val=True)` at times = 0.5 as the trainer's evaluate() calls
+                     it (trainer_multigpus_alldatas3.py:271-290), on the ground-truth latents `<video>.latent.npy` (n, C) next to each video;
+                     with --piano also the roll loss and the Video2Roll metrics against `<video>.3.npy`.  Prints one JSON line per batch:
+                     loss, roll_loss, precision, recall, f1, acc.  One rank only; nothing is written.
 The moviepy mux of audio and video stays outside (out of scope).
 """
 from __future__ import annotations
@@ -125,6 +129,21 @@ def piano_frames_for(video_paths, l: int, preprocess, decode):
     return load_piano_frames(video_paths, l, video_frames=[frames_of(vp) for vp in video_paths], preprocess=preprocess)
 
 
+def validate_batch(model, video_paths, extras, frames=None) -> dict:
+    """--validate: one `forward(val=True)` over a collated batch.  The ground-truth latents `<video>.latent.npy` (n, C) are zero
+    padded to the longest clip of the batch and `lens` holds their lengths; `frames`: the --piano stack of the same clips."""
+    from .features import load_midi_ground_truth
+    lat = [torch.from_numpy(np.load(vp.rsplit(".", 1)[0] + ".latent.npy")).float() for vp in video_paths]
+    n = extras["text_embed"].shape[1]
+    lens = torch.tensor([min(x.shape[0], n) for x in lat])
+    inp = torch.stack([torch.nn.functional.pad(x[:n], (0, 0, 0, n - min(x.shape[0], n))) for x in lat])
+    midis = None if frames is None else load_midi_ground_truth(video_paths, n)
+    r = model.forward(inp, times=0.5, lens=lens, val=True, frames=frames, midis=midis, text_embed=extras["text_embed"],
+                      context=extras["context"], context_mask=extras["context_mask"])
+    return dict(clips=len(video_paths), loss=float(r.loss), roll_loss=model.val_stats["roll"],
+                **{k: float(v) for k, v in zip(("precision", "recall", "f1", "acc"), r.loss_breakdown)})
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("ckpt")
@@ -162,6 +181,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "prompt every clip with the first S seconds of <video>.wav, encoded by the HIP Encodec encoder")
     ap.add_argument("--codes", type=float, default=None, choices=[1.5, 3.0, 6.0, 12.0, 24.0], metavar="KBPS",
                     help="with --encodec: also write <name>.codes.npy, the int16 (n_q, n) Encodec codes of the clip at this bandwidth")
+    ap.add_argument("--validate", action="store_true", help="instead of sampling, run the validation pass forward(val=True) on "
+                    "<video>.latent.npy and print one JSON line per batch: loss, roll_loss, precision, recall, f1, acc")
     return ap
 
 
@@ -173,6 +194,9 @@ def main(argv=None):
 
     if a.codes is not None and not a.encodec:
         ap.error("--codes needs --encodec (the state dict that holds the quantizer's codebooks)")
+
+    if a.validate and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--validate runs on one rank")
 
     import torch.distributed as dist
     from . import E2TTS, collate_clips, gather_latents, shard_range
@@ -187,6 +211,7 @@ def main(argv=None):
     channels = tk.pop("num_channels", 128)
     model = E2TTS(transformer=dict(if_text_modules=True, if_cross_attn=True, if_audio_conv=True, if_text_conv=True, **tk),
                   num_channels=channels, sampling_rate=24000, if_cond_proj_in=a.audio_prompt_seconds > 0, tokenizer="phoneme_zh",
+                  audiocond_drop_prob=0.3 if a.audio_prompt_seconds > 0 else 1.1,          # predict.py:71-72, 144: the two travel together
                   compute_dtype=a.dtype, device=torch.device("cuda", local), bucket_frames=a.bucket_frames, bucket_ctx=a.bucket_ctx,
                   frames_compute_dtype=a.frames_dtype, video_encoder=a.video_encoder)
     ck = torch.load(a.ckpt, map_location="cpu")
@@ -247,6 +272,10 @@ def main(argv=None):
                 # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
                 frames = piano_frames_for([vp for vp, _ in mine], int(batch8[3].max()), model.piano_frame_preprocessor(), decode)
             decoded.clear()
+            if a.validate:
+                import json
+                print(json.dumps(dict(batch=b0 // a.batch, **validate_batch(model, [vp for vp, _ in mine], extras, frames))), flush=True)
+                continue
             cond, lens = batch8[1], batch8[3]
             if a.audio_prompt_seconds > 0:                           # raw waves (b, nw): sample() encodes them (x3:2157-2160)
                 cond = torch.stack([read_audio_prompt(vp, a.audio_prompt_seconds) for vp, _ in mine])

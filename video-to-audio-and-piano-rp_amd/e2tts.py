@@ -1,6 +1,6 @@
 """Drop-in `E2TTS` for the sampling path: same constructor keywords, `sample()`,
-`transformer_with_pred_head()`, `cfg_transformer_with_pred_head()` and checkpoint key layout as
-the reference class (x3:1275-1318, 1993-2113, 2127-2305; `x3` =
+`transformer_with_pred_head()`, `cfg_transformer_with_pred_head()`, the validation pass `forward(val=True)` and checkpoint key
+layout as the reference class (x3:1275-1318, 1993-2113, 2127-2305, 2307-2588; `x3` =
 /root/reference/src/e2_tts_pytorch/e2_tts_crossatt3.py), running on the HIP kernels of
 include/v2a_cfm.h.  Callers: predict.py:266, app.py:267, src/inference_v2a.py:183,
 src/inference_v2p.py:183.
@@ -31,6 +31,8 @@ from .dit import DiTConfig, DiTEngine, NOTES, process_streams
 
 IMAGE_ENCODERS = {"clip_vit": CLIPImageEncoder, "dinov2": DINOv2ImageEncoder}     # video_encoder -> its HIP encoder
 
+LossBreakdown = namedtuple("LossBreakdown", ["flow", "velocity_consistency", "a", "b"])                     # x3:132
+E2TTSReturn = namedtuple("E2TTS", ["loss", "cond", "pred_flow", "pred_data", "loss_breakdown"])               # x3:134
 _IncompatibleKeys = namedtuple("_IncompatibleKeys", ["missing_keys", "unexpected_keys"])
 _V2R_PREFIX = "video2roll_net."
 
@@ -41,6 +43,18 @@ def lens_to_mask(t: torch.Tensor, length: int | None = None) -> torch.Tensor:
         length = int(t.amax())
     seq = torch.arange(length, device=t.device)
     return seq[None, :] < t[:, None]
+
+
+def val_span_mask(lens: torch.Tensor, n: int) -> torch.Tensor:
+    """The infilling span of the validation pass, (b, n) bool: `mask_from_frac_lengths(lens, frac, max_length=n, val=True) & mask`
+    with frac = (0.7 + 1.0) / 2 (x3:316-337, 2358-2362), in the reference's torch float32 ops on the host: 85 % of every clip, centred."""
+    lens = torch.as_tensor(lens).cpu().long()
+    frac = torch.tensor([(0.7 + 1.0) / 2.0] * lens.shape[0]).float()
+    lengths = (frac * lens).long()
+    start = ((lens - lengths) * torch.tensor([0.5] * lens.shape[0]).float()).long().clamp(min=0)
+    seq = torch.arange(int(n))
+    span = (seq[None, :] >= start[:, None]) & (seq[None, :] < (start + lengths)[:, None])
+    return span & lens_to_mask(lens, int(n))
 
 
 def sway_grid(steps: int, sway_sampling: bool = True) -> torch.Tensor:
@@ -458,6 +472,48 @@ class E2TTS:
         assert context.shape[0] == b
         return context, context_mask
 
+    def _clip_conditioning(self, text, video_paths, video_frames, batch: int, n: int):
+        """The (b, n, dim_text) CLIP conditioning of `sample` and `forward` (x3:2183-2184, 2335-2336) when no text_embed= was given."""
+        cfgm = self.cfg
+        if video_paths is not None and self.video_encoder_fn is not None:
+            return self.video_encoder_fn(video_paths, n)
+        if video_paths is not None:
+            # cached CLIP features next to the videos, resampled to the latent rate (encode_video's cache branch,
+            # x3:1796-1813); with video_frames and the image encoder, missing caches are encoded first (x3:1706-1793)
+            from .features import encode_video_cached, feature_cache_path
+            encoder_fn = None
+            if video_frames is not None:
+                if self._clip is None:
+                    raise RuntimeError("video_frames needs the CLIP image encoder: call load_image_encoder first")
+                if len(video_frames) != len(video_paths):
+                    raise ValueError(f"video_frames: {len(video_frames)} entries for {len(video_paths)} video_paths")
+                plain = [vp[0] if isinstance(vp, tuple) else vp for vp in video_paths]
+                todo = [fr if vp is not None and fr is not None and not os.path.exists(feature_cache_path(vp, self.video_encoder)) else None
+                        for vp, fr in zip(plain, video_frames)]
+                done = {vp: e for vp, e in zip(plain, self._encode_video_frames(todo)) if e is not None}
+                def encoder_fn(vp):
+                    if vp not in done:
+                        raise FileNotFoundError(f"{feature_cache_path(vp, self.video_encoder)}: no cached CLIP features and no frames for {vp}")
+                    return done[vp]
+            return encode_video_cached(video_paths, n, dim=cfgm.dim_text, video_encoder=self.video_encoder,
+                                       sampling_rate=self.sampling_rate or 24000, frame_size=self.frame_size, encoder_fn=encoder_fn)
+        if video_frames is not None:
+            if self._clip is None:
+                raise RuntimeError("video_frames needs the CLIP image encoder: call load_image_encoder first")
+            if len(video_frames) != batch:
+                raise ValueError(f"video_frames: {len(video_frames)} entries for a batch of {batch}")
+            from .features import resample_clip_features
+            rows = []
+            for e in self._encode_video_frames(list(video_frames)):
+                rows.append(torch.zeros(n, cfgm.dim_text) if e is None else
+                            resample_clip_features(e[0], e[1], n, sampling_rate=self.sampling_rate or 24000,
+                                                   frame_size=self.frame_size))
+            return torch.stack(rows, 0)
+        if torch.is_tensor(text) and text.ndim == 3:
+            return text
+        raise NotImplementedError("pass video_paths (with cached .npz CLIP features), text_embed= (b, n, dim_text) "
+                                  "or video_encoder_fn=")
+
     # ---- reference API: one forward ----------------------------------------------------------
     @torch.no_grad()
     def transformer_with_pred_head(self, x, cond=None, times=None, mask=None, text=None, frames_embed=None,
@@ -518,6 +574,93 @@ class E2TTS:
             par = (xd * unit).sum(-1, keepdim=True) * unit
             upd = ((xd - par) + par * keep_parallel_frac).reshape(shp).to(pred.dtype)
         return pred + upd * cfg_strength
+
+    # ---- reference API: the validation pass ------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, inp, *, text=None, times=None, lens=None, velocity_consistency_model=None, velocity_consistency_delta=1e-3,
+                prompt=None, video_drop_prompt=None, audio_drop_prompt=None, val=False, video_paths=None, frames=None, midis=None,
+                # build-side extensions
+                x0=None, text_embed=None, context=None, context_mask=None, frames_embed=None, video_frames=None):
+        """x3:2307-2588, the `val=True` branch -- what the trainer's evaluate() calls: a fixed span (`val_span_mask`), fixed noise, one
+        evaluation of the DiT with nothing dropped, the flow-matching loss on the span and, with `frames`, the roll loss and the
+        precision / recall / f1 / accuracy of the Video2Roll encoder against `midis`.  Returns the reference's
+        `E2TTSReturn(loss, cond, pred_flow, pred_data, LossBreakdown(precision, recall, f1, acc))` on inp's device, loss = flow loss +
+        10 * roll loss; `val_stats` keeps the parts (flow, roll, tp, fp, fn, tn) of the last call.  Training (`val=False`) is out of scope.
+        `inp` (b, n, C) latents or a raw wave (b, nw) through `mel_spec`; `times` a scalar, (b,) or None (= torch.rand(b));
+        `frames` (bf, 1, t, 100, 900) with `midis` (bf, n, NOTES) cover the last bf <= b clips.
+        `x0`: the noise (b, n, C); without it, randn of a generator seeded 0 on the model's device -- the reference seeds the global
+        RNG with 0 and re-seeds it from the clock (x3:2373-2377), this leaves the global RNG alone.
+        `text_embed`, `context`, `context_mask`, `video_frames`: as in `sample`; `frames_embed` (bf, n, NOTES): the roll in place of
+        `encode_frames(frames, n)`."""
+        if not val:
+            raise NotImplementedError("forward(val=False) is the training step (random spans, random condition dropping, gradients): "
+                                      "out of scope, only the validation pass val=True is built")
+        if velocity_consistency_model is not None:
+            raise NotImplementedError("velocity_consistency_model: the velocity consistency loss is a training term (x3:2508-2536)")
+        has_cond = not self.audiocond_drop_prob > 1.0                                  # x3:2400-2407
+        if has_cond and self.audiocond_snr is not None:
+            raise NotImplementedError("audiocond_snr: the reference adds fresh device noise to the audio condition (x3:2115-2125, 2406)")
+        self.eval()
+        if inp.ndim == 2:                                                              # raw wave (x3:2328-2331)
+            if self.mel_spec is None:
+                raise NotImplementedError("a raw-wave `inp` needs mel_spec_module, which the shipped config does not set "
+                                          "(load_audio_encoder sets the Encodec encoder)")
+            inp = self.mel_spec(inp).permute(0, 2, 1)                                  # b d n -> b n d
+            assert inp.shape[-1] == self.num_channels, (tuple(inp.shape), self.num_channels)
+        b, n = inp.shape[:2]
+        out_device, dev, C_ = inp.device, self._device, self.num_channels
+        if text_embed is None:
+            text_embed = self._clip_conditioning(text, video_paths, video_frames, b, n)    # x3:2335-2336
+        lens = torch.full((b,), n, dtype=torch.long) if lens is None else torch.as_tensor(lens).cpu().long()
+        mask = lens_to_mask(lens, n)                                                   # x3:2348
+        span = val_span_mask(lens, n)                                                  # x3:2358-2362
+        mask_u8, span_u8 = mask.to(dev, torch.uint8).contiguous(), span.to(dev, torch.uint8).contiguous()
+        x1 = inp.detach().to(dev, torch.float32).contiguous()
+        if x0 is None:
+            x0 = torch.randn(b, n, C_, device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+        x0 = x0.to(dev, torch.float32).contiguous()
+        assert x0.shape == x1.shape == (b, n, C_), (tuple(x0.shape), tuple(x1.shape))
+        if times is None:
+            times = torch.rand(b)                                                      # x3:2382
+        times = torch.as_tensor(times, dtype=torch.float32).cpu()
+        times = times.repeat(b) if times.ndim == 0 else times                          # x3:2384
+        assert times.shape == (b,), tuple(times.shape)
+        w, flow = torch.empty_like(x1), torch.empty_like(x1)
+        cond = torch.empty_like(x1) if has_cond else None
+        L.cfm_interp(x0, x1, times.to(dev), span_u8 if has_cond else None, w, flow, cond)      # x3:2394-2407
+        # -- roll loss and metrics of the frame encoder (x3:2418-2448); no frames: roll and midis are zero, and so are all five
+        stats = torch.zeros(8, dtype=torch.float64, device=dev)                        # flow: sum, count; roll: sum, count, tp, fp, fn, tn
+        roll = torch.zeros(b, n, self.cfg.notes, device=dev)
+        if frames is not None or frames_embed is not None:
+            if midis is None:
+                raise ValueError("forward: `frames` needs `midis` (bf, n, NOTES), the MIDI ground truth of the same clips")
+            if frames_embed is None:
+                frames_embed = (self.frames_encoder_fn or self.encode_frames)(frames, n)       # x3:2423
+            fe = frames_embed.to(dev, torch.float32).contiguous()
+            md = midis.to(dev, torch.float32).contiguous()
+            bf = fe.shape[0]
+            if not (0 < bf <= b and fe.shape == md.shape == (bf, n, self.cfg.notes)):
+                raise ValueError(f"forward: roll {tuple(fe.shape)} and midis {tuple(md.shape)}, expected (bf <= {b}, {n}, {self.cfg.notes})")
+            L.roll_metrics(fe, md, mask_u8[b - bf:], stats[2:])                        # x3:2429-2443
+            roll[b - bf:] = fe                                                         # x3:2469-2470: zero clips in front
+        pred = self.transformer_with_pred_head(w, cond, times=times, mask=mask, text=text_embed, frames_embed=roll, prompt=prompt,
+                                               video_drop_prompt=video_drop_prompt, audio_drop_prompt=audio_drop_prompt,
+                                               drop_audio_cond=False, drop_text_cond=False, drop_text_prompt=False,
+                                               context=context, context_mask=context_mask)                  # x3:2488-2502
+        L.masked_sqerr(pred, flow, span_u8, stats[:2])                                 # x3:2542-2547
+        st = stats.cpu()                                                               # the one transfer of the scalars
+        flow_loss = st[0] / st[1]                                                      # an empty span: 0 / 0 = nan, as torch's mean of nothing
+        roll_loss = st[2] / st[3] if frames_embed is not None else st[2]               # no frames: 0 (x3:2419-2420)
+        tp, fp, fn, tn = (float(v) for v in st[4:])
+        ratio = lambda num, den: num / den if den != 0 else 0.0                        # x3:2445-2448
+        pre, rec, f1, acc = ratio(tp, tp + fp), ratio(tp, tp + fn), ratio(2 * tp, 2 * tp + fp + fn), ratio(tp, tp + fp + fn)
+        self.val_stats = dict(flow=float(flow_loss), roll=float(roll_loss), tp=tp, fp=fp, fn=fn, tn=tn)
+        f32 = lambda v: torch.as_tensor(v, dtype=torch.float64).to(torch.float32).to(out_device)
+        total = f32(flow_loss + 10.0 * roll_loss)                                      # x3:2574-2577
+        return E2TTSReturn(total, (cond if has_cond else w).to(out_device), pred.to(out_device), (x0 + pred).to(out_device),
+                           LossBreakdown(f32(pre), f32(rec), f32(f1), f32(acc)))        # x3:2579, 2588
+
+    __call__ = forward
 
     # ---- reference API: the sampler ------------------------------------------------------------
     @torch.no_grad()
@@ -580,46 +723,7 @@ class E2TTS:
         lens = torch.as_tensor(lens).cpu().long()
         # -- CLIP conditioning (x3:2183-2184)
         if text_embed is None:
-            if video_paths is not None and self.video_encoder_fn is not None:
-                text_embed = self.video_encoder_fn(video_paths, cond_seq_len)
-            elif video_paths is not None:
-                # cached CLIP features next to the videos, resampled to the latent rate (encode_video's cache branch,
-                # x3:1796-1813); with video_frames and the image encoder, missing caches are encoded first (x3:1706-1793)
-                from .features import encode_video_cached, feature_cache_path
-                encoder_fn = None
-                if video_frames is not None:
-                    if self._clip is None:
-                        raise RuntimeError("video_frames needs the CLIP image encoder: call load_image_encoder first")
-                    if len(video_frames) != len(video_paths):
-                        raise ValueError(f"video_frames: {len(video_frames)} entries for {len(video_paths)} video_paths")
-                    plain = [vp[0] if isinstance(vp, tuple) else vp for vp in video_paths]
-                    todo = [fr if vp is not None and fr is not None and not os.path.exists(feature_cache_path(vp, self.video_encoder)) else None
-                            for vp, fr in zip(plain, video_frames)]
-                    done = {vp: e for vp, e in zip(plain, self._encode_video_frames(todo)) if e is not None}
-                    def encoder_fn(vp):
-                        if vp not in done:
-                            raise FileNotFoundError(f"{feature_cache_path(vp, self.video_encoder)}: no cached CLIP features and no frames for {vp}")
-                        return done[vp]
-                text_embed = encode_video_cached(video_paths, cond_seq_len, dim=cfgm.dim_text, video_encoder=self.video_encoder,
-                                                 sampling_rate=self.sampling_rate or 24000, frame_size=self.frame_size,
-                                                 encoder_fn=encoder_fn)
-            elif video_frames is not None:
-                if self._clip is None:
-                    raise RuntimeError("video_frames needs the CLIP image encoder: call load_image_encoder first")
-                if len(video_frames) != batch:
-                    raise ValueError(f"video_frames: {len(video_frames)} entries for a batch of {batch}")
-                from .features import resample_clip_features
-                rows = []
-                for e in self._encode_video_frames(list(video_frames)):
-                    rows.append(torch.zeros(cond_seq_len, cfgm.dim_text) if e is None else
-                                resample_clip_features(e[0], e[1], cond_seq_len, sampling_rate=self.sampling_rate or 24000,
-                                                       frame_size=self.frame_size))
-                text_embed = torch.stack(rows, 0)
-            elif torch.is_tensor(text) and text.ndim == 3:
-                text_embed = text
-            else:
-                raise NotImplementedError("pass video_paths (with cached .npz CLIP features), text_embed= (b, n, dim_text) "
-                                          "or video_encoder_fn=")
+            text_embed = self._clip_conditioning(text, video_paths, video_frames, batch, cond_seq_len)
         # -- duration (x3:2196-2216)
         if duration is None:
             duration = lens.clone()

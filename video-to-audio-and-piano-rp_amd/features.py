@@ -189,3 +189,30 @@ def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None
         if c is not None:
             out[i, : c.shape[0]] = c
     return out.permute(0, 4, 1, 2, 3).contiguous()
+
+
+# ---- MIDI ground truth of the V2P validation pass (x3:1852-1866) -------------------------------------------------------
+NOTE_MIN, NOTE_MAX = 15, 65          # x3:71-72 (`NOTTE_MIN`, `NOTE_MAX`): the 51 piano keys the roll covers
+
+
+def midi_ground_truth_path(video_path: str) -> str:
+    """x3:1852: the frame-level MIDI roll of a clip lies next to it."""
+    return video_path.replace(".mp4", ".3.npy")
+
+
+def load_midi_ground_truth(video_paths, l: int) -> torch.Tensor | None:
+    """x3:1852-1866: `<video>.3.npy` (frames, 88 keys) -> columns NOTE_MIN..NOTE_MAX as float32, zero padded or cut to `l` frames:
+    (b', l, 51) over the paths that are not None (tuples are (path, start_sample, max_sample)), or None when there is none.  This is
+    `midis` of `E2TTS.forward(val=True)`; `E2TTS.encode_video_frames` keeps returning zeros, as the reference's live branch does."""
+    rows = []
+    for vp in video_paths:
+        if vp is None:
+            continue
+        if isinstance(vp, tuple):
+            vp = vp[0]
+        gt = torch.from_numpy(np.load(midi_ground_truth_path(vp)).astype(np.float32))[:, NOTE_MIN:NOTE_MAX + 1]
+        out = torch.zeros(int(l), gt.shape[1])
+        k = min(int(l), gt.shape[0])
+        out[:k] = gt[:k]
+        rows.append(out)
+    return torch.stack(rows, 0) if rows else None
