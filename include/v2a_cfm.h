@@ -68,7 +68,8 @@ enum {
   V2A_EPI_STORE = 0,      /* out = acc + bias                                    */
   V2A_EPI_SIGMOID = 1,    /* out = sigmoid(acc + bias)            (AdaLNZero table) */
   V2A_EPI_GEGLU = 2,      /* W rows packed [16 value | 16 gate] per 16 outputs:
-                             out[m][j] = (acc_v + b_v) * gelu_erf(acc_g + b_g); out has N/2 cols */
+                             out[m][j] = (acc_v + b_v) * gelu_erf(acc_g + b_g); out has N/2 cols.  fp32 output: erff; bf16 and
+                             V2A_BF16_SPLIT (hi | lo plane) output: erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7 */
   V2A_EPI_RESID = 3,      /* out = resid + acc + bias             (text/frames streams, cross-condition) */
   V2A_EPI_GATE_RESID = 4, /* out = resid + gate[n] * (acc + bias) (AdaLNZero x3:546-551 + residual x3:1128) */
   V2A_EPI_GEGLU_TANH = 5, /* v2a_gemm_skinny_f32 only (v2a_gemm rejects it): the GEGLU row packing with value = wi_1, gate = wi_0,
@@ -150,8 +151,12 @@ typedef struct v2a_gemm_args {
    *   5 = the 256x256 phase-interleaved (8-phase) kernel: a stage = 32 logical k, staged as rows [32 k hi | 32 k lo] of both operands,
    *       three products (A_lo W_hi, A_hi W_lo, A_hi W_hi) from one set of fragments; dense rows only; every ka a multiple of 64;
    *   6 = 128x256, 7 = 128x128 (8 waves, 3-deep ring): a stage = 32 k of the four planes.
-   * With a_row_offset / out_row_offset only 0 and 1..4 are admitted (a_ktile_offset is laid out for 64-wide K tiles).  The sum order
-   * of an output element depends on the shape chosen, so results of different tile_hint values agree to rounding, not bit for bit. */
+   * With a_row_offset / out_row_offset only 0 and 1..4 are admitted (a_ktile_offset is laid out for 64-wide K tiles).  Every shape adds the
+   * three products of a 32-wide k step -- A_lo W_hi, A_hi W_lo, A_hi W_hi, in that order -- to one accumulator chain, k steps in ascending order,
+   * whether a stage holds 64 k (two steps) or 32: the sum order of an output element does not depend on the shape.  STORE (with or without
+   * fused RoPE) / RESID / GATE_RESID results, their shadows and norm_ssq are equal bit for bit on the ring shapes 1..4, 6, 7, and the fp32
+   * results of shape 5 (the 8-phase kernel forms the same products in the same order per 32 logical k) equal them too
+   * (tests/test_gemm_split_ring_gpu.py asserts both).  GEGLU / SWIGLU / GELU results agree to rounding only: their store forms may evaluate the activation differently. */
   int32_t tile_hint;
   /* RMSNorm folded into its neighbours (bf16 x bf16, 16-byte aligned epilogue operands, N % 32 == 0):
    * PRODUCER (RESID / GATE_RESID with out_bf16): with norm_gamma the shadow is out_bf16[m][n] = bf16(out[m][n] * gamma[n]),
@@ -172,7 +177,7 @@ typedef struct v2a_gemm_args {
   int32_t row_ssq_parts, row_norm_dim;
   /* non-zero: the out_bf16 shadow is written in the V2A_BF16_SPLIT layout, row m = [hi_0 .. hi_{N-1} | lo_0 .. lo_{N-1}] of the
    * (gamma-scaled, when norm_gamma is given) fp32 result, ld_out_bf16 >= 2 * N: the operand of a later split-bf16 GEMM without a
-   * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU and GELU epilogues only): out row m = [hi | lo] planes of the N/2
+   * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU, SWIGLU and GELU epilogues only): out row m = [hi | lo] planes of the N/2
    * hidden values, ldo >= N (GELU: of the N values, ldo >= 2N). */
   int32_t out_bf16_split;
   /* ABI 8, split operands / split shadow only.  a_lo_offset[s]: elements from the hi plane of a row of segment s to its lo plane; 0 = ka[s], the

@@ -729,7 +729,7 @@ def test_gemm_split_native(L, hint, epi, M, N, ks):
         assert torch.equal(sh.cpu(), _split_planes(out.cpu() * gam))
         torch.testing.assert_close(ssq.cpu().double(), (out.cpu().double() ** 2).reshape(M, N // 32, 32).sum(-1), rtol=1e-5, atol=1e-6)
     else:
-        # GEGLU: W rows regrouped [16 value | 16 gate]; output hi | lo planes of the N / 2 hidden values, exact erf GELU
+        # GEGLU: W rows regrouped [16 value | 16 gate]; output hi | lo planes of the N / 2 hidden values, erf GELU by gelu_fast_f (Abramowitz-Stegun erf, 1.5e-7 abs)
         half = N // 2
         perm = torch.cat([torch.cat([torch.arange(j * 16, j * 16 + 16), half + torch.arange(j * 16, j * 16 + 16)]) for j in range(half // 16)])
         wp, bp = w[perm], bias[perm]
