@@ -665,6 +665,44 @@ int v2a_masked_sqerr(const float* pred, const float* target, const uint8_t* mask
 int v2a_roll_metrics(const float* roll, const float* midis, const uint8_t* mask, int32_t B, int32_t T, int32_t notes, double* scratch,
                      double* out, v2a_stream_t stream);
 
+/* =====================================================================================
+ * Wave front end: the first channel of an audio file at any rate -> the 24 kHz, normalised wave the Encodec encoder reads
+ * (trainer_multigpus_alldatas3.py:1047-1050 and 1427-1431, torch_tools.py:53-56).  Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+/* Workgroup partials of v2a_wave_resample / v2a_wave_stats: `parts` holds V2A_WAVE_MAX_PARTS records of 16 bytes,
+ * { double sum; float min; float max; }, 8-byte aligned; the entry point stores in *n_parts (host) how many it wrote. */
+#define V2A_WAVE_MAX_PARTS 256
+/* LDS a resampler workgroup may take for its input window and the filter table together; a table that does not fit beside the
+ * window is read from global memory (same arithmetic, same bits). */
+#define V2A_WAVE_LDS_BYTES (128 * 1024)
+/* Largest filter table, n * K entries (16 MiB of fp32); wave.py refuses a rate pair above it before anything is allocated. */
+#define V2A_WAVE_TABLE_MAX (1 << 22)
+
+/* Polyphase sinc resampler.  o / n: input / output rate divided by their gcd; table (n, K) fp32, K = 2 * width + o, row p = the
+ * taps of output phase p (wave.py: sinc_resample_table).  For j = q * n + p < out_len = ceil(n * L / o):
+ *   y[j] = fma(xpad[q o + K - 1], table[p][K - 1], ... fma(xpad[q o + 1], table[p][1], fma(xpad[q o], table[p][0], 0)))
+ * with xpad[i] = x[i - width] inside the wave and 0 outside: fp32, one chain from k = 0 up, so a sample does not depend on the
+ * tiling of the launch nor on where the table was read from.  x (L) and y (out_len) fp32; nothing past y[out_len - 1] is written.
+ * `parts` / *n_parts: the partials of y, see above.  K <= 8192, n * K <= V2A_WAVE_TABLE_MAX.
+ * Replaces: `torchaudio.functional.resample(waveform, orig_freq, new_freq)` (trainer_multigpus_alldatas3.py:1048-1049, 1429-1430):
+ * `_get_sinc_resample_kernel` is the host table, `_apply_sinc_resample_kernel` (pad, conv1d of stride o, transpose, cut) this launch. */
+int v2a_wave_resample(const float* x, int64_t L, const float* table, int32_t o, int32_t n, int32_t K, int32_t width, float* y,
+                      int64_t out_len, void* parts, int32_t* n_parts, v2a_stream_t stream);
+/* The same partials for a wave x (n) that needs no resampling (orig_freq == new_freq).
+ * Replaces: the reductions of `torch.mean(waveform)` and `torch.max(torch.abs(waveform[0, :]))` (torch_tools.py:54-55). */
+int v2a_wave_stats(const float* x, int64_t n, void* parts, int32_t* n_parts, v2a_stream_t stream);
+/* With (sum, min, max) = the n_parts partials combined in index order (no atomics: two calls give the same bits):
+ *   m    = float(sum / n)                               the double sum divided in double, rounded once
+ *   peak = max(fl32(max - m), fl32(m - min))            = max_i |fl32(x[i] - m)|, rounding being monotonic
+ *   out[i] = ((x[i] - m) / (peak + 1e-8f)) * 0.5f       i < min(n, n_out): three rounded fp32 operations, IEEE division
+ *   out[i] = 0                                          n <= i < n_out
+ * and stats[0] = m, stats[1] = peak (device).  out is either x itself (in place) or does not overlap it.
+ * Replaces: `normalize_wav` (torch_tools.py:53-56) and the cut `waveform[:, :val_length * hop_size]` that follows it in the
+ * validation set (trainer_multigpus_alldatas3.py:1129-1134). */
+int v2a_wave_normalize(const float* x, int64_t n, const void* parts, int32_t n_parts, float* out, int64_t n_out, float* stats,
+                       v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

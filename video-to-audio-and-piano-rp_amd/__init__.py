@@ -16,8 +16,10 @@ from .t5 import T5Encoder  # noqa: F401
 from .clip import CLIPImageEncoder  # noqa: F401
 from .dinov2 import DINOv2ImageEncoder  # noqa: F401
 from .piano_frames import PianoFramePlan, PianoFramePreprocessor  # noqa: F401
+from .wave import WaveFrontEnd, sinc_resample_table  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
            "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "val_span_mask", "E2TTSReturn", "LossBreakdown", "load_midi_ground_truth", "expected_state_dict_shapes", "NOTES",
-           "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor"]
+           "Video2RollEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor",
+           "WaveFrontEnd", "sinc_resample_table"]

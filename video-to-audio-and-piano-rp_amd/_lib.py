@@ -115,6 +115,7 @@ EXPORTS = [
     "v2a_clip_resize_h", "v2a_clip_resize_v", "v2a_clip_embed_init", "v2a_clip_layernorm", "v2a_clip_attention",
     "v2a_elu_pad_lr", "v2a_encodec_stage0", "v2a_piano_resize_h", "v2a_piano_resize_v",
     "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode", "v2a_cfm_interp", "v2a_masked_sqerr", "v2a_roll_metrics",
+    "v2a_wave_resample", "v2a_wave_stats", "v2a_wave_normalize",
 ]
 
 
@@ -183,6 +184,9 @@ def _declare(lib):
     lib.v2a_cfm_interp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.v2a_masked_sqerr.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.v2a_roll_metrics.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.v2a_wave_resample.argtypes = [vp, i64, vp, i32, i32, i32, i32, vp, i64, vp, C.POINTER(i32), vp]
+    lib.v2a_wave_stats.argtypes = [vp, i64, vp, C.POINTER(i32), vp]
+    lib.v2a_wave_normalize.argtypes = [vp, i64, vp, i32, vp, i64, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int

@@ -32,6 +32,11 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
                      it (trainer_multigpus_alldatas3.py:271-290), on the ground-truth latents `<video>.latent.npy` (n, C) next to each video;
                      with --piano also the roll loss and the Video2Roll metrics against `<video>.3.npy`.  Prints one JSON line per batch:
                      loss, roll_loss, precision, recall, f1, acc.  One rank only; nothing is written.
+  --wav              (with --encodec) `<video>.wav` may have any sample rate: its first channel goes through the HIP wave front end
+                     (wave.py: resampled to 24 kHz and normalised as the reference's data path does on the CPU,
+                     trainer_multigpus_alldatas3.py:1047-1050, 1427-1431) into the HIP Encodec encoder.  Under --validate a video without
+                     `<video>.latent.npy` takes its ground truth from `<video>.wav` (an existing `.latent.npy` wins); under
+                     --audio-prompt-seconds the prompt is the first S seconds of the front end's output.
 The moviepy mux of audio and video stays outside (out of scope).
 """
 from __future__ import annotations
@@ -85,6 +90,45 @@ def read_audio_prompt(video_path: str, seconds: float) -> torch.Tensor:
     return wav[:nw].float().contiguous()
 
 
+def read_wave(path: str):
+    """--wav: the first channel of an audio file at whatever rate it has -> ((n,) float32, rate), read with torchaudio or soundfile."""
+    try:
+        import torchaudio
+        wav, rate = torchaudio.load(path)
+        wav = wav[0]
+    except ImportError:
+        try:
+            import soundfile
+        except ImportError as e:
+            raise RuntimeError("--wav reads <video>.wav with torchaudio or soundfile; neither is installed") from e
+        data, rate = soundfile.read(path, dtype="float32", always_2d=True)
+        wav = torch.from_numpy(data[:, 0].copy())
+    return wav.float().contiguous(), int(rate)
+
+
+def wave_prompt(model, video_path: str, seconds: float) -> torch.Tensor:
+    """--wav --audio-prompt-seconds: the first `seconds` of `<video>.wav` after the front end (24 kHz, normalised), (nw,) on the device."""
+    path = video_path.rsplit(".", 1)[0] + ".wav"
+    nw = int(round(24000 * seconds))
+    wav = model.wave_front_end()(*read_wave(path))
+    if wav.shape[0] < nw:
+        raise ValueError(f"{path}: {wav.shape[0]} samples at 24 000 Hz, --audio-prompt-seconds {seconds} needs {nw}")
+    return wav[:nw]
+
+
+def validation_sources(video_paths, wav: bool = False):
+    """--validate: where each clip's ground-truth latents come from, ("latent", `<video>.latent.npy`) or, with --wav and no such
+    file, ("wav", `<video>.wav`).  An existing `.latent.npy` wins; without --wav it is the only source, present or not."""
+    out = []
+    for vp in video_paths:
+        stem = vp.rsplit(".", 1)[0]
+        if wav and not os.path.exists(stem + ".latent.npy") and os.path.exists(stem + ".wav"):
+            out.append(("wav", stem + ".wav"))
+        else:
+            out.append(("latent", stem + ".latent.npy"))
+    return out
+
+
 def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None, video_encoder: str = "clip_vit"):
     """clip_encode: optional `video_path -> (image_embeds, duration)` that makes a missing `<video>.generated.npz` (--clip);
     video_encoder: which cache name is read and written (--video-encoder)."""
@@ -129,12 +173,20 @@ def piano_frames_for(video_paths, l: int, preprocess, decode):
     return load_piano_frames(video_paths, l, video_frames=[frames_of(vp) for vp in video_paths], preprocess=preprocess)
 
 
-def validate_batch(model, video_paths, extras, frames=None) -> dict:
+def validate_batch(model, video_paths, extras, frames=None, wav: bool = False) -> dict:
     """--validate: one `forward(val=True)` over a collated batch.  The ground-truth latents `<video>.latent.npy` (n, C) are zero
-    padded to the longest clip of the batch and `lens` holds their lengths; `frames`: the --piano stack of the same clips."""
+    padded to the longest clip of the batch and `lens` holds their lengths; `frames`: the --piano stack of the same clips.
+    wav (--wav): a clip without `.latent.npy` is encoded from `<video>.wav` by `E2TTS.encode_audio`, cut at the batch's n frames."""
     from .features import load_midi_ground_truth
-    lat = [torch.from_numpy(np.load(vp.rsplit(".", 1)[0] + ".latent.npy")).float() for vp in video_paths]
     n = extras["text_embed"].shape[1]
+    lat = []
+    for kind, path in validation_sources(video_paths, wav):
+        if kind == "wav":
+            w, rate = read_wave(path)
+            z, zl = model.encode_audio([w], [rate], max_frames=n)
+            lat.append(z[0, :int(zl[0])].cpu())
+        else:
+            lat.append(torch.from_numpy(np.load(path)).float())
     lens = torch.tensor([min(x.shape[0], n) for x in lat])
     inp = torch.stack([torch.nn.functional.pad(x[:n], (0, 0, 0, n - min(x.shape[0], n))) for x in lat])
     midis = None if frames is None else load_midi_ground_truth(video_paths, n)
@@ -183,6 +235,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --encodec: also write <name>.codes.npy, the int16 (n_q, n) Encodec codes of the clip at this bandwidth")
     ap.add_argument("--validate", action="store_true", help="instead of sampling, run the validation pass forward(val=True) on "
                     "<video>.latent.npy and print one JSON line per batch: loss, roll_loss, precision, recall, f1, acc")
+    ap.add_argument("--wav", action="store_true", help="with --encodec: <video>.wav at any sample rate goes through the HIP wave front end "
+                    "(resample to 24 kHz, normalize_wav) into the HIP Encodec encoder: the ground truth of --validate for a video without "
+                    "<video>.latent.npy, and the prompt of --audio-prompt-seconds")
     return ap
 
 
@@ -194,6 +249,9 @@ def main(argv=None):
 
     if a.codes is not None and not a.encodec:
         ap.error("--codes needs --encodec (the state dict that holds the quantizer's codebooks)")
+
+    if a.wav and not a.encodec:
+        ap.error("--wav needs --encodec (the state dict that holds the encoder)")
 
     if a.validate and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--validate runs on one rank")
@@ -248,7 +306,7 @@ def main(argv=None):
             except ImportError as e:
                 raise FileNotFoundError(f"{vp}: no cached CLIP features and moviepy is not installed to decode it for --clip") from e
             return cenc(frames).cpu(), duration
-    if a.audio_prompt_seconds > 0:                                   # a checkpoint without cond_proj_in.* was refused above
+    if a.audio_prompt_seconds > 0 or a.wav:                          # a checkpoint without cond_proj_in.* was refused above
         model.load_audio_encoder(torch.load(a.encodec, map_location="cpu"))
     vocoder = None
     if a.encodec and rank == 0:
@@ -274,11 +332,12 @@ def main(argv=None):
             decoded.clear()
             if a.validate:
                 import json
-                print(json.dumps(dict(batch=b0 // a.batch, **validate_batch(model, [vp for vp, _ in mine], extras, frames))), flush=True)
+                print(json.dumps(dict(batch=b0 // a.batch, **validate_batch(model, [vp for vp, _ in mine], extras, frames, a.wav))), flush=True)
                 continue
             cond, lens = batch8[1], batch8[3]
             if a.audio_prompt_seconds > 0:                           # raw waves (b, nw): sample() encodes them (x3:2157-2160)
-                cond = torch.stack([read_audio_prompt(vp, a.audio_prompt_seconds) for vp, _ in mine])
+                cond = torch.stack([wave_prompt(model, vp, a.audio_prompt_seconds) if a.wav else read_audio_prompt(vp, a.audio_prompt_seconds)
+                                    for vp, _ in mine])
                 lens = torch.full((len(mine),), -(-cond.shape[1] // 320), dtype=torch.int32)
             lat = model.sample(cond, lens=lens, duration=batch8[3], steps=a.steps, cfg_strength=a.cfg_strength,
                                remove_parallel_component=False, sway_sampling=True, video_drop_prompt=batch8[4],

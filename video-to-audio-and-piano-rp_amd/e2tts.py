@@ -233,6 +233,7 @@ class E2TTS:
         self._clip = None                         # optional image encoder (load_image_encoder: CLIP x3:1423-1425 or DINOv2 x3:1432-1433)
         self._audio_encoder = None                # optional Encodec encoder behind a raw-wave cond (load_audio_encoder, x3:1350)
         self._audio_quantizer = None              # optional Encodec quantizer behind an integer cond of codes (load_audio_quantizer)
+        self._wave_front_end = None               # resample + normalize_wav in front of the audio encoder (encode_audio), made on first use
         self._piano_pre = None                    # piano-frame preprocessor of this device (piano_frame_preprocessor, x3:1877-1891)
         L.lib()  # no library -> no sampler
 
@@ -386,6 +387,36 @@ class E2TTS:
         self._audio_encoder = enc
         self.mel_spec = lambda wave: enc.encoder(wave.unsqueeze(1))
         return enc
+
+    def wave_front_end(self):
+        """The `WaveFrontEnd` in front of the audio encoder: any rate -> the model's rate, `normalize_wav`; made on first use."""
+        from .wave import WaveFrontEnd
+        dev = self._audio_encoder.dev if self._audio_encoder is not None else torch.device(self._device)
+        if self._wave_front_end is None or self._wave_front_end.dev != dev:
+            self._wave_front_end = WaveFrontEnd(dev, new_freq=self.sampling_rate or 24000)
+        return self._wave_front_end
+
+    def encode_audio(self, waves, rates, max_frames=None, normalize=True):
+        """Audio as it comes out of a file -> ground-truth / prompt latents, all on the device: what the reference's data path does on
+        the CPU in front of the model (trainer_multigpus_alldatas3.py:1047-1050, 1129-1134, 1427-1432).  waves: a list of (n_i,) or
+        (channels, n_i) waves, of which channel 0 is taken; rates: their sample rates (one int for all).  Each goes through the
+        `WaveFrontEnd` (resampled to the model's rate, `normalize_wav` unless normalize=False, cut to max_frames * hop samples -- the
+        validation set's `val_length`) straight into the `EncodecEncoder` of `load_audio_encoder`.
+        -> (latents (b, n, C) fp32 on the device, zero behind each clip's frames; lens (b,) int64 on the host)."""
+        if self._audio_encoder is None:
+            raise RuntimeError("encode_audio needs the Encodec encoder: load_audio_encoder(state_dict)")
+        enc = self._audio_encoder
+        rates = [int(rates)] * len(waves) if isinstance(rates, (int, float)) else [int(r) for r in rates]
+        if len(rates) != len(waves) or not waves:
+            raise ValueError(f"encode_audio: {len(waves)} waves, {len(rates)} rates")
+        fe = self.wave_front_end()
+        cut = None if max_frames is None else int(max_frames) * enc.hop
+        lat = enc.encode_list([fe(w, r, normalize=normalize, max_samples=cut) for w, r in zip(waves, rates)])      # (C, T_i) each
+        lens = torch.tensor([z.shape[1] for z in lat], dtype=torch.long)
+        out = torch.zeros(len(lat), int(lens.max()), lat[0].shape[0], dtype=torch.float32, device=enc.dev)
+        for i, z in enumerate(lat):
+            out[i, :z.shape[1]] = z.t()
+        return out, lens
 
     def load_audio_quantizer(self, src):
         """The Encodec quantizer behind an integer `cond` of codes (b, n_q, n) -- the layout of `EncodecModel.encode`'s audio_codes[0] --
