@@ -307,11 +307,15 @@ int v2a_attention(const v2a_attn_args* args, v2a_stream_t stream);
 int v2a_qproj_xattn(const v2a_gemm_args* gemm, const v2a_attn_args* attn, v2a_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
- * Small fp32 linear with output row scatter (K arbitrary, VALU):
+ * Small fp32 linear with output row scatter (1 <= K <= 2048, VALU; V2A_ERR_ARG beyond):
  *   out[(m / T)*out_batch_stride + (row_off + m % T)*d + n] =
  *        bias[n] + add[(m % T)*d + n] + sum_k a[m*K + k] * wt[k*d + n]
  * and, when `dup_batch_offset` > 0, the same value again at batch (m/T + dup_batch_offset)
  * (cond and null CFG halves share proj_in(x) + abs_pos_emb).
+ * Two launch forms, both with the block's A rows in dynamic LDS at 8 * K bytes per row: 8 rows per block when that gives at least
+ * 512 blocks (ceil(rows / 8) * (M / T), rows = T plus the register rows), else 2 rows per block.  The 2-row form stays within 32 KB at
+ * every K; the 8-row form takes 64 KB at K = 1024 and, for K in (1024, 2048], up to 128 KB, for which it raises the kernel's dynamic
+ * LDS limit once per device (V2A_ERR_LAUNCH if the device refuses).  The two forms are not required to agree in the last bits of a sum.
  * Replaces: proj_in x3:2027 + abs_pos_emb x3:957-960 + register pack x3:975-976;
  * proj_frames x3:2069.
  * ------------------------------------------------------------------------------------- */

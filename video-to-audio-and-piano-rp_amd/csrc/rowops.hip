@@ -856,8 +856,16 @@ extern "C" int v2a_linear_small(const float* a, int64_t M, int32_t K, const floa
   const int rows = (regs ? row_off : 0) + T;
   const int64_t nb8 = (int64_t)((rows + 7) / 8) * (M / T);
   if (nb8 >= 512) {
+    // 8 rows of (a, a) pairs are 64 * K bytes of dynamic LDS: past K = 1024 that is more than the 64 KB a kernel gets without opting in
+    // (128 KB at the largest K), so the limit is raised once per device as for the dwconv streaming kernel.  The MI355X runtime was
+    // measured to launch K = 1032 and 2048 without it; the launch no longer depends on that
+    const size_t smem = 2 * 8 * (size_t)K * sizeof(float);
+    if (smem > 64 * 1024) {
+      static std::atomic<uint64_t> lds_set{0};
+      if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(linear_small_kernel<8>), 2 * 8 * 2048 * sizeof(float), lds_set, "v2a_linear_small")) return rc;
+    }
     dim3 grid((unsigned)((rows + 7) / 8), (unsigned)(M / T)), block(256);
-    hipLaunchKernelGGL((linear_small_kernel<8>), grid, block, 2 * 8 * K * sizeof(float), (hipStream_t)stream, a, K, wt, bias, add,
+    hipLaunchKernelGGL((linear_small_kernel<8>), grid, block, smem, (hipStream_t)stream, a, K, wt, bias, add,
                        T, out, obs, row_off, d, dup, regs, (bf16_t*)out_bf16);
   // (4-row blocks -- 196 blocks, one round at one clip -- measured 27 us against 16.5 us for the 391 blocks of 2 rows: the block time is
   // the latency chain of its K weight-row loads, and more blocks per CU overlap more of it)
