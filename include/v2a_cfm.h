@@ -707,6 +707,36 @@ int v2a_wave_stats(const float* x, int64_t n, void* parts, int32_t* n_parts, v2a
 int v2a_wave_normalize(const float* x, int64_t n, const void* parts, int32_t n_parts, float* out, int64_t n_out, float* stats,
                        v2a_stream_t stream);
 
+/* =====================================================================================
+ * Roll2Midi generator: the U-Net behind the Video2Roll key roll (`r2m` = src/audeo/Roll2MidiNet.py:42-87, run as in
+ * Roll2Midi_inference.py:51-71).  Every convolution is 3x3 / stride 1 / pad 1, so all maps share one (n, H, W) pixel grid and each
+ * of them is a v2a_gemm (eval-mode BatchNorm folded in, the transposed convolutions r2m:27 as plain ones with flipped, transposed
+ * weights).  The three kernels below do what v2a_gemm cannot.  They address a CHANNEL SLICE of an NHWC fp32 map that may carry a
+ * zero border of `border` pixels: pixel (i, y, x) of the slice starts at
+ *   base + ((i*(H + 2*border) + y + border)*(W + 2*border) + x + border) * pitch,
+ * base = the map + the slice's channel offset, pitch = the channels of the whole map (a multiple of 8; base 16-byte aligned).
+ * A shadow is the copy the next convolution's GEMM reads, at the same offsets from `shadow`: shadow_mode 0 = none (shadow NULL),
+ * 1 = bf16, 2 = V2A_BF16_SPLIT planes, hi = bf16(v) and, lo_offset elements further (>= the hi map, a multiple of 8), lo =
+ * bf16(v - hi).  Only interiors are written: the caller zeroes the borders once.  Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+/* down1 (r2m:46, 62): roll x (n, H, W) fp32 -> co channels (co % 8 == 0), 3x3 / pad 1, no bias, LeakyReLU(0.2).  wt is [9][co]
+ * fp32, tap = ky*3 + kx.  Per output one chain acc = fma(wt[tap][c], x[y + ky - 1][x + kx - 1], acc) from tap 0 up (zero outside
+ * the roll), then acc > 0 ? acc : 0.2f * acc.  K = 9 does not fill a K tile of v2a_gemm. */
+int v2a_roll2midi_stem(const float* x, const float* wt, int32_t n, int32_t H, int32_t W, int32_t co, float* out, void* shadow,
+                       int32_t shadow_mode, int64_t lo_offset, int64_t pitch, int32_t border, v2a_stream_t stream);
+/* x = x > 0 ? x : 0.2f * x in place on the C channels (C % 8 == 0) of a slice, and the shadow of the result: the nn.LeakyReLU(0.2)
+ * of down2..down6 (r2m:13), which no epilogue of v2a_gemm has.  leaky(0) = 0: a zero border stays zero without being touched. */
+int v2a_leaky_shadow(float* x, void* shadow, int32_t shadow_mode, int64_t lo_offset, int32_t n, int32_t H, int32_t W, int32_t C,
+                     int64_t pitch, int32_t border, v2a_stream_t stream);
+/* conv1d + sigmoid (r2m:58, 84-86) and the threshold of Roll2Midi_inference.py:65 per pixel of two slices with one geometry, u
+ * (nu channels of up5) and d (nd channels of down1), nu and nd multiples of 4, w (nu + nd) fp32:
+ *   z = fma(w[nu + nd - 1], d[nd - 1], ... fma(w[nu], d[0], fma(w[nu - 1], u[nu - 1], ... fma(w[0], u[0], bias))))
+ *   logits[i] = z,  probs[i] = 1 / (1 + expf(-z)),  midi[i] = probs[i] >= threshold        dense (n, H, W); NULL = not written */
+int v2a_roll2midi_head(const float* u, int64_t u_pitch, int32_t nu, const float* d, int64_t d_pitch, int32_t nd, const float* w,
+                       float bias, float threshold, int32_t n, int32_t H, int32_t W, int32_t border, float* logits, float* probs,
+                       uint8_t* midi, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,7 @@ EXPORTS = [
     "v2a_elu_pad_lr", "v2a_encodec_stage0", "v2a_piano_resize_h", "v2a_piano_resize_v",
     "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode", "v2a_cfm_interp", "v2a_masked_sqerr", "v2a_roll_metrics",
     "v2a_wave_resample", "v2a_wave_stats", "v2a_wave_normalize",
+    "v2a_roll2midi_stem", "v2a_leaky_shadow", "v2a_roll2midi_head",
 ]
 
 
@@ -187,6 +188,9 @@ def _declare(lib):
     lib.v2a_wave_resample.argtypes = [vp, i64, vp, i32, i32, i32, i32, vp, i64, vp, C.POINTER(i32), vp]
     lib.v2a_wave_stats.argtypes = [vp, i64, vp, C.POINTER(i32), vp]
     lib.v2a_wave_normalize.argtypes = [vp, i64, vp, i32, vp, i64, vp, vp]
+    lib.v2a_roll2midi_stem.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, vp]
+    lib.v2a_leaky_shadow.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, i64, i32, vp]
+    lib.v2a_roll2midi_head.argtypes = [vp, i64, i32, vp, i64, i32, vp, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -591,6 +595,29 @@ def roll_head(args: "RollHeadArgs"):
 
 def roll_expand(roll, out, *, B, t, notes, rep, l):
     check(lib().v2a_roll_expand(roll.data_ptr(), out.data_ptr(), B, t, notes, rep, l, stream_ptr()))
+
+
+# ---- Roll2Midi generator (roll2midi.py) ----------------------------------------------------------
+SH_NONE, SH_BF16, SH_SPLIT = 0, 1, 2      # shadow modes of v2a_roll2midi_stem / v2a_leaky_shadow
+
+
+def roll2midi_stem(x, wt, out, shadow, *, n, H, W, co, shadow_mode, lo_offset, pitch, border):
+    """x (n, H, W) fp32 roll -> the co channels of down1 in the slice that starts at `out` (and its shadow at `shadow`)."""
+    _launch("roll2midi_stem", 18.0 * n * H * W * co, n * H * W * (4.0 + co * (4 + 2 * shadow_mode)),
+            lambda: lib().v2a_roll2midi_stem(x.data_ptr(), wt.data_ptr(), n, H, W, co, out.data_ptr(), _p(shadow), shadow_mode, lo_offset,
+                                             pitch, border, stream_ptr()))
+
+
+def leaky_shadow(x, shadow, *, n, H, W, C_, shadow_mode, lo_offset, pitch, border):
+    """LeakyReLU(0.2) in place on the slice that starts at `x`, and the shadow of the result."""
+    _launch("leaky_shadow", 0.0, n * H * W * C_ * (8.0 + 2 * shadow_mode),
+            lambda: lib().v2a_leaky_shadow(x.data_ptr(), _p(shadow), shadow_mode, lo_offset, n, H, W, C_, pitch, border, stream_ptr()))
+
+
+def roll2midi_head(u, d, w, *, u_pitch, nu, d_pitch, nd, bias, threshold, n, H, W, border, logits=None, probs=None, midi=None):
+    _launch("roll2midi_head", 2.0 * n * H * W * (nu + nd), n * H * W * (4.0 * (nu + nd) + 9),
+            lambda: lib().v2a_roll2midi_head(u.data_ptr(), u_pitch, nu, d.data_ptr(), d_pitch, nd, w.data_ptr(), float(bias), float(threshold),
+                                             n, H, W, border, _p(logits), _p(probs), _p(midi), stream_ptr()))
 
 
 # ---- N1: Encodec decoder (vocoder) ---------------------------------------------------------------

@@ -37,6 +37,10 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
                      trainer_multigpus_alldatas3.py:1047-1050, 1427-1431) into the HIP Encodec encoder.  Under --validate a video without
                      `<video>.latent.npy` takes its ground truth from `<video>.wav` (an existing `.latent.npy` wins); under
                      --audio-prompt-seconds the prompt is the first S seconds of the front end's output.
+  --roll2midi CKPT   (with --piano) the Roll2Midi generator of the reference's Audeo chain (src/audeo/Roll2MidiNet.py, run as in
+                     Roll2Midi_inference.py): a torch-saved checkpoint holding `state_dict_G`, or that state dict.  The per-frame key
+                     probabilities of the Video2Roll encoder go through it on the GPU and `<name>.midi.npz` is written next to each output:
+                     `midi` (t, 51) uint8, the reference's key name (Roll2Midi_inference.py:79), and `prob` (t, 51) float32.
 The moviepy mux of audio and video stays outside (out of scope).
 """
 from __future__ import annotations
@@ -238,7 +242,22 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--wav", action="store_true", help="with --encodec: <video>.wav at any sample rate goes through the HIP wave front end "
                     "(resample to 24 kHz, normalize_wav) into the HIP Encodec encoder: the ground truth of --validate for a video without "
                     "<video>.latent.npy, and the prompt of --audio-prompt-seconds")
+    ap.add_argument("--roll2midi", default=None, metavar="CKPT", help="with --piano: checkpoint (or state dict) of the Roll2Midi generator "
+                    "(`state_dict_G`): also write <name>.midi.npz with `midi` (t, 51) uint8 and `prob` (t, 51) float32 per video frame")
+    ap.add_argument("--roll2midi-dtype", default="bf16x3", choices=["fp32", "bf16", "bf16x3"], help="compute mode of the Roll2Midi generator")
     return ap
+
+
+def write_midi_rolls(model, frames, video_paths, out_dir) -> list:
+    """--roll2midi: `E2TTS.frames_to_midi` over the --piano stack of a batch -> `<out_dir>/<name>.midi.npz` per clip."""
+    probs, midi = model.frames_to_midi(frames)
+    probs, midi = probs.cpu().numpy(), midi.cpu().numpy()
+    paths = []
+    for i, vp in enumerate(video_paths):
+        name = vp.rsplit("/", 1)[-1].rsplit(".", 1)[0]
+        paths.append(os.path.join(out_dir, name + ".midi.npz"))
+        np.savez(paths[-1], midi=midi[i], prob=probs[i])
+    return paths
 
 
 def main(argv=None):
@@ -252,6 +271,9 @@ def main(argv=None):
 
     if a.wav and not a.encodec:
         ap.error("--wav needs --encodec (the state dict that holds the encoder)")
+
+    if a.roll2midi and not a.piano:
+        ap.error("--roll2midi needs --piano (the frames the Video2Roll encoder reads)")
 
     if a.validate and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--validate runs on one rank")
@@ -276,6 +298,8 @@ def main(argv=None):
     res = model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # predict.py:161-168
     if res.missing_keys:
         raise RuntimeError(f"checkpoint lacks {len(res.missing_keys)} parameters of the sampled path, e.g. {res.missing_keys[0]}")
+    if a.roll2midi:
+        model.load_roll2midi(a.roll2midi, compute=a.roll2midi_dtype)
     t5_encode = None
     if a.t5 and a.t5_engine == "hip":
         from .t5 import T5Encoder
@@ -330,6 +354,8 @@ def main(argv=None):
                 # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
                 frames = piano_frames_for([vp for vp, _ in mine], int(batch8[3].max()), model.piano_frame_preprocessor(), decode)
             decoded.clear()
+            if a.roll2midi and frames is not None and not a.validate:
+                written += write_midi_rolls(model, frames, [vp for vp, _ in mine], a.out_dir)
             if a.validate:
                 import json
                 print(json.dumps(dict(batch=b0 // a.batch, **validate_batch(model, [vp for vp, _ in mine], extras, frames, a.wav))), flush=True)

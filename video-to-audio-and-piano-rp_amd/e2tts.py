@@ -235,6 +235,7 @@ class E2TTS:
         self._audio_quantizer = None              # optional Encodec quantizer behind an integer cond of codes (load_audio_quantizer)
         self._wave_front_end = None               # resample + normalize_wav in front of the audio encoder (encode_audio), made on first use
         self._piano_pre = None                    # piano-frame preprocessor of this device (piano_frame_preprocessor, x3:1877-1891)
+        self._r2m = None                          # optional Roll2Midi generator behind frames_to_midi (load_roll2midi)
         L.lib()  # no library -> no sampler
 
     # ---- nn.Module-like surface used by the callers (predict.py:156-170) -------------------
@@ -345,6 +346,37 @@ class E2TTS:
         if stack is None:
             return None, None
         return stack, torch.zeros(stack.shape[0], int(l), self.cfg.notes)
+
+    def _video2roll(self):
+        if self._v2r is None:
+            from .video2roll import Video2RollEngine
+            self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute)
+        return self._v2r
+
+    def load_roll2midi(self, src, **kw):
+        """The Roll2Midi generator behind `frames_to_midi` (src/audeo/Roll2MidiNet.py, run as in Roll2Midi_inference.py): a
+        `Roll2MidiEngine`, a state dict in the layout of the reference's `checkpoint['state_dict_G']`, a checkpoint dict holding
+        `state_dict_G`, or a path to a torch-saved one of either.  `kw` go to the engine's constructor (compute, chunk)."""
+        from .roll2midi import Roll2MidiEngine
+        if isinstance(src, Roll2MidiEngine):
+            self._r2m = src
+            return src
+        if isinstance(src, (str, Path)):
+            src = torch.load(str(src), map_location="cpu")
+        if not isinstance(src, dict):
+            raise TypeError(f"load_roll2midi: a Roll2MidiEngine, a state dict, a checkpoint dict or a path, got {type(src).__name__}")
+        self._r2m = Roll2MidiEngine(src.get("state_dict_G", src), self._device, **kw)
+        return self._r2m
+
+    def frames_to_midi(self, frames, window: int = 100, threshold: float = 0.5, tail: str = "own"):
+        """(b, 1, t, 100, 900) grey piano frames -> (probs (b, t, 51) fp32, midi (b, t, 51) uint8) at the video frame rate: the
+        Video2Roll encoder's per-frame key probabilities refined by the Roll2Midi generator, `midi = probs >= threshold`
+        (`Roll2MidiEngine.refine`).  Both networks run on the device with no host visit between them."""
+        if self._v2r_sd is None:
+            raise NotImplementedError("frames_to_midi needs the Video2Roll encoder: load a checkpoint holding `video2roll_net.*` (load_state_dict)")
+        if self._r2m is None:
+            raise NotImplementedError("frames_to_midi needs the Roll2Midi generator: load_roll2midi(state_dict_G, a checkpoint holding it, or its path)")
+        return self._r2m.refine(self._video2roll().frame_probs(frames), window=window, threshold=threshold, tail=tail)
 
     def piano_frame_preprocessor(self):
         """The `PianoFramePreprocessor` of this model's device (made on first use)."""

@@ -1,0 +1,343 @@
+"""Roll2Midi generator on the MI355X kernels: the U-Net that turns a Video2Roll key roll into the MIDI roll.
+
+Mirrors `Generator` of src/audeo/Roll2MidiNet.py:42-87 (`r2m` below) in eval mode and the way Roll2Midi_inference.py:36-71
+runs it: 100-frame windows of key probabilities (1, keys, w) -> probabilities of the same shape, thresholded at 0.5.
+
+Design (not a translation of the reference's NCHW module tree):
+  * every convolution of the net is 3x3 / stride 1 / pad 1, so all maps share one (n, keys, w) pixel grid, stored NHWC fp32;
+  * each convolution is one `v2a_gemm` with the eval-mode BatchNorm (eps = 0.8: `nn.BatchNorm2d(c, 0.8)`, r2m:12,28) folded into
+    weight / bias; a `ConvTranspose2d(ci, co, 3, 1, 1)` (r2m:27) is the plain convolution with w'[co][ci][ky][kx] =
+    w[ci][co][2-ky][2-kx], transformed once at load time; ReLU of the up blocks in the GEMM epilogue;
+  * bf16 / bf16x3: implicit GEMM over zero-bordered maps (offset tables, no patch matrix).  The skip concatenations (r2m:38) are
+    never materialised: up_k writes channels [0, co) of the concatenated map and d_k was written once into channels [co, co + skip)
+    of that same map, from where down_{k+1} reads it as a channel slice (the tables are plain element offsets);
+  * fp32: explicit `v2a_im2col` patch matrices and the exact-fp32 GEMM; a concatenated input is two A segments of one GEMM;
+  * three row kernels complete it (csrc/roll2midi.hip): `v2a_roll2midi_stem` (down1: K = 9 fills no K tile), `v2a_leaky_shadow`
+    (LeakyReLU(0.2), which the GEMM epilogue lacks, + the bf16 / hi | lo copy the next GEMM reads) and `v2a_roll2midi_head`
+    (conv1d 80 -> 1 + sigmoid + threshold).
+There is no CPU fallback: without libv2a_cfm.so every call raises.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+
+KEYS = 51
+BN_EPS = 0.8                # nn.BatchNorm2d(out_size, 0.8): the second positional argument is eps (r2m:12,28)
+LEAKY = 0.2
+_DOWN = ((1, 64), (64, 128), (128, 256), (256, 512), (512, 1024), (1024, 1024))             # down1..down6: (ci, co)   r2m:46-51
+_UP = ((1024, 512), (1024 + 512, 256), (512 + 256, 128), (256 + 128, 64), (128 + 64, 16))   # up1..up5: (ci, co)       r2m:53-57
+UP5_PAD = 64                # up5's 16 output channels as a GEMM of 64 (zero weight rows): the head reads the first 16
+
+
+def expected_state_dict_shapes() -> dict[str, tuple]:
+    """Key layout of `Generator((1, 51, 100)).state_dict()`, the reference's `checkpoint['state_dict_G']`."""
+    s: dict[str, tuple] = {}
+
+    def bn(p, c):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            s[f"{p}.{k}"] = (c,)
+        s[f"{p}.num_batches_tracked"] = ()
+
+    for i, (ci, co) in enumerate(_DOWN, 1):
+        s[f"down{i}.model.0.weight"] = (co, ci, 3, 3)
+        if i > 1:
+            bn(f"down{i}.model.1", co)
+    for i, (ci, co) in enumerate(_UP, 1):
+        s[f"up{i}.model.0.weight"] = (ci, co, 3, 3)          # ConvTranspose2d: [in][out][ky][kx]
+        bn(f"up{i}.model.1", co)
+    s["conv1d.weight"] = (1, 80, 1, 1)
+    s["conv1d.bias"] = (1,)
+    return s
+
+
+def check_state_dict(sd: dict) -> None:
+    if any(k.startswith("att") for k in sd):
+        raise NotImplementedError("Roll2MidiEngine: the state dict holds attention gates (att1.* ...): that is Roll2MidiNet_enhance.py, "
+                                  "which has no HIP path; only the plain Generator of Roll2MidiNet.py is built")
+    want = expected_state_dict_shapes()
+    missing = [k for k in want if k not in sd and not k.endswith("num_batches_tracked")]
+    if missing:
+        raise KeyError(f"Roll2MidiEngine: state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
+    bad = [k for k, shp in want.items() if k in sd and not k.endswith("num_batches_tracked") and tuple(sd[k].shape) != tuple(shp)]
+    if bad:
+        raise ValueError(f"Roll2MidiEngine: shape mismatch for {bad[:4]}")
+
+
+def transposed_conv_weight(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d(ci, co, 3, stride 1, pad 1) weight [ci][co][ky][kx] -> the Conv2d(ci, co, 3, 1, 1) weight of the same map."""
+    return w.permute(1, 0, 2, 3).flip(2, 3).contiguous()
+
+
+def folded_conv(sd: dict, name: str) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """Block `name` (down1..6, up1..5) as a plain convolution: fp32 weight [co][ci][3][3] with the BatchNorm scale folded in, and the
+    folded shift as bias (None for down1, which has neither BatchNorm nor bias)."""
+    w = sd[f"{name}.model.0.weight"].float()
+    if name.startswith("up"):
+        w = transposed_conv_weight(w)
+    bn = f"{name}.model.1"
+    if f"{bn}.weight" not in sd:
+        return w, None
+    s = sd[f"{bn}.weight"].float() / torch.sqrt(sd[f"{bn}.running_var"].float() + BN_EPS)
+    return w * s[:, None, None, None], sd[f"{bn}.bias"].float() - sd[f"{bn}.running_mean"].float() * s
+
+
+def gemm_weight(w: torch.Tensor, segments: tuple[int, ...] | None = None, pad_to: int = 0) -> torch.Tensor:
+    """[co][ci][3][3] -> GEMM rows [co][K], K in (ky, kx, c) order (NHWC sources).  segments (fp32 mode): the input channels are the
+    concatenation of maps with these widths, each its own patch matrix: K = [(ky, kx, c of map 0) | (ky, kx, c of map 1) ...]."""
+    co = w.shape[0]
+    parts, c0 = [], 0
+    for c in segments or (w.shape[1],):
+        parts.append(w[:, c0:c0 + c].permute(0, 2, 3, 1).reshape(co, -1))
+        c0 += c
+    assert c0 == w.shape[1]
+    wk = torch.cat(parts, 1)
+    if pad_to > co:
+        wk = torch.cat([wk, torch.zeros(pad_to - co, wk.shape[1])], 0)
+    return wk.contiguous()
+
+
+def slice_conv_tables(n, H, W, src_pitch, src_off, ci, dst_pitch, border=1, device="cpu"):
+    """Offset tables (elements, int32) of a 3x3 / pad 1 convolution for v2a_gemm's implicit-GEMM mode, reading the ci channels at
+    channel offset src_off of a bordered NHWC map of src_pitch channels and writing into a bordered map of dst_pitch channels.
+    The A pointer is map + src_off and the out pointer map + the destination slice's offset, so the tables hold pixel offsets only:
+    a_row[m] = the top-left tap of output pixel m, a_k[kt] = (ky*Wp + kx)*src_pitch + c0, o_row[m] = the interior pixel m."""
+    assert border >= 1, "the source map's zero border must cover the convolution's padding"
+    assert ci % 64 == 0 and src_off % 8 == 0 and src_pitch % 8 == 0 and dst_pitch % 8 == 0, "whole 64-element K tiles, 16-byte aligned slices"
+    assert src_off + ci <= src_pitch
+    Hp, Wp = H + 2 * border, W + 2 * border
+    ni = torch.arange(n, device=device, dtype=torch.int64)[:, None, None]
+    yo = torch.arange(H, device=device, dtype=torch.int64)[None, :, None]
+    xo = torch.arange(W, device=device, dtype=torch.int64)[None, None, :]
+    a_row = ((ni * Hp + yo + border - 1) * Wp + xo + border - 1) * src_pitch
+    k0 = torch.arange(0, 9 * ci, 64, device=device, dtype=torch.int64)
+    tap, c0 = k0 // ci, k0 % ci
+    a_k = ((tap // 3) * Wp + tap % 3) * src_pitch + c0
+    o_row = ((ni * Hp + yo + border) * Wp + xo + border) * dst_pitch
+    # every 64-element read of the hi plane stays inside the map (the lo plane starts one whole map further)
+    assert src_off + int(a_row.max()) + int(a_k.max()) + 64 <= n * Hp * Wp * src_pitch < 2 ** 31
+    assert int(o_row.max()) + dst_pitch <= n * Hp * Wp * dst_pitch < 2 ** 31
+    i32 = lambda t: t.reshape(-1).to(torch.int32).contiguous()
+    return i32(a_row), i32(a_k), i32(o_row)
+
+
+def window_spans(t: int, window: int) -> list[tuple[int, int]]:
+    """[start, stop) of the windows `refine` cuts t frames into: whole windows, then the shorter rest."""
+    return [(s, min(s + window, t)) for s in range(0, t, window)]
+
+
+class _Slice:
+    """C channels at channel offset `off` of an NHWC fp32 map (n, H + 2b, W + 2b, pitch) and of its shadow."""
+    __slots__ = ("f32", "sh", "off", "C", "pitch", "plane")
+
+    def __init__(self, f32, sh, off, C):
+        self.f32, self.sh, self.off, self.C = f32, sh, off, C
+        self.pitch, self.plane = f32.shape[-1], f32.numel()
+
+    def base(self):
+        return self.f32.view(-1)[self.off:]
+
+    def shadow(self):
+        return None if self.sh is None else self.sh.view(-1)[self.off:]
+
+    def nchw(self, border, C=None):
+        v = self.f32 if border == 0 else self.f32[:, border:-border, border:-border]
+        return v[..., self.off:self.off + (C or self.C)].permute(0, 3, 1, 2)
+
+
+class Roll2MidiEngine:
+    """`Generator` of Roll2MidiNet.py in eval mode on HIP kernels.
+
+    sd: the reference's `checkpoint['state_dict_G']` (or pass prefix=).  compute: "bf16" (bf16 MFMA operands, fp32 accumulate /
+    activations), "bf16x3" (split-bf16 hi | lo planes on both sides, three MFMA products per fp32 product: the parity mode at
+    implicit-GEMM speed; default) or "fp32" (exact-fp32 MFMA over explicit patch matrices).
+    chunk: windows per pass.  Default 8 in the bf16 / bf16x3 modes (no patch matrix; the maps of a 51x100 window take 87 MB in fp32
+    plus 44 / 87 MB of shadows) and 2 in fp32 mode (the patch matrices of up2, K = 13 824, take 282 MB per window).  A window's
+    output does not depend on the chunk it ran in."""
+
+    def __init__(self, sd, device="cuda:0", compute="bf16x3", prefix="", chunk=None):
+        L.lib()                                                   # fail loudly without the HIP library
+        if compute not in ("bf16", "bf16x3", "fp32"):
+            raise ValueError(f"compute must be 'bf16', 'bf16x3' or 'fp32', got {compute!r}")
+        self.dev = torch.device(device)
+        self.compute = compute
+        self.split = compute == "bf16x3"
+        self.implicit = compute != "fp32"
+        self.code = L.F32 if compute == "fp32" else L.BF16
+        self.mode = L.SH_NONE if compute == "fp32" else (L.SH_SPLIT if self.split else L.SH_BF16)
+        self.chunk = int(chunk) if chunk else (8 if self.implicit else 2)
+        sd = {k[len(prefix):]: v.detach().cpu() for k, v in sd.items() if k.startswith(prefix)}
+        check_state_dict(sd)
+        dev = self.dev
+        self.w, self.bias = {}, {}
+        for name, segs, pad in self._layers():
+            w, b = folded_conv(sd, name)
+            wk = gemm_weight(w, None if self.implicit else segs, pad)
+            if pad and b is not None:
+                b = torch.cat([b, torch.zeros(pad - b.shape[0])])
+            self.w[name] = (L.split_planes(wk) if self.split else wk.to(torch.bfloat16 if self.implicit else torch.float32)).to(dev).contiguous()
+            self.bias[name] = None if b is None else b.to(dev).contiguous()
+        self.stem_wt = folded_conv(sd, "down1")[0].reshape(64, 9).t().contiguous().to(dev)        # [tap][co]
+        self.head_w = sd["conv1d.weight"].float().reshape(80).contiguous().to(dev)
+        self.head_b = float(sd["conv1d.bias"].float()[0])
+        self._bufs: dict = {}
+        self._tabs: dict = {}
+
+    @staticmethod
+    def _layers():
+        """(block, widths of the concatenated inputs, padded output width) of the convolutions that run as GEMMs."""
+        out = [(f"down{i}", (ci,), 0) for i, (ci, _) in enumerate(_DOWN, 1) if i > 1]
+        skips = (0, 1024, 512, 256, 128)                            # d5, d4, d3, d2 behind up1..up4's outputs (r2m:74-82)
+        for i, (ci, co) in enumerate(_UP, 1):
+            out.append((f"up{i}", (ci,) if i == 1 else (ci - skips[i - 1], skips[i - 1]), UP5_PAD if co < 64 else 0))
+        return out
+
+    # ---- buffers ------------------------------------------------------------------------------------
+    def _maps(self, n, H, W):
+        """The slices d1..d6 (down outputs) and p1..p5 (up outputs) for n windows of H x W, cached by geometry: a bordered map
+        relies on its border staying zero."""
+        key = ("maps", n, H, W)
+        m = self._bufs.get(key)
+        if m is not None:
+            return m
+        dev, b = self.dev, 1 if self.implicit else 0
+        f = lambda C: torch.zeros(n, H + 2 * b, W + 2 * b, C, device=dev, dtype=torch.float32)
+        s = lambda C: torch.zeros(((2,) if self.split else ()) + (n, H + 2 * b, W + 2 * b, C), device=dev, dtype=torch.bfloat16) if self.implicit else None
+        m = {}
+        if self.implicit:
+            # concatenated maps [p_k | d_(6-k)]: r2m:38 without the copy
+            for k, (cu, cd) in enumerate(((512, 1024), (256, 512), (128, 256), (64, 128), (UP5_PAD, 64)), 1):
+                f32, sh = f(cu + cd), s(cu + cd)
+                m[f"p{k}"] = _Slice(f32, sh, 0, cu)
+                m[f"d{6 - k}"] = _Slice(f32, sh, cu, cd)
+                m[f"u{k}"] = _Slice(f32, sh, 0, cu + cd)
+            m["d6"] = _Slice(f(1024), s(1024), 0, 1024)
+        else:
+            for k, (_, co) in enumerate(_DOWN, 1):
+                m[f"d{k}"] = _Slice(f(co), None, 0, co)
+            for k, (_, co) in enumerate(_UP, 1):
+                m[f"p{k}"] = _Slice(f(max(co, UP5_PAD)), None, 0, max(co, UP5_PAD))
+        self._bufs[key] = m
+        return m
+
+    def _col(self, which, rows, K):
+        need = rows * K
+        buf = self._bufs.get(("col", which))
+        if buf is None or buf.numel() < need:
+            buf = self._bufs[("col", which)] = torch.empty(need, device=self.dev, dtype=torch.float32)
+        return buf[:need].view(rows, K)
+
+    # ---- one convolution ----------------------------------------------------------------------------
+    def _conv(self, name, srcs, dst, n, H, W, *, relu):
+        """srcs: the slices whose concatenation the convolution reads (implicit GEMM: ONE slice of a concatenated map)."""
+        w, bias, rows, N = self.w[name], self.bias[name], n * H * W, self.w[name].shape[0]
+        assert N == dst.C
+        if self.implicit:
+            (src,) = srcs
+            key = (n, H, W, src.pitch, src.off, src.C, dst.pitch)
+            t = self._tabs.get(key)
+            if t is None:
+                t = self._tabs[key] = slice_conv_tables(n, H, W, src.pitch, src.off, src.C, dst.pitch, 1, self.dev)
+            K = 9 * src.C
+            sp = {}
+            shadow = dst.shadow() if relu else None           # down blocks: v2a_leaky_shadow writes the shadow after the activation
+            if self.split:
+                sp["a_split"] = True
+                if shadow is not None:
+                    sp.update(out_bf16_split=True, out_bf16_lo_offset=dst.plane)
+            L.gemm([L.Operand(src.shadow(), K, K, src.plane if self.split else 0)], w, dst.base(), M=rows, N=N, compute=self.code,
+                   bias=bias, relu=relu, ldo=dst.pitch, out_bf16=shadow, ld_out_bf16=dst.pitch,
+                   a_row_offset=t[0], a_ktile_offset=t[1], out_row_offset=t[2], **sp)
+            return
+        segs = []
+        for i, src in enumerate(srcs):
+            K = 9 * src.C
+            col = self._col(i, rows, K)
+            L.im2col(src.f32, col, B=n, H=H, W=W, C_=src.C, kh=3, kw=3, stride=1, pad=1, Ho=H, Wo=W, ldo=K)
+            segs.append((col, K, K))
+        L.gemm(segs, w, dst.f32, M=rows, N=N, compute=self.code, bias=bias, relu=relu, ldo=dst.pitch)
+
+    def _leaky(self, sl, n, H, W):
+        L.leaky_shadow(sl.base(), sl.shadow(), n=n, H=H, W=W, C_=sl.C, shadow_mode=self.mode, lo_offset=sl.plane if self.split else 0,
+                       pitch=sl.pitch, border=1 if self.implicit else 0)
+
+    def _pass(self, x, logits, probs, midi, threshold, taps=None):
+        """x (n, H, W) fp32 on the device -> the dense (n, H, W) outputs that are not None."""
+        n, H, W = x.shape
+        m = self._maps(n, H, W)
+        b = 1 if self.implicit else 0
+        d1 = m["d1"]
+        L.roll2midi_stem(x, self.stem_wt, d1.base(), d1.shadow(), n=n, H=H, W=W, co=64, shadow_mode=self.mode,
+                         lo_offset=d1.plane if self.split else 0, pitch=d1.pitch, border=b)
+        for k in range(2, 7):                                        # r2m:64-72
+            self._conv(f"down{k}", [m[f"d{k - 1}"]], m[f"d{k}"], n, H, W, relu=False)
+            self._leaky(m[f"d{k}"], n, H, W)
+        self._conv("up1", [m["d6"]], m["p1"], n, H, W, relu=True)    # r2m:74
+        for k in range(2, 6):                                        # r2m:76-82: up_k(cat(up_(k-1), d_(7-k)))
+            srcs = [m[f"u{k - 1}"]] if self.implicit else [m[f"p{k - 1}"], m[f"d{7 - k}"]]
+            self._conv(f"up{k}", srcs, m[f"p{k}"], n, H, W, relu=True)
+        p5 = m["p5"]
+        L.roll2midi_head(p5.base(), d1.base(), self.head_w, u_pitch=p5.pitch, nu=16, d_pitch=d1.pitch, nd=64, bias=self.head_b,
+                         threshold=threshold, n=n, H=H, W=W, border=b, logits=logits, probs=probs, midi=midi)
+        if taps is not None:
+            for k in range(1, 7):
+                taps.setdefault(f"d{k}", []).append(m[f"d{k}"].nchw(b).clone())
+            for k in range(1, 6):
+                up = m[f"p{k}"].nchw(b, _UP[k - 1][1])
+                taps.setdefault(f"u{k}", []).append(torch.cat([up, m[f"d{6 - k}"].nchw(b)], 1))
+
+    def _run(self, x, threshold, want_logits=False, want_midi=False, taps=None):
+        """x (n, keys, w) -> (probs or logits (n, keys, w) fp32, midi (n, keys, w) uint8 or None), chunk windows per pass."""
+        x = x.to(self.dev, torch.float32).contiguous()
+        n = x.shape[0]
+        out = torch.empty_like(x)
+        midi = torch.empty(x.shape, device=self.dev, dtype=torch.uint8) if want_midi else None
+        for s in range(0, n, self.chunk):
+            e = min(s + self.chunk, n)
+            self._pass(x[s:e], out[s:e] if want_logits else None, None if want_logits else out[s:e], None if midi is None else midi[s:e],
+                       threshold, taps)
+        return out, midi
+
+    # ---- reference-shaped entry points ------------------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, x, return_logits=False, taps=None):
+        """`Generator.forward` in eval mode (r2m:60-87): x (n, 1, keys, w) probabilities -> (n, 1, keys, w) probabilities, or with
+        return_logits the values in front of the last sigmoid.  Any keys >= 1 and w >= 1: the net is fully convolutional.
+        taps: a dict that receives d1..d6 and u1..u5 (the concatenated outputs of the up blocks), NCHW, one entry per pass."""
+        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] < 1 or x.shape[3] < 1:
+            raise ValueError(f"Roll2MidiEngine.forward: x must be (n, 1, keys, w), got {tuple(x.shape)}")
+        if x.shape[0] == 0:
+            return torch.empty(x.shape, device=self.dev, dtype=torch.float32)
+        return self._run(x[:, 0], 0.5, want_logits=return_logits, taps=taps)[0].unsqueeze(1)
+
+    @torch.no_grad()
+    def refine(self, roll, window=100, threshold=0.5, tail="own"):
+        """roll (b, t, keys) key probabilities (`Video2RollEngine.frame_probs`) -> (probs (b, t, keys) fp32, midi (b, t, keys) uint8 =
+        probs >= threshold).  t is cut into windows of `window` frames (Roll2Midi_inference.py:44-49 with 2 x 50 frames); the shorter
+        last one runs at its own width (tail="own") or, as the reference does (Roll2Midi_inference.py:39-42, 58: zero LOGITS in front
+        of torch.sigmoid), padded to the full width with probability 0.5 and cropped afterwards (tail="pad")."""
+        if tail not in ("own", "pad"):
+            raise ValueError(f"refine: tail must be 'own' or 'pad', got {tail!r}")
+        if roll.dim() != 3 or int(window) < 1:
+            raise ValueError(f"refine: roll must be (b, t, keys) and window >= 1, got {tuple(roll.shape)}, window {window}")
+        window = int(window)
+        roll = roll.to(self.dev, torch.float32)
+        b, t, keys = roll.shape
+        probs = torch.empty(b, t, keys, device=self.dev, dtype=torch.float32)
+        midi = torch.empty(b, t, keys, device=self.dev, dtype=torch.uint8)
+        full = t // window
+        groups = []                                                   # (first frame, windows, frames per window, frames kept)
+        if full:
+            groups.append((0, full, window, window))
+        if t % window:
+            groups.append((full * window, 1, window if tail == "pad" else t % window, t % window))
+        for first, nw, w, keep in groups:
+            x = roll[:, first:first + nw * keep]
+            if keep < w:
+                x = torch.cat([x, torch.full((b, w - keep, keys), 0.5, device=self.dev)], 1)
+            x = x.reshape(b * nw, w, keys).transpose(1, 2)            # (windows, keys, w): the reference's `data.T`
+            p, mi = self._run(x, float(threshold), want_midi=True)
+            probs[:, first:first + nw * keep] = p.transpose(1, 2)[:, :keep].reshape(b, nw * keep, keys)
+            midi[:, first:first + nw * keep] = mi.transpose(1, 2)[:, :keep].reshape(b, nw * keep, keys)
+        return probs, midi

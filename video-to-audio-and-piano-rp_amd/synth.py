@@ -92,6 +92,54 @@ def random_video2roll_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
     return sd
 
 
+def random_roll2midi_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `Roll2MidiNet.Generator((1, 51, 100)).state_dict()`, the reference's
+    `checkpoint['state_dict_G']` (no Roll2Midi checkpoint is reachable offline).  numpy's legacy RandomState stream, so the golden
+    vectors of tests/golden/roll2midi.npz can be regenerated anywhere.  He-scaled convolutions (std sqrt(2 / (9 ci)); the transposed
+    ones by their input channels too), BatchNorm weight in [0.8, 1.6] and running_var in [0.5, 2] -- with eps = 0.8 the folded scale
+    stays near 1 -- and a conv1d weight scaled so the logits spread over several units."""
+    import numpy as np
+
+    from .roll2midi import expected_state_dict_shapes
+
+    rs = np.random.RandomState(seed)
+    sd = {}
+    for k, shp in expected_state_dict_shapes().items():
+        if k.endswith("num_batches_tracked"):
+            v = np.array(1000, dtype=np.int64)
+        elif k.endswith("running_var"):
+            v = rs.uniform(0.5, 2.0, shp).astype(np.float32)
+        elif k.endswith("running_mean"):
+            v = (0.1 * rs.standard_normal(shp)).astype(np.float32)
+        elif k.endswith("model.1.weight"):
+            v = rs.uniform(0.8, 1.6, shp).astype(np.float32)
+        elif k == "conv1d.weight":
+            v = (rs.standard_normal(shp) * 2.0).astype(np.float32)
+        elif k.endswith(".bias"):
+            v = (0.1 * rs.standard_normal(shp)).astype(np.float32)
+        else:
+            ci = shp[0] if k.startswith("up") else shp[1]
+            v = (rs.standard_normal(shp) * math.sqrt(2.0 / (9 * ci))).astype(np.float32)
+        sd[k] = torch.from_numpy(v) if v.ndim else torch.tensor(int(v))
+    return sd
+
+
+def synthetic_key_roll(b: int, t: int, keys: int = 51, seed: int = 0, logits: bool = False) -> torch.Tensor:
+    """(b, t, keys) fp32 key probabilities as a Video2Roll encoder would give them: a few held notes (high) on a low, noisy floor.
+    numpy RandomState and float64 arithmetic rounded once, reproducible across machines.  logits: the values in front of the sigmoid."""
+    import numpy as np
+
+    rs = np.random.RandomState(seed)
+    logit = -3.0 + 0.8 * rs.standard_normal((b, t, keys))
+    for bi in range(b):
+        for _ in range(max(2, t // 6)):
+            k, s, d = rs.randint(0, keys), rs.randint(0, t), rs.randint(1, 12)
+            logit[bi, s:s + d, k] += 6.0
+    if logits:
+        return torch.from_numpy(logit.astype(np.float32))
+    return torch.from_numpy((1.0 / (1.0 + np.exp(-logit))).astype(np.float32))
+
+
 def synthetic_piano_frames(b: int, t: int, H: int = 100, W: int = 900, seed: int = 0) -> torch.Tensor:
     """(b, 1, t, H, W) grey frames in [0, 1] (ToTensor range, x3:1878-1890): a static keyboard-like stripe pattern plus a
     few moving bright blobs and noise.  numpy RandomState, reproducible across machines."""

@@ -433,6 +433,15 @@ class Video2RollEngine:
         return self._run(frames, 5, False, windows=[(i, 2) for i in range(n)], taps=taps)
 
     @torch.no_grad()
+    def frame_probs(self, x):
+        """x (b, 1, t, H, W) -> the key probabilities per video frame (b, t, notes): what `encode_frames` computes before it repeats
+        every row x3 for the 75 Hz latent rate.  The Roll2Midi generator (roll2midi.py) works at the video frame rate."""
+        b, c, t, H, W = x.shape
+        assert c == 1
+        frames = x[:, 0].to(self.dev, torch.float32).contiguous()
+        return self._run(frames, t, True).view(b, t, self.notes)
+
+    @torch.no_grad()
     def encode_frames(self, x, l: int):
         """`E2TTS.encode_frames(x, l)` (x3:1525-1553): x (b, 1, t, H, W) -> roll probabilities (b, l, notes)."""
         b, c, t, H, W = x.shape
