@@ -178,7 +178,9 @@ typedef struct v2a_gemm_args {
   /* non-zero: the out_bf16 shadow is written in the V2A_BF16_SPLIT layout, row m = [hi_0 .. hi_{N-1} | lo_0 .. lo_{N-1}] of the
    * (gamma-scaled, when norm_gamma is given) fp32 result, ld_out_bf16 >= 2 * N: the operand of a later split-bf16 GEMM without a
    * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU, SWIGLU and GELU epilogues only): out row m = [hi | lo] planes of the N/2
-   * hidden values, ldo >= N (GELU: of the N values, ldo >= 2N). */
+   * hidden values, ldo >= N (GELU: of the N values, ldo >= 2N).  A split shadow is written by the LDS-staged epilogue of the ring and 8-phase
+   * kernels only: out_bf16_split is refused (V2A_ERR_ARG) with compute_dtype V2A_F32, with fp32 A on bf16 compute, with the SIGMOID epilogue and
+   * with epilogue operands that are not 16-byte aligned -- those launches run a scalar epilogue that would write the hi plane alone. */
   int32_t out_bf16_split;
   /* ABI 8, split operands / split shadow only.  a_lo_offset[s]: elements from the hi plane of a row of segment s to its lo plane; 0 = ka[s], the
    * layout [hi k | lo k].  out_bf16_lo_offset: the same for the shadow row; 0 = N.  They let ONE buffer of rows [x_hi | s_hi | x_lo | s_lo] serve

@@ -1,5 +1,6 @@
 """CPU: the bf16x3 mode of the Video2Roll encoder answers its argument checks before any HIP call -- the engine and E2TTS
-refuse unknown modes, v2a_gemm refuses split operands with offset tables on the shapes that cannot take them, the split
+refuse unknown modes, v2a_gemm refuses split operands with offset tables on the shapes that cannot take them and a split
+shadow (out_bf16_split) on the launches whose scalar epilogue could not write its lo plane, the split
 producers (v2a_frames_pack_split, v2a_pool2d_split) refuse null pointers and bad geometry, and the CLI's --frames-dtype
 reaches E2TTS."""
 import ctypes
@@ -70,6 +71,34 @@ def test_split_shadow_with_out_row_offset_needs_lo_offset(L):
     g.out_row_offset = 1 << 16
     assert L.lib().v2a_gemm(ctypes.byref(g), None) == -1
     assert "out_bf16_lo_offset" in L.lib().v2a_last_error().decode()
+
+
+def _dense_shadow_args(L, *, compute, a_dtype, epilogue=None):
+    """A dense GEMM with an out_bf16 shadow whose pointers are never dereferenced: every check but the one under test passes."""
+    g = L.GemmArgs()
+    p = 1 << 16
+    g.a[0], g.lda[0], g.ka[0], g.nseg = p, 128, 128, 1
+    g.a_dtype, g.compute_dtype = a_dtype, compute
+    g.w, g.ldw = p, 128
+    g.M, g.N = 256, 128
+    g.epilogue = L.EPI_STORE if epilogue is None else epilogue
+    g.out, g.ldo, g.out_dtype = p, 128, L.F32
+    g.out_bf16, g.ld_out_bf16, g.out_bf16_split = p, 256, 1
+    return g
+
+
+@pytest.mark.parametrize("case", ["fp32 compute", "fp32 A on bf16 compute", "bf16 SIGMOID", "unaligned shadow rows"])
+def test_split_shadow_refused_where_the_scalar_epilogue_runs(L, case):
+    """out_bf16_split on a launch whose epilogue writes bf16(v) alone would leave the lo plane unwritten and report success: refused on the host."""
+    g = {"fp32 compute": lambda: _dense_shadow_args(L, compute=L.F32, a_dtype=L.F32),
+         "fp32 A on bf16 compute": lambda: _dense_shadow_args(L, compute=L.BF16, a_dtype=L.F32),
+         "bf16 SIGMOID": lambda: _dense_shadow_args(L, compute=L.BF16, a_dtype=L.BF16, epilogue=L.EPI_SIGMOID),
+         "unaligned shadow rows": lambda: _dense_shadow_args(L, compute=L.BF16, a_dtype=L.BF16)}[case]()
+    if case == "unaligned shadow rows":
+        g.out_bf16 = (1 << 16) + 2                           # not 8-byte aligned: the ring kernel would fall back to the scalar epilogue
+    assert L.lib().v2a_gemm(ctypes.byref(g), None) == -1    # V2A_ERR_ARG
+    msg = L.lib().v2a_last_error().decode()
+    assert "out_bf16_split" in msg and "lo plane" in msg, msg
 
 
 def test_frames_pack_split_refuses_bad_args(L):

@@ -685,6 +685,13 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
     if (a->out_bf16) ok = ok && ((uintptr_t)a->out_bf16 & 7) == 0 && a->ld_out_bf16 % 4 == 0;
     p.vec_epi = ok ? 1 : 0;
   }
+  // only the LDS-staged epilogue of the ring and 8-phase kernels writes the lo plane of a split shadow; the scalar epilogue (the exact-fp32
+  // kernel, fp32 A on bf16 compute, the bf16 SIGMOID kernel, and the ring kernels without 16-byte aligned operands) writes bf16(v) alone
+  if (p.out2_split)
+    V2A_REQUIRE(a->compute_dtype == V2A_BF16 && a->a_dtype != V2A_F32 && a->epilogue != V2A_EPI_SIGMOID && p.vec_epi,
+                "v2a_gemm: out_bf16_split needs bf16 compute on bf16 or split A, an epilogue other than SIGMOID and 16-byte aligned epilogue "
+                "operands (compute dtype %d, A dtype %d, epilogue %d): no other kernel writes the lo plane",
+                a->compute_dtype, a->a_dtype, a->epilogue);
   p.relu = a->relu;
   // off by default: +0.7 % throughput, but the fp32 summation order of a row then depends on how many rows the call has, so a
   // clip's result would change (in the last bits) with the batch it is sampled in; v2a_set_tuning enables it
