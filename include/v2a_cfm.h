@@ -51,7 +51,7 @@ enum {
   V2A_ERR_LAUNCH = -2  /* hipGetLastError() after launch */
 };
 
-int v2a_abi_version(void);        /* 8 */
+int v2a_abi_version(void);        /* 9 */
 const char* v2a_last_error(void);
 
 /* ---------------------------------------------------------------------------------------
@@ -136,21 +136,39 @@ typedef struct v2a_gemm_args {
    * v2a_tuning.gemm_force_tile for THIS call (bf16 x bf16 only).  The sampler passes 1 (128x256 tiles, one workgroup per CU) for
    * the text / frames streams: their GEMMs run beside the audio stream's, and few fat workgroups that own whole CUs disturb
    * the critical path less than many small ones spread over every CU (+3.5 % end to end, measured).
-   * Plain bf16 x bf16 operands, 0 = by shape or 1..16 (any other value is rejected); tile, waves (rows x columns), ring depth, wave tile:
-   *    1 = 128x256, 2x4, 3-deep, 64x64         2 = 128x128, 2x2, 3-deep, 64x64         3 = 128x64, 2x2, 3-deep, 64x32
-   *    4 = 5 = 64x64, 2x2, 3-deep, 32x32       6 = 256x256, 2x4, 2-deep, 128x64        8 = 64x128, 2x2, 6-deep, 32x64
-   *    9 = 64x64, 2x2, 6-deep, 32x32          10 = 64x64, 2x2, 4-deep, 32x32          11 = 64x64, 2x2, 5-deep, 32x32
-   *   12 = 128x128, 2x2, 4-deep, 64x64        13 = 128x128, 2x4, 3-deep, 64x32        14 = 64x64, 2x4, 3-deep, 32x16
-   *   15 = 128x64, 4x2, 3-deep, 32x32         16 = 64x128, 2x4, 3-deep, 32x32
+   * Plain bf16 x bf16 operands, 0 = by shape or 1..16 (any other value is rejected).  The LDS-DMA ring shapes, one row per tile_hint
+   * (V2A_RING_TILES in csrc/gemm.hip holds the same rows under k = tile_hint - 1):
+   *   plain hint | tile    | waves (rows x columns) | ring depth | K stage | wave tile
+   *            1 | 128x256 | 2x4 | 3 | 64 | 64x64
+   *            2 | 128x128 | 2x2 | 3 | 64 | 64x64
+   *            3 | 128x64  | 2x2 | 3 | 64 | 64x32
+   *            4 | 64x64   | 2x2 | 3 | 64 | 32x32
+   *            5 | 64x64   | 2x2 | 3 | 64 | 32x32      (another name of 4)
+   *            6 | 256x256 | 2x4 | 2 | 64 | 128x64
+   *            8 | 64x128  | 2x2 | 6 | 64 | 32x64
+   *            9 | 64x64   | 2x2 | 6 | 64 | 32x32
+   *           10 | 64x64   | 2x2 | 4 | 64 | 32x32
+   *           11 | 64x64   | 2x2 | 5 | 64 | 32x32
+   *           12 | 128x128 | 2x2 | 4 | 64 | 64x64
+   *           13 | 128x128 | 2x4 | 3 | 64 | 64x32
+   *           14 | 64x64   | 2x4 | 3 | 64 | 32x16
+   *           15 | 128x64  | 4x2 | 3 | 64 | 32x32
+   *           16 | 64x128  | 2x4 | 3 | 64 | 32x32
    *    7 = the 256x256 phase-interleaved (8-phase) kernel: dense rows and 16-byte aligned epilogue operands only
    * 14 has no GEGLU form (value / gate groups of 16 columns need wave tiles of 32) and is refused together with norm_ssq (V2A_ERR_ARG: the
    * partial sums per 32 columns need wave tiles of at least 32 columns); norm_gamma alone, the shadow without sums, runs on it.  The K order
    * of an output element is the same on every ring shape: STORE / RESID / GATE_RESID results of hints 1..6 and 8..16 are equal bit for bit.
-   * Split operands (a_dtype V2A_BF16_SPLIT) have tile shapes of their own, 0 = by shape or 1..7 (any other value is rejected):
-   *   1 = 64x64, 2 = 128x64, 3 = 128x128 (8 waves, 2-deep ring), 4 = 64x128 (8 waves): LDS-DMA ring, a stage = 64 k of the four planes;
+   * Split operands (a_dtype V2A_BF16_SPLIT) have tile shapes of their own, 0 = by shape or 1..7 (any other value is rejected).  The LDS-DMA
+   * ring shapes (V2A_SPLIT_RING_TILES in csrc/gemm.hip); a stage holds K stage logical k of the four planes:
+   *   split hint | tile    | waves (rows x columns) | ring depth | K stage | wave tile
+   *            1 | 64x64   | 2x2 | 3 | 64 | 32x32
+   *            2 | 128x64  | 2x2 | 3 | 64 | 64x32
+   *            3 | 128x128 | 2x4 | 2 | 64 | 64x32
+   *            4 | 64x128  | 2x4 | 3 | 64 | 32x32
+   *            6 | 128x256 | 2x4 | 3 | 32 | 64x64
+   *            7 | 128x128 | 2x4 | 3 | 32 | 64x32
    *   5 = the 256x256 phase-interleaved (8-phase) kernel: a stage = 32 logical k, staged as rows [32 k hi | 32 k lo] of both operands,
-   *       three products (A_lo W_hi, A_hi W_lo, A_hi W_hi) from one set of fragments; dense rows only; every ka a multiple of 64;
-   *   6 = 128x256, 7 = 128x128 (8 waves, 3-deep ring): a stage = 32 k of the four planes.
+   *       three products (A_lo W_hi, A_hi W_lo, A_hi W_hi) from one set of fragments; dense rows only; every ka a multiple of 64.
    * With a_row_offset / out_row_offset only 0 and 1..4 are admitted (a_ktile_offset is laid out for 64-wide K tiles).  Every shape adds the
    * three products of a 32-wide k step -- A_lo W_hi, A_hi W_lo, A_hi W_hi, in that order -- to one accumulator chain, k steps in ascending order,
    * whether a stage holds 64 k (two steps) or 32: the sum order of an output element does not depend on the shape.  STORE (with or without
@@ -195,11 +213,28 @@ int v2a_gemm(const v2a_gemm_args* args, v2a_stream_t stream);
 /* sizeof(v2a_gemm_args) as the library was built: a binding checks its mirror of the struct against this */
 int v2a_gemm_args_size(void);
 
+/* ABI 9: what v2a_gemm would launch for these arguments under the current v2a_tuning.  v2a_gemm_choose runs everything v2a_gemm runs up
+ * to, but not including, its first HIP call -- the argument checks, the tile selection, the dispatch to the instantiation -- and that
+ * instantiation writes *choice from its own constants.  Return codes and v2a_last_error texts are those of v2a_gemm for the same arguments
+ * (a refusal leaves *choice zeroed).  No pointer of args is dereferenced and no GPU is needed. */
+enum { V2A_GEMM_REGISTER_STAGED = 0, V2A_GEMM_RING = 1, V2A_GEMM_8PHASE = 2 };
+typedef struct v2a_gemm_choice {
+  int32_t family;            /* V2A_GEMM_*: the register-staged kernel (exact fp32, fp32 A, SIGMOID), the LDS-DMA ring, the 8-phase kernel */
+  int32_t split;             /* non-zero: the instantiation for split (hi | lo plane) operands */
+  int32_t bm, bn, bk;        /* workgroup tile and the logical K of one stage */
+  int32_t waves_m, waves_n;  /* waves of a workgroup, rows x columns */
+  int32_t stages;            /* LDS buffers a K stage rotates through */
+  int32_t tiles;             /* workgroups of the launch */
+  int32_t xcd_gm, xcd_gn;    /* XCD grid over the tile space (used by the ring and 8-phase kernels) */
+  int32_t vec_epi;           /* non-zero: the LDS-staged epilogue with 16-byte row pieces */
+} v2a_gemm_choice;
+int v2a_gemm_choose(const v2a_gemm_args* args, v2a_gemm_choice* choice);
+
 /* Tile-selection overrides of v2a_gemm for A/B measurements (bench.py, scripts/).  Library defaults: force -1, rotation 0,
  * 8-phase kernel on (staggered) from 400 tiles.
  * Process-wide; call it between launches, not concurrently with them.  NULL restores the defaults. */
 typedef struct v2a_tuning {
-  int32_t gemm_force_tile;        /* -1 = by shape; 0..5 = one LDS-DMA tile shape for every bf16 x bf16 GEMM (0 128x256, 1 128x128, 2 128x64, 3 64x64, 5 256x256), 6 = the 256x256 8-phase kernel, 7 / 8 = 64x128 / 64x64 with a 6-deep ring */
+  int32_t gemm_force_tile;        /* -1 = by shape; k = 0..8 without 4: the shape of plain tile_hint k + 1 (v2a_gemm_args) for every bf16 x bf16 GEMM (0 128x256, 1 128x128, 2 128x64, 3 64x64, 5 256x256), 6 = the 256x256 8-phase kernel, 7 / 8 = 64x128 / 64x64 with a 6-deep ring */
   int32_t gemm_k_rotation;        /* ignored since ABI 5 (was: M bands that share a W panel start their K walk at different K tiles; +0.7 %, and it made
                                    * the fp32 summation order depend on M): the K loop now walks running pointers */
   int32_t gemm_8phase;            /* 256x256 phase-interleaved kernel for wide outputs (N >= 2048): 0 off, 1 on (staggered wave rows), 2 on (lock-step) */

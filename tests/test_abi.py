@@ -35,7 +35,7 @@ def test_header_symbols_are_exported(lib):
 
 def test_abi_version_and_error_string(lib):
     L = lib.lib()
-    assert L.v2a_abi_version() == lib.ABI_VERSION == 8
+    assert L.v2a_abi_version() == lib.ABI_VERSION == 9
     g = lib.GemmArgs()
     g.nseg = 5
     assert L.v2a_gemm(ctypes.byref(g), None) == -1                 # V2A_ERR_ARG, before any HIP call
@@ -74,6 +74,23 @@ def _struct_fields(src, name):
             if part:
                 names.append(re.findall(r"\*?\s*([A-Za-z_][A-Za-z0-9_]*)\s*(?:\[\d+\])?\s*$", part)[0])
     return names
+
+
+def test_gemm_choice_struct_matches_header(lib):
+    """The ctypes mirror of v2a_gemm_choice follows the header field for field (all int32), the family codes are the header's, and the
+    library fills it through that layout without a GPU."""
+    src = open(os.path.join(ROOT, "include", "v2a_cfm.h")).read()
+    assert [f[0] for f in lib.GemmChoice._fields_] == _struct_fields(src, "v2a_gemm_choice")
+    assert all(f[1] is ctypes.c_int32 for f in lib.GemmChoice._fields_) and ctypes.sizeof(lib.GemmChoice) == 4 * len(lib.GemmChoice._fields_)
+    body = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    codes = dict(re.findall(r"(V2A_GEMM_[A-Z0-9_]+) = (\d+)", body))
+    assert codes == dict(V2A_GEMM_REGISTER_STAGED=str(lib.GEMM_REGISTER_STAGED), V2A_GEMM_RING=str(lib.GEMM_RING), V2A_GEMM_8PHASE=str(lib.GEMM_8PHASE))
+    w = torch.zeros(64, 64)
+    c = lib.gemm_choice([(w, 64, 64)], w, w, M=64, N=64, compute=lib.F32)           # CPU tensors: only their addresses are looked at
+    assert [getattr(c, f[0]) for f in lib.GemmChoice._fields_] == [lib.GEMM_REGISTER_STAGED, 0, 128, 128, 16, 2, 2, 2, 1, 2, 4, 1]
+    with pytest.raises(lib.V2AError, match="M=0"):
+        lib.gemm_choice([(w, 64, 64)], w, w, M=0, N=64, compute=lib.F32)
+    assert lib.lib().v2a_gemm_choose(ctypes.byref(lib.GemmArgs()), None) == -1 and b"null choice" in lib.lib().v2a_last_error()
 
 
 def test_integration_md_binding_matches_header(lib):

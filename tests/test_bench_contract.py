@@ -30,7 +30,8 @@ def test_profile_files_named_by_bench_exist(bench):
                                        ("gemm<bf16,a_split,geglu,bf16>", "ROCPROF_STATS_8CLIPS"), ("gemm<bf16,a_split,resid,f32>", "ROCPROF_STATS_8CLIPS_ALONE")])
 def test_rocprof_block_finds_the_dominant_kernel_classes(bench, key, stats):
     """The GEMM classes of the headline (bf16x3) mode in the committed summaries: split-operand ring instantiations (S3 = true), the 8-phase
-    kernel for `tile4` (split tile_hint 5) and by-shape launches, the 128x256 ring on 32-wide K stages for `tile5` (split tile_hint 6: the frames stream's narrow GEMMs)."""
+    kernel for `tile4` (_lib.SPLIT_TILE_8PHASE: profiler keys are tile<hint - 1>) and by-shape launches, the 128x256 ring on 32-wide K stages for
+    `tile5` (_lib.SPLIT_TILE_128x256_K32: the frames stream's narrow GEMMs)."""
     r = bench.rocprof_avg(key, 6.7e9, 2.5e15 / 1e12, getattr(bench, stats))
     assert r is not None and r["calls"] > 100 and 5.0 < r["avg_us"] < 1500.0 and ("gemm_bf16_dma_kernel" in r["source"] or "gemm_bf16_8ph_kernel" in r["source"]), r
     if "tile4" in key:

@@ -249,7 +249,7 @@ def test_header_and_binding_declare_swiglu():
     from v2a_amd import _lib
     h = open(os.path.join(ROOT, "include", "v2a_cfm.h")).read()
     assert "V2A_EPI_SWIGLU = 7" in h and _lib.EPI_SWIGLU == 7 and _lib._EPI_NAMES[7] == "swiglu"
-    assert _lib.ABI_VERSION == 8 and "v2a_abi_version" in _lib.EXPORTS
+    assert _lib.ABI_VERSION == 9 and "v2a_abi_version" in _lib.EXPORTS
 
 
 def test_swiglu_instantiations_have_no_scratch():

@@ -94,7 +94,7 @@ def test_new_symbols_are_declared_exported_and_check_arguments():
     h = open(os.path.join(ROOT, "include", "v2a_cfm.h")).read()
     for name in ("v2a_elu_pad_lr", "v2a_encodec_stage0"):
         assert re.search(r"int %s\(" % name, h) and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     L = _lib.lib()
     assert L.v2a_elu_pad_lr(None, 32, 8, 4, 1, 1, 1, None) == -1 and b"null" in L.v2a_last_error()
     assert L.v2a_elu_pad_lr(16, 16, 8, 4, 1, 1, 1, None) == -1 and b"aliased" in L.v2a_last_error()

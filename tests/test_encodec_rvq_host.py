@@ -53,7 +53,7 @@ def test_new_symbols_are_declared_exported_and_check_arguments():
         assert re.search(r"int %s\(" % name, h) and name in _lib.EXPORTS
     assert "EncodecEuclideanCodebook.quantize" in h and "EncodecResidualVectorQuantizer.encode" in h
     assert "EncodecResidualVectorQuantizer.decode" in h
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     L = _lib.lib()
     enc = lambda x=4096, cb=4096, S=32, Kc=1024, D=128, n_q=32, B=1, T=5, st=(640, 1, 5): L.v2a_encodec_rvq_encode(
         x, *st, B, T, cb, 8192, S, Kc, D, n_q, 16384, None)

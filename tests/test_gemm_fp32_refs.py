@@ -76,12 +76,20 @@ def test_tie_inputs_separate_the_three_roundings():
 def test_tile_rule_is_the_one_in_the_source():
     src = open(os.path.join(ROOT, "video-to-audio-and-piano-rp_amd", "csrc", "gemm.hip")).read()
     flat = re.sub(r"\s+", " ", src)
-    assert "const int64_t t128 = (int64_t)((a->M + 127) / 128) * ((a->N + 127) / 128);" in flat
-    assert "if (t128 < 224 && a->M > 64) return dispatch_epi<float, false, 64, 64>(a, p, s); return dispatch_epi<float, false, 128, 128>(a, p, s);" in flat
+    assert "int fp32_tile_by_shape(int M, int N) { return ntiles(M, N, 128, 128) < 224 && M > 64 ? 64 : 128; }" in flat
+    assert ("return fp32_tile_by_shape(a->M, a->N) == 64 ? dispatch_epi<float, false, 64, 64>(a, p, to) : dispatch_epi<float, false, 128, 128>(a, p, to);"
+            in flat)
+    # ... and the one the library follows: the instantiation v2a_gemm would launch reports its tile and its workgroups (no GPU needed)
+    from v2a_amd import _lib as L
+    if not os.path.exists(L.LIB_PATH):
+        L.build()
+    t = torch.zeros(1, 16)
     for M in (1, 63, 64, 65, 128, 129, 200, 1792, 1793, 1800, 3000):
         for N in (1, 3, 20, 128, 129, 144, 272, 1792, 1793, 1920, 4096):
             t128 = -(-M // 128) * -(-N // 128)
             assert R.tile_of(M, N) == (64 if (t128 < 224 and M > 64) else 128), (M, N)
+            c = L.gemm_choice([(t, 16, 16)], t, t, M=M, N=N, compute=L.F32, ldo=N)
+            assert (c.family, c.bm, c.bn, c.bk, c.tiles) == (L.GEMM_REGISTER_STAGED, R.tile_of(M, N), R.tile_of(M, N), 16, R.workgroups(M, N)), (M, N)
     # the shapes of the GPU file reach the tiles, workgroup counts and remainders they were chosen for
     for (M, N), (tile, wgs) in R.TILES.items():
         assert (R.tile_of(M, N), R.workgroups(M, N)) == (tile, wgs), (M, N)

@@ -149,7 +149,7 @@ def test_tuned_tiles_table_names_existing_ab_logs():
 
 
 def test_engine_surfaces_refused_main_tile_with_folded_norms():
-    """main_tile = 13 is tile_hint 14 (64x64 tiles, wave tile 32x16), which cannot leave the sums of squares a folded RMSNorm's producer owes its
+    """main_tile = 13 (plain tile ids are the k of tile_hint = k + 1: the header's row for hint 14, 64x64 tiles, wave tile 32x16) cannot leave the sums of squares a folded RMSNorm's producer owes its
     consumer: v2a_gemm refuses the pair on the host, before any launch, and the engine hands the error on instead of sampling with wrong scales.
     The engine runs on the CPU against a stand-in library that answers 0 to everything except that one call, which goes to the real argument check."""
     from v2a_amd import _lib as L

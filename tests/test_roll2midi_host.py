@@ -45,7 +45,7 @@ def test_header_ctypes_and_exports_agree(lib):
         fn = getattr(L, name)
         assert fn.argtypes == want, (name, fn.argtypes, want)
         assert fn.restype is ctypes.c_int
-    assert L.v2a_abi_version() == lib.ABI_VERSION == 8              # the entry points are additive
+    assert L.v2a_abi_version() == lib.ABI_VERSION == 9              # the entry points are additive
 
 
 def test_entry_points_validate_on_cpu(lib):

@@ -110,7 +110,7 @@ def test_entry_points_validate_arguments_on_cpu():
     assert L.v2a_roll_metrics(16, 16, None, 1, 1, 51, 16, 16, None) == -1 and b"null" in L.v2a_last_error()
     assert L.v2a_roll_metrics(16, 16, 16, 1, 1, 51, 16, 12, None) == -1 and b"alignment" in L.v2a_last_error()
     assert _lib.LOSS_MAX_PARTS == 256
-    assert L.v2a_abi_version() == 8                                       # additive exports
+    assert L.v2a_abi_version() == 9                                       # additive exports
 
 
 def test_cli_has_validate():

@@ -124,7 +124,7 @@ def test_new_symbols_are_declared_exported_and_check_arguments():
     h = open(os.path.join(ROOT, "include", "v2a_cfm.h")).read()
     for name in ("v2a_wave_resample", "v2a_wave_stats", "v2a_wave_normalize"):
         assert re.search(r"int %s\(" % name, h) and name in _lib.EXPORTS
-    assert _lib.ABI_VERSION == 8 and _lib.lib().v2a_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and _lib.lib().v2a_abi_version() == 9
     L = _lib.lib()
     np_ = ctypes.c_int32(0)
     ok = dict(x=4096, L=1000, table=8192, o=147, n=80, K=171, width=12, y=16384, out_len=545, parts=32768)

@@ -54,6 +54,20 @@ class GemmArgs(C.Structure):
     ]
 
 
+class GemmChoice(C.Structure):
+    """Mirror of `v2a_gemm_choice`: what v2a_gemm would launch (v2a_gemm_choose)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "split", "bm", "bn", "bk", "waves_m", "waves_n", "stages", "tiles", "xcd_gm", "xcd_gn",
+                                         "vec_epi")]
+
+
+GEMM_REGISTER_STAGED, GEMM_RING, GEMM_8PHASE = 0, 1, 2       # v2a_gemm_choice.family
+
+# The tile ids the engines ask for by name (the tile_hint tables of include/v2a_cfm.h).  Plain bf16 operands: k of v2a_tuning.gemm_force_tile,
+# tile_hint = k + 1, profiler key tile<k>.  Split operands: the tile_hint itself, profiler key tile<hint - 1>.
+TILE_128x128, TILE_8PHASE, TILE_128x128_8WAVES, TILE_128x64_8WAVES = 1, 6, 12, 14
+SPLIT_TILE_8PHASE, SPLIT_TILE_128x256_K32 = 5, 6
+
+
 class DwconvNorm(C.Structure):
     """Mirror of `v2a_dwconv_norm`: the RMSNorm after the depthwise convolution, folded into it."""
     _fields_ = [("out_bf16", C.c_void_p), ("ld_out_bf16", C.c_int64), ("norm_gamma", C.c_void_p), ("step", C.c_void_p),
@@ -107,7 +121,7 @@ class RollHeadArgs(C.Structure):
 
 
 EXPORTS = [
-    "v2a_abi_version", "v2a_last_error", "v2a_gemm", "v2a_gemm_args_size", "v2a_set_tuning", "v2a_rmsnorm", "v2a_dwconv_silu_residual", "v2a_dwconv_silu_residual_norm",
+    "v2a_abi_version", "v2a_last_error", "v2a_gemm", "v2a_gemm_args_size", "v2a_gemm_choose", "v2a_set_tuning", "v2a_rmsnorm", "v2a_dwconv_silu_residual", "v2a_dwconv_silu_residual_norm",
     "v2a_rope_inplace", "v2a_attention", "v2a_qproj_xattn", "v2a_linear_small", "v2a_fill_registers", "v2a_time_cond",
     "v2a_apg_reduce", "v2a_cfg_euler", "v2a_step_advance", "v2a_cast_bf16", "v2a_split_bf16",
     "v2a_im2col", "v2a_frames_pack", "v2a_pool2d", "v2a_roll_head", "v2a_roll_expand", "v2a_frames_pack_split", "v2a_pool2d_split",
@@ -134,7 +148,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
-ABI_VERSION = 8          # what v2a_abi_version() of this source tree returns (csrc/rowops.hip)
+ABI_VERSION = 9          # what v2a_abi_version() of this source tree returns (csrc/rowops.hip)
 
 
 def _declare(lib):
@@ -143,6 +157,7 @@ def _declare(lib):
     lib.v2a_last_error.restype = C.c_char_p
     lib.v2a_gemm.argtypes = [C.POINTER(GemmArgs), vp]
     lib.v2a_gemm_args_size.restype = C.c_int
+    lib.v2a_gemm_choose.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmChoice)]
     lib.v2a_set_tuning.argtypes = [C.POINTER(Tuning)]
     lib.v2a_attention.argtypes = [C.POINTER(AttnArgs), vp]
     lib.v2a_qproj_xattn.argtypes = [C.POINTER(GemmArgs), C.POINTER(AttnArgs), vp]
@@ -353,6 +368,14 @@ def gemm(a_segs, w, out, **kw):
     """One v2a_gemm launch; arguments as for gemm_args."""
     g, key, flops, nbytes = gemm_args(a_segs, w, out, **kw)
     _launch(key, flops, nbytes, lambda: lib().v2a_gemm(C.byref(g), stream_ptr()))
+
+
+def gemm_choice(a_segs, w, out, **kw) -> GemmChoice:
+    """What gemm() with the same arguments would launch under the current tuning (v2a_gemm_choose): nothing is launched or read, so
+    tensors on any device do; a refusal raises as gemm() would."""
+    c = GemmChoice()
+    check(lib().v2a_gemm_choose(C.byref(gemm_args(a_segs, w, out, **kw)[0]), C.byref(c)))
+    return c
 
 
 def gemm_args(a_segs, w, out, *, M, N, compute, epilogue=EPI_STORE, bias=None, resid=None, gate=None,

@@ -124,50 +124,51 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 }
 
 template <typename T, bool A_F32, int EPI, typename OutT, int BM, int BN>
-int launch(const GemmParams& p, hipStream_t s) {
+int launch(const GemmParams& p, GemmTarget to) {
   constexpr int LR = TileCfg<T>::LDS_ROW;
   constexpr size_t smem = 2 * (size_t)(BM + BN) * LR * sizeof(T);
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   auto kern = gemm_kernel<T, A_F32, EPI, OutT, BM, BN>;
+  if (to.chosen(p, V2A_GEMM_REGISTER_STAGED, false, BM, BN, TileCfg<T>::BK, 2, 2, 2, tiles)) return V2A_OK;
   if constexpr (smem > 48 * 1024) {
     static std::atomic<uint64_t> lds_set{0};
     if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(kern), smem, lds_set, "v2a_gemm")) return rc;
   }
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), smem, s, p);
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), smem, to.stream, p);
   return v2a_check_launch("v2a_gemm");
 }
 
 template <typename T, bool A_F32, int BM, int BN>
-int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
+int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
   const bool out_f32 = a->out_dtype == V2A_F32;
   switch (a->epilogue) {
     case V2A_EPI_STORE:
-      if (out_f32) return launch<T, A_F32, V2A_EPI_STORE, float, BM, BN>(p, s);
-      if constexpr (sizeof(T) == 2) return launch<T, A_F32, V2A_EPI_STORE, bf16_t, BM, BN>(p, s);
+      if (out_f32) return launch<T, A_F32, V2A_EPI_STORE, float, BM, BN>(p, to);
+      if constexpr (sizeof(T) == 2) return launch<T, A_F32, V2A_EPI_STORE, bf16_t, BM, BN>(p, to);
       break;
     case V2A_EPI_SIGMOID:
-      if (out_f32) return launch<T, A_F32, V2A_EPI_SIGMOID, float, BM, BN>(p, s);
+      if (out_f32) return launch<T, A_F32, V2A_EPI_SIGMOID, float, BM, BN>(p, to);
       break;
     case V2A_EPI_GELU:
-      if (out_f32) return launch<T, A_F32, V2A_EPI_GELU, float, BM, BN>(p, s);
+      if (out_f32) return launch<T, A_F32, V2A_EPI_GELU, float, BM, BN>(p, to);
       break;
     case V2A_EPI_GEGLU:
       if (out_f32) {
-        if constexpr (sizeof(T) == 4) return launch<T, A_F32, V2A_EPI_GEGLU, float, BM, BN>(p, s);
+        if constexpr (sizeof(T) == 4) return launch<T, A_F32, V2A_EPI_GEGLU, float, BM, BN>(p, to);
       } else {
-        if constexpr (sizeof(T) == 2) return launch<T, A_F32, V2A_EPI_GEGLU, bf16_t, BM, BN>(p, s);
+        if constexpr (sizeof(T) == 2) return launch<T, A_F32, V2A_EPI_GEGLU, bf16_t, BM, BN>(p, to);
       }
       break;
     case V2A_EPI_SWIGLU:   // exact-fp32 compute only (gemm_prepare refuses plain bf16 compute)
       if constexpr (sizeof(T) == 4) {
-        if (out_f32) return launch<T, A_F32, V2A_EPI_SWIGLU, float, BM, BN>(p, s);
+        if (out_f32) return launch<T, A_F32, V2A_EPI_SWIGLU, float, BM, BN>(p, to);
       }
       break;
     case V2A_EPI_RESID:
-      if (out_f32) return launch<T, A_F32, V2A_EPI_RESID, float, BM, BN>(p, s);
+      if (out_f32) return launch<T, A_F32, V2A_EPI_RESID, float, BM, BN>(p, to);
       break;
     case V2A_EPI_GATE_RESID:
-      if (out_f32) return launch<T, A_F32, V2A_EPI_GATE_RESID, float, BM, BN>(p, s);
+      if (out_f32) return launch<T, A_F32, V2A_EPI_GATE_RESID, float, BM, BN>(p, to);
       break;
   }
   return v2a_fail(V2A_ERR_ARG, "v2a_gemm: unsupported epilogue %d / out_dtype %d for compute dtype %d", a->epilogue,
@@ -473,7 +474,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_dma_kernel(const Gem
 }
 
 template <int EPI, typename OutT, int BM, int BN, int WGM, int WGN, int NST, bool S3 = false, int BK = 64>
-int launch_dma(const GemmParams& p_in, hipStream_t s) {
+int launch_dma(const GemmParams& p_in, GemmTarget to) {
   GemmParams p = p_in;
   v2a_detail::fill_tile_map(p, BM, BN);
   V2A_REQUIRE((int64_t)p.tiles_m * p.tiles_n < (1 << 24), "v2a_gemm: %d x %d tiles exceed the tile map", p.tiles_m, p.tiles_n);
@@ -484,27 +485,28 @@ int launch_dma(const GemmParams& p_in, hipStream_t s) {
   // panel being re-read from L2 by the 13-25 M-band workgroups of its XCD (profiles/ notes in DESIGN.md)
   auto kern = gemm_bf16_dma_kernel<EPI, OutT, BM, BN, WGM, WGN, NST, S3, BK>;
   if constexpr (BK != 64) V2A_REQUIRE(!p.a_koff, "v2a_gemm(dma): K-tile offset tables are laid out for 64-wide K tiles");
+  if (to.chosen(p, V2A_GEMM_RING, S3, BM, BN, BK, WGM, WGN, NST, tiles)) return V2A_OK;
   static std::atomic<uint64_t> lds_set{0};
   if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(kern), smem, lds_set, "v2a_gemm(dma)")) return rc;
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(64 * WGM * WGN), smem, s, p);
+  hipLaunchKernelGGL(kern, dim3(tiles), dim3(64 * WGM * WGN), smem, to.stream, p);
   return v2a_check_launch("v2a_gemm(dma)");
 }
 
 template <int BM, int BN, int WGM, int WGN, int NST = 3>
-int dispatch_dma(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
+int dispatch_dma(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
   const bool out_f32 = a->out_dtype == V2A_F32;
   switch (a->epilogue) {
     case V2A_EPI_STORE:
-      return out_f32 ? launch_dma<V2A_EPI_STORE, float, BM, BN, WGM, WGN, NST>(p, s) : launch_dma<V2A_EPI_STORE, bf16_t, BM, BN, WGM, WGN, NST>(p, s);
+      return out_f32 ? launch_dma<V2A_EPI_STORE, float, BM, BN, WGM, WGN, NST>(p, to) : launch_dma<V2A_EPI_STORE, bf16_t, BM, BN, WGM, WGN, NST>(p, to);
     case V2A_EPI_GEGLU:   // fp32 output: the hidden activation of the bf16x3 mode, split into hi / lo planes afterwards
       if constexpr ((BN / WGN / 16) % 2 == 0)
-        return out_f32 ? launch_dma<V2A_EPI_GEGLU, float, BM, BN, WGM, WGN, NST>(p, s) : launch_dma<V2A_EPI_GEGLU, bf16_t, BM, BN, WGM, WGN, NST>(p, s);
+        return out_f32 ? launch_dma<V2A_EPI_GEGLU, float, BM, BN, WGM, WGN, NST>(p, to) : launch_dma<V2A_EPI_GEGLU, bf16_t, BM, BN, WGM, WGN, NST>(p, to);
       break;
     case V2A_EPI_RESID:
-      if (out_f32) return launch_dma<V2A_EPI_RESID, float, BM, BN, WGM, WGN, NST>(p, s);
+      if (out_f32) return launch_dma<V2A_EPI_RESID, float, BM, BN, WGM, WGN, NST>(p, to);
       break;
     case V2A_EPI_GATE_RESID:
-      if (out_f32) return launch_dma<V2A_EPI_GATE_RESID, float, BM, BN, WGM, WGN, NST>(p, s);
+      if (out_f32) return launch_dma<V2A_EPI_GATE_RESID, float, BM, BN, WGM, WGN, NST>(p, to);
       break;
   }
   return v2a_fail(V2A_ERR_ARG, "v2a_gemm(dma): unsupported epilogue %d / out_dtype %d", a->epilogue, a->out_dtype);
@@ -512,40 +514,139 @@ int dispatch_dma(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
 
 // split-bf16 operands (bf16x3 mode): the epilogues that mode uses
 template <int BM, int BN, int WGM, int WGN, int NST, int BK = 64>
-int dispatch_s3(const v2a_gemm_args* a, const GemmParams& p, hipStream_t s) {
+int dispatch_s3(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
   const bool out_f32 = a->out_dtype == V2A_F32;
   switch (a->epilogue) {
     case V2A_EPI_STORE:
-      if (out_f32) return launch_dma<V2A_EPI_STORE, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      if (out_f32) return launch_dma<V2A_EPI_STORE, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       break;
     case V2A_EPI_GEGLU:
       if constexpr ((BN / WGN / 16) % 2 == 0) {
-        if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GEGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+        if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GEGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       }
       break;
     case V2A_EPI_SWIGLU:
       if constexpr ((BN / WGN / 16) % 2 == 0) {
-        if (out_f32) return launch_dma<V2A_EPI_SWIGLU, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
-        if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_SWIGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+        if (out_f32) return launch_dma<V2A_EPI_SWIGLU, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
+        if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_SWIGLU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       }
       break;
     case V2A_EPI_GELU:
-      if (out_f32) return launch_dma<V2A_EPI_GELU, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
-      if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GELU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      if (out_f32) return launch_dma<V2A_EPI_GELU, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
+      if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GELU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       break;
     case V2A_EPI_RESID:
-      if (out_f32) return launch_dma<V2A_EPI_RESID, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      if (out_f32) return launch_dma<V2A_EPI_RESID, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       break;
     case V2A_EPI_GATE_RESID:
-      if (out_f32) return launch_dma<V2A_EPI_GATE_RESID, float, BM, BN, WGM, WGN, NST, true, BK>(p, s);
+      if (out_f32) return launch_dma<V2A_EPI_GATE_RESID, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       break;
   }
   return v2a_fail(V2A_ERR_ARG, "v2a_gemm(split bf16): unsupported epilogue %d / out_dtype %d for this tile shape", a->epilogue, a->out_dtype);
 }
 
-// split operands on the 8-phase kernel: marks the launch as split (GemmParams::s3_kl = the logical K, K stays the logical K).  The kernel
-// stages 32 logical k of the hi and the lo plane of both operands together and forms A_lo x W_hi, A_hi x W_lo, A_hi x W_hi from one set of fragments
-void mark_split_8phase(GemmParams& q) { q.s3_kl = q.K; }
+// ---- the ring tile shapes: each is stated in its list below and instantiated by launch_ring_tile, nowhere else (the tile_hint comment of
+// include/v2a_cfm.h documents the same rows).  Plain bf16 x bf16 operands, keyed by k = v2a_tuning.gemm_force_tile = v2a_gemm_args.tile_hint - 1:
+//   X(k, BM, BN, wave rows, wave columns, ring depth)
+#define V2A_RING_TILES(X)                                                                    \
+  X(0, 128, 256, 2, 4, 3)  /* 8 waves, 144 KB LDS, 1 workgroup/CU */                         \
+  X(1, 128, 128, 2, 2, 3)  /* 4 waves,  96 KB */                                             \
+  X(2, 128, 64, 2, 2, 3)   /* 4 waves,  72 KB, 2 workgroups/CU */                            \
+  X(3, 64, 64, 2, 2, 3)    /* 4 waves,  48 KB, 3 workgroups/CU */                            \
+  X(5, 256, 256, 2, 4, 2)  /* 8 waves, 128x64 wave tiles, 2-deep ring of 64 KB stages */     \
+  X(7, 64, 128, 2, 2, 6)   /* 4 waves, 144 KB: 6-deep ring, 1 workgroup/CU (<= 256 tiles) */ \
+  X(8, 64, 64, 2, 2, 6)    /* 4 waves,  96 KB: 6-deep ring, 1 workgroup/CU (<= 256 tiles) */ \
+  X(9, 64, 64, 2, 2, 4)                                                                      \
+  X(10, 64, 64, 2, 2, 5)                                                                     \
+  X(11, 128, 128, 2, 2, 4)                                                                   \
+  X(12, 128, 128, 2, 4, 3) /* 8 waves (two per SIMD), wave tile 64x32 */                     \
+  X(13, 64, 64, 2, 4, 3)   /* 8 waves, wave tile 32x16 (no GEGLU) */                         \
+  X(14, 128, 64, 4, 2, 3)  /* 8 waves, wave tile 32x32 */                                    \
+  X(15, 64, 128, 2, 4, 3)  /* 8 waves, wave tile 32x32 */
+// the ids the code below names.  kTile8Phase is no ring shape: the 256x256 phase-interleaved kernel (gemm_8phase.hip); v2a_tuning.gemm_force_tile
+// reaches the ids up to kTileForceMax, the later shapes are asked for by hint only
+enum { kTile128x256 = 0, kTile128x128 = 1, kTile128x64 = 2, kTile64x64 = 3, kTile64x64Again = 4, kTile256x256 = 5, kTile8Phase = 6,
+       kTileForceMax = 8, kTile64x64Waves8 = 13, kTileMax = 15 };
+// Split (hi | lo plane) operands, keyed by the tile_hint itself; the planes double a stage.  (64x128 with four waves on 32-wide stages -- 72 KB,
+// two workgroups per CU -- measured 15-25 % slower than shape 4 at every size: profiles/r05_split_probe.txt; not kept.)
+//   X(hint, BM, BN, wave rows, wave columns, ring depth, K extent of a stage); offset tables run on the 64-wide K stage shapes, up to kSplitScatteredMax
+#define V2A_SPLIT_RING_TILES(X)                                                            \
+  X(1, 64, 64, 2, 2, 3, 64)    /*  96 KB */                                                \
+  X(2, 128, 64, 2, 2, 3, 64)   /* 144 KB */                                                \
+  X(3, 128, 128, 2, 4, 2, 64)  /* 8 waves, 128 KB */                                       \
+  X(4, 64, 128, 2, 4, 3, 64)   /* 8 waves, 144 KB */                                       \
+  X(6, 128, 256, 2, 4, 3, 32)  /* 8 waves, wave tile 64x64; 3 stages of 48 KB (round 5) */ \
+  X(7, 128, 128, 2, 4, 3, 32)  /* 8 waves, 3 stages of 32 KB (round 5) */
+enum { kSplit64x64 = 1, kSplit128x64 = 2, kSplit128x128 = 3, kSplit64x128 = 4, kSplit8Phase = 5, kSplit128x256K32 = 6, kSplitMax = 7, kSplitScatteredMax = 4 };
+
+#define V2A_TILE_CASE(id, ...) case id:
+constexpr bool is_ring_tile(int k) { switch (k) { V2A_RING_TILES(V2A_TILE_CASE) return true; } return false; }
+#define V2A_LAUNCH_PLAIN(id, BM, BN, WGM, WGN, NST) case id: return dispatch_dma<BM, BN, WGM, WGN, NST>(a, p, to);
+#define V2A_LAUNCH_SPLIT(id, BM, BN, WGM, WGN, NST, BK) case id: return dispatch_s3<BM, BN, WGM, WGN, NST, BK>(a, p, to);
+int launch_ring_tile(bool split, int id, const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
+  if (split) switch (id) { V2A_SPLIT_RING_TILES(V2A_LAUNCH_SPLIT) }
+  else switch (id == kTile64x64Again ? kTile64x64 : id) { V2A_RING_TILES(V2A_LAUNCH_PLAIN) }
+  return v2a_fail(V2A_ERR_ARG, "v2a_gemm: no %s ring tile %d", split ? "split" : "plain", id);
+}
+
+// ---- selection by shape: pure functions of the problem's extents, a few flags and the tuning; each returns an id of the lists above, chosen
+// by the workgroups the problem yields on bm x bn tiles (256 CUs)
+constexpr int64_t ntiles(int M, int N, int bm, int bn) { return (int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
+// register-staged exact-fp32 kernel, tile edge: 64x64 tiles while 128x128 ones would leave CUs idle (one clip: 13 x 8 tiles for N = 1024);
+// the K order of an output element does not depend on the tile, so the result is the same bit for bit
+int fp32_tile_by_shape(int M, int N) { return ntiles(M, N, 128, 128) < 224 && M > 64 ? 64 : 128; }
+
+// Plain bf16 x bf16.  dense: no offset tables and 16-byte aligned epilogue operands, what the 8-phase kernel needs.  Stand-alone launches
+// measured with scripts/gemm_probe.py; M = 1564 / 3128 / 6256 / 12512 rows = 1 / 2 / 4 / 8 clips:
+//   * 256x256 phase-interleaved kernel: wide outputs from min_tiles_8phase tiles; narrow outputs (512 < N < 2048) once they
+//     fill >= 150 CUs with one tile each (8 clips: 1045 vs 793 TF/s at 12512x1024x4096, 1135 vs 967 at 12512x1280x5120);
+//   * 128x256 ring kernel: wide outputs below that, narrow ones from ~4 clips (778 vs 534 TF/s at 6256x1024x4096) and N <= 512 at 8 clips (653 vs 450 TF/s at 12512x512x2048);
+//   * 128x128 from ~2 clips, 64x64 below (one clip: only small tiles give every CU work).
+int plain_tile_by_shape(int M, int N, bool dense, const v2a_detail::GemmTuning& tune) {
+  const bool can8 = tune.use_8phase && dense;
+  auto nt = [&](int bm, int bn) { return ntiles(M, N, bm, bn); };
+  if (N <= 64) return nt(128, 64) >= 512 ? kTile128x64 : kTile64x64;          // conv layers with few output channels
+  if (N <= 128) return nt(128, 128) >= 512 ? kTile128x128 : (nt(128, 64) >= 512 ? kTile128x64 : kTile64x64);
+  if (N >= 2048) {
+    if (can8 && nt(256, 256) >= tune.min_tiles_8phase) return kTile8Phase;
+    if (nt(256, 256) >= 512) return kTile256x256;                             // 8-phase kernel switched off: 2-deep ring of 64 KB stages
+    return nt(128, 256) >= 96 ? kTile128x256 : kTile64x64;
+  }
+  if (N > 512) {
+    if (can8 && nt(256, 256) >= 150) return kTile8Phase;
+    if (nt(128, 256) >= 180) return kTile128x256;
+    if (nt(128, 128) >= 180) return kTile128x128;
+  } else {
+    if (nt(128, 256) >= 150) return kTile128x256;
+    if (nt(128, 128) >= 256) return kTile128x128;
+  }
+  return nt(64, 64) >= 2048 && nt(128, 64) >= 512 ? kTile128x64 : kTile64x64;
+}
+
+// Split operands; glu: a GEGLU / SWIGLU epilogue; scattered: offset tables (implicit-GEMM convolution).  Stand-alone launches measured with
+// scripts/split_probe.py, profiles/r05_split_probe.txt.  (A 128x128 tile whose two wave groups alternate along K -- one multiplies a stage while the
+// other reads and stages the next -- was built and measured in round 5: 20-25 % slower than shape 7, bound by the DMA issue of its loading waves;
+// profiles/r05_pingpong_probe.txt, source kept as scripts/probes/gemm_pingpong.hip.txt)
+int split_tile_by_shape(int M, int N, bool glu, bool scattered, const v2a_detail::GemmTuning& tune) {
+  auto nt = [&](int bm, int bn) { return ntiles(M, N, bm, bn); };
+  if (scattered) {
+    // Video2Roll convolutions (scripts/v2r_split_tiles.py, one 251-frame clip per launch, RESID + ReLU + split shadow; us for shapes 1 / 2 / 3 / 4):
+    // N = 64,  M 1.41e6, K 576:  899 / 740 / 846 / 984;   N = 128, M 3.7e5, K 1152: 677 / 584 / 406 / 450;  N = 256, M 1.0e5, K 2304: 590 / 534 / 396 / 416;
+    // N = 512, M 2.9e4, K 4608: 632 / 620 / 401 / 450;  N = 128, M 4.7e4, K 512 (FTB4 conv0): 61 / 57 / 42 / 40.  128x64 for the 64-channel layers, the
+    // 8-wave 128x128 tile from N = 128 on; 64x128 only below 256 tiles of 128x128 (unmeasured for the encoder: its smallest launch has 365)
+    return N <= 64 ? kSplit128x64 : (nt(128, 128) >= 256 ? kSplit128x128 : kSplit64x128);
+  }
+  // the phase-interleaved 256x256 kernel on stages of 32 logical k x (hi | lo) planes, three products per stage (lo x hi, hi x lo, hi x hi; every plane is
+  // staged and read once, and its K loop hides the operand stream behind the MFMAs): wide outputs from 150 tiles (audio feed-forward at one clip, measured
+  // on the earlier three-pass form: 76 us against 102 us on the best split ring tile) and -- round 5 -- narrow ones (512 < N < 2048, any number of logical
+  // segments) from 150 tiles, i.e. from ~6 clips per GPU: at 8 clips the 64x128 split ring ran them at 28 % of the MFMA peak (issued products) against 46 % here
+  if (tune.use_8phase && N > 512 && nt(256, 256) >= 150) return kSplit8Phase;
+  if (glu || N >= 2048) return nt(128, 128) >= 200 ? kSplit128x128 : kSplit64x128;
+  // N <= 512 with many rows (the frames stream at 8 clips per GPU: 98 tiles of 256x256 cannot fill the chip on the 8-phase kernel):
+  // 128x256 tiles on 32-wide K stages, 960 against 721 TF/s (64x128) at 12512x512x2048
+  if (N <= 512 && nt(128, 256) >= 128) return kSplit128x256K32;
+  return nt(64, 128) >= 160 ? kSplit64x128 : kSplit64x64;
+}
 
 }  // namespace
 
@@ -574,7 +675,8 @@ extern "C" int v2a_set_tuning(const v2a_tuning* t) {
   // every field is checked before any is assigned: a rejected call leaves the previous tuning whole
   V2A_REQUIRE(t->dwconv_rows_per_wave == 0 || t->dwconv_rows_per_wave == 4 || t->dwconv_rows_per_wave == 6 || t->dwconv_rows_per_wave == -1,
               "v2a_set_tuning: dwconv_rows_per_wave %d", t->dwconv_rows_per_wave);
-  V2A_REQUIRE(t->gemm_force_tile >= -1 && t->gemm_force_tile <= 8 && t->gemm_force_tile != 4, "v2a_set_tuning: gemm_force_tile %d", t->gemm_force_tile);
+  V2A_REQUIRE(t->gemm_force_tile == -1 || (t->gemm_force_tile <= kTileForceMax && (t->gemm_force_tile == kTile8Phase || is_ring_tile(t->gemm_force_tile))),
+              "v2a_set_tuning: gemm_force_tile %d", t->gemm_force_tile);
   V2A_REQUIRE(t->gemm_8phase >= 0 && t->gemm_8phase <= 2, "v2a_set_tuning: gemm_8phase %d", t->gemm_8phase);
   V2A_REQUIRE(t->gemm_8phase_min_tiles >= 0 && t->attn_one_group_from >= 0, "v2a_set_tuning: negative threshold");
   v2a_detail::g_dwconv_rows_per_wave = t->dwconv_rows_per_wave > 0 ? t->dwconv_rows_per_wave : 4;
@@ -766,148 +868,55 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   return V2A_OK;
 }
 
-extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) {
+// gemm_prepare -> kernel family -> tile id (asked for by hint, forced by v2a_set_tuning, or by shape) -> that tile's launcher
+static int gemm_dispatch(const v2a_gemm_args* a, GemmTarget to) {
   GemmParams p;
   if (int rc = gemm_prepare(a, p)) return rc;
-  const bool split_in = a->a_dtype == V2A_BF16_SPLIT;
   const v2a_detail::GemmTuning tune = v2a_detail::g_gemm_tuning;
-  hipStream_t s = (hipStream_t)stream;
-  if (a->compute_dtype == V2A_F32) {
-    // exact-fp32 kernel: 64x64 tiles while 128x128 ones would leave CUs idle (one clip: 13 x 8 tiles for N = 1024); the K order of
-    // an output element does not depend on the tile, so the result is the same bit for bit
-    const int64_t t128 = (int64_t)((a->M + 127) / 128) * ((a->N + 127) / 128);
-    if (t128 < 224 && a->M > 64) return dispatch_epi<float, false, 64, 64>(a, p, s);
-    return dispatch_epi<float, false, 128, 128>(a, p, s);
-  }
-  if (split_in) {
+  const bool scattered = a->a_row_offset || a->out_row_offset;
+  if (a->compute_dtype == V2A_F32)
+    return fp32_tile_by_shape(a->M, a->N) == 64 ? dispatch_epi<float, false, 64, 64>(a, p, to) : dispatch_epi<float, false, 128, 128>(a, p, to);
+  if (a->a_dtype == V2A_BF16_SPLIT) {
     V2A_REQUIRE(p.vec_epi, "v2a_gemm: split operands need 16-byte aligned epilogue operands");
-    V2A_REQUIRE(a->tile_hint >= 0 && a->tile_hint <= 7, "v2a_gemm: tile_hint %d with split operands (0 = by shape, 1..7)", a->tile_hint);
+    V2A_REQUIRE(a->tile_hint >= 0 && a->tile_hint <= kSplitMax, "v2a_gemm: tile_hint %d with split operands (0 = by shape, 1..7)", a->tile_hint);
     // implicit-GEMM convolution (the bf16x3 Video2Roll encoder): offset tables run on the BK = 64 split ring shapes 1..4 only -- the
     // 8-phase kernel knows dense rows only, and the K-tile tables are laid out for 64-wide K tiles (shapes 6 / 7 stage 32)
-    const bool scattered = a->a_row_offset || a->out_row_offset;
-    V2A_REQUIRE(!scattered || a->tile_hint <= 4,
+    V2A_REQUIRE(!scattered || a->tile_hint <= kSplitScatteredMax,
                 "v2a_gemm: tile_hint %d with split operands and offset tables (0 = by shape, 1..4: the 64-wide K stage ring shapes)", a->tile_hint);
-    auto nt = [&](int bm, int bn) { return (int64_t)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
-    // split-operand tile shapes (hi + lo planes double a stage): 1 = 64x64 (96 KB), 2 = 128x64 (144 KB), 3 = 128x128 with 8 waves and a
-    // 2-deep ring (128 KB), 4 = 64x128 with 8 waves (144 KB), 5 = the 8-phase kernel; with 32-wide K stages (round 5): 6 = 128x256 with
-    // 8 waves (wave tile 64x64; 3 stages of 48 KB), 7 = 128x128 with 8 waves (3 stages of 32 KB).  (64x128 with four waves on 32-wide
-    // stages -- 72 KB, two workgroups per CU -- measured 15-25 % slower than shape 4 at every size: profiles/r05_split_probe.txt; not kept.)
-    int cfg = a->tile_hint;
-    // the phase-interleaved 256x256 kernel on stages of 32 logical k x (hi | lo) planes, three products per stage (lo x hi, hi x lo,
-    // hi x hi; every plane is staged and read once, and its K loop hides the operand stream behind the MFMAs): wide outputs from 150
-    // tiles (audio feed-forward at one clip, measured on the earlier three-pass form: 76 us against 102 us on the best split ring tile) and -- round 5 -- narrow ones (512 < N < 2048, any number of logical segments) from 150 tiles,
-    // i.e. from ~6 clips per GPU: at 8 clips the 64x128 split ring ran them at 28 % of the MFMA peak (issued products) against 46 % here.
-    // tile_hint 5 asks for it, 0 picks by shape.
-    const bool wide8 = !scattered && tune.use_8phase && (cfg == 5 || (cfg == 0 && a->N > 512 && nt(256, 256) >= 150));
-    if (wide8) {
-      GemmParams q = p;
-      mark_split_8phase(q);
+    int id = a->tile_hint ? a->tile_hint : split_tile_by_shape(a->M, a->N, is_glu(a->epilogue), scattered, tune);
+    if (id == kSplit8Phase && !tune.use_8phase) id = kSplit64x128;      // asked for by hint with the kernel switched off
+    if (id != kSplit8Phase) return launch_ring_tile(true, id, a, p, to);
+    p.s3_kl = p.K;      // marks the launch as split: 32 logical k of the hi and the lo plane of both operands per stage, K stays the logical K
 #ifdef V2A_GEMM_PROBE
-      if (tune.dbg & 32) q.s3_kl = 0;                   // error attribution: hi x hi only (the plain form on the hi planes)
+    if (tune.dbg & 32) p.s3_kl = 0;                     // error attribution: hi x hi only (the plain form on the hi planes)
 #endif
-      return v2a_detail::launch_gemm_8phase(q, a->epilogue, a->out_dtype == V2A_BF16_SPLIT ? V2A_BF16 : a->out_dtype, s);
-    }
-    // (a 128x128 tile whose two wave groups alternate along K -- one multiplies a stage while the other reads and stages the next -- was built
-    // and measured in round 5: 20-25 % slower than shape 7, bound by the DMA issue of its loading waves; profiles/r05_pingpong_probe.txt, source
-    // kept as scripts/probes/gemm_pingpong.hip.txt)
-    if (cfg == 0 && scattered) {
-      // Video2Roll convolutions (scripts/v2r_split_tiles.py, one 251-frame clip per launch, RESID + ReLU + split shadow; us for
-      // shapes 1 / 2 / 3 / 4):  N = 64,  M 1.41e6, K 576:  899 / 740 / 846 / 984;   N = 128, M 3.7e5, K 1152: 677 / 584 / 406 / 450;
-      // N = 256, M 1.0e5, K 2304: 590 / 534 / 396 / 416;  N = 512, M 2.9e4, K 4608: 632 / 620 / 401 / 450;  N = 128, M 4.7e4, K 512
-      // (FTB4 conv0): 61 / 57 / 42 / 40.  128x64 for the 64-channel layers, the 8-wave 128x128 tile from N = 128 on; 64x128 only
-      // below 256 tiles of 128x128 (unmeasured for the encoder: its smallest launch has 365)
-      cfg = a->N <= 64 ? 2 : (nt(128, 128) >= 256 ? 3 : 4);
-    } else if (cfg == 0) {
-      // (stand-alone, scripts/split_probe.py, profiles/r05_split_probe.txt)
-      if (is_glu(a->epilogue) || a->N >= 2048) cfg = nt(128, 128) >= 200 ? 3 : 4;
-      // N <= 512 with many rows (the frames stream at 8 clips per GPU: 98 tiles of 256x256 cannot fill the chip on the 8-phase kernel):
-      // 128x256 tiles on 32-wide K stages, 960 against 721 TF/s (64x128) at 12512x512x2048
-      else if (a->N <= 512 && nt(128, 256) >= 128) cfg = 6;
-      else cfg = nt(64, 128) >= 160 ? 4 : 1;
-    }
-    switch (cfg) {
-      case 1: return dispatch_s3<64, 64, 2, 2, 3>(a, p, s);
-      case 2: return dispatch_s3<128, 64, 2, 2, 3>(a, p, s);
-      case 3: return dispatch_s3<128, 128, 2, 4, 2>(a, p, s);
-      case 6: return dispatch_s3<128, 256, 2, 4, 3, 32>(a, p, s);
-      case 7: return dispatch_s3<128, 128, 2, 4, 3, 32>(a, p, s);
-      default: return dispatch_s3<64, 128, 2, 4, 3>(a, p, s);
-    }
+    return v2a_detail::launch_gemm_8phase(p, a->epilogue, a->out_dtype == V2A_BF16_SPLIT ? V2A_BF16 : a->out_dtype, to);
   }
-  if (a->a_dtype == V2A_F32) return dispatch_epi<bf16_t, true, 128, 128>(a, p, s);
-  if (a->epilogue == V2A_EPI_SIGMOID) return dispatch_epi<bf16_t, false, 128, 128>(a, p, s);
-  // bf16 x bf16: LDS-DMA kernel; tile shape by how many workgroups the problem yields (256 CUs)
-  auto ntiles = [&](int bm, int bn) { return (int64_t)((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn); };
-  // wide outputs: 256x256 tile with the phase-interleaved K loop (gemm_8phase.hip) once the problem yields enough tiles
-  V2A_REQUIRE(a->tile_hint >= 0 && a->tile_hint <= 16, "v2a_gemm: tile_hint %d", a->tile_hint);
+  if (a->a_dtype == V2A_F32) return dispatch_epi<bf16_t, true, 128, 128>(a, p, to);
+  if (a->epilogue == V2A_EPI_SIGMOID) return dispatch_epi<bf16_t, false, 128, 128>(a, p, to);
+  // bf16 x bf16: the LDS-DMA ring kernel or the 8-phase kernel
+  V2A_REQUIRE(a->tile_hint >= 0 && a->tile_hint <= kTileMax + 1, "v2a_gemm: tile_hint %d", a->tile_hint);
   // the producer's partial sums are butterflies over the 8 lanes that hold 32 columns of ONE row: with 16-column wave tiles a row has 4 lanes,
   // an octet would add 16 columns each of two rows, and the two waves of a 32-column group would write the same entry
-  V2A_REQUIRE(a->tile_hint != 14 || !a->norm_ssq,
+  V2A_REQUIRE(a->tile_hint != kTile64x64Waves8 + 1 || !a->norm_ssq,
               "v2a_gemm: tile_hint 14 (64x64 tiles, wave tile 32x16) cannot write norm_ssq: the partial sums per 32 columns need wave tiles of "
               "at least 32 columns");
-  const bool dense = !a->a_row_offset && !a->out_row_offset && p.vec_epi;
-  if (a->tile_hint > 0 && tune.force_tile < 0) {
-    if (a->tile_hint == 7) {
-      V2A_REQUIRE(dense, "v2a_gemm: tile_hint 7 (256x256 8-phase) needs dense rows and 16-byte aligned epilogue operands");
-      return v2a_detail::launch_gemm_8phase(p, a->epilogue, a->out_dtype, s);
-    }
-    switch (a->tile_hint - 1) {
-      case 5: return dispatch_dma<256, 256, 2, 4, 2>(a, p, s);
-      case 0: return dispatch_dma<128, 256, 2, 4>(a, p, s);
-      case 1: return dispatch_dma<128, 128, 2, 2>(a, p, s);
-      case 2: return dispatch_dma<128, 64, 2, 2>(a, p, s);
-      case 7: return dispatch_dma<64, 128, 2, 2, 6>(a, p, s);
-      case 8: return dispatch_dma<64, 64, 2, 2, 6>(a, p, s);
-      case 9: return dispatch_dma<64, 64, 2, 2, 4>(a, p, s);
-      case 10: return dispatch_dma<64, 64, 2, 2, 5>(a, p, s);
-      case 11: return dispatch_dma<128, 128, 2, 2, 4>(a, p, s);
-      case 12: return dispatch_dma<128, 128, 2, 4, 3>(a, p, s);   // 8 waves (two per SIMD), wave tile 64x32
-      case 13: return dispatch_dma<64, 64, 2, 4, 3>(a, p, s);     // 8 waves, wave tile 32x16 (no GEGLU)
-      case 14: return dispatch_dma<128, 64, 4, 2, 3>(a, p, s);    // 8 waves, wave tile 32x32
-      case 15: return dispatch_dma<64, 128, 2, 4, 3>(a, p, s);    // 8 waves, wave tile 32x32
-      default: return dispatch_dma<64, 64, 2, 2>(a, p, s);
-    }
-  }
-  // Tile shape by how many workgroups the problem yields on 256 CUs (stand-alone launches measured with scripts/gemm_probe.py;
-  // M = 1564 / 3128 / 6256 / 12512 rows = 1 / 2 / 4 / 8 clips):
-  //   * 256x256 phase-interleaved kernel: wide outputs from min_tiles_8phase tiles; narrow outputs (512 < N < 2048) once they
-  //     fill >= 150 CUs with one tile each (8 clips: 1045 vs 793 TF/s at 12512x1024x4096, 1135 vs 967 at 12512x1280x5120);
-  //   * 128x256 ring kernel: wide outputs below that, narrow ones from ~4 clips (778 vs 534 TF/s at 6256x1024x4096) and
-  //     N <= 512 at 8 clips (653 vs 450 TF/s at 12512x512x2048);
-  //   * 128x128 from ~2 clips, 64x64 below (one clip: only small tiles give every CU work).
-  const bool can8 = tune.use_8phase && dense;
+  const bool dense = !scattered && p.vec_epi;
+  const bool hinted = a->tile_hint > 0 && tune.force_tile < 0;
+  V2A_REQUIRE(!hinted || a->tile_hint - 1 != kTile8Phase || dense, "v2a_gemm: tile_hint 7 (256x256 8-phase) needs dense rows and 16-byte aligned epilogue operands");
   // a forced 8-phase kernel applies to dense launches only: it knows nothing of the implicit-GEMM offset tables (Video2Roll
   // convolutions), which keep their by-shape choice
-  if (tune.force_tile == 6 && dense) return v2a_detail::launch_gemm_8phase(p, a->epilogue, a->out_dtype, s);
-  int cfg;
-  if (tune.force_tile >= 0 && tune.force_tile != 6) cfg = tune.force_tile;
-  else if (a->N <= 64) cfg = ntiles(128, 64) >= 512 ? 2 : 3;          // conv layers with few output channels
-  else if (a->N <= 128) cfg = ntiles(128, 128) >= 512 ? 1 : (ntiles(128, 64) >= 512 ? 2 : 3);
-  else if (a->N >= 2048) {
-    if (can8 && ntiles(256, 256) >= tune.min_tiles_8phase) cfg = 6;
-    else if (ntiles(256, 256) >= 512) cfg = 5;                         // 8-phase kernel switched off: 2-deep ring of 64 KB stages
-    else if (ntiles(128, 256) >= 96) cfg = 0;
-    else cfg = 3;
-  } else if (a->N > 512) {
-    if (can8 && ntiles(256, 256) >= 150) cfg = 6;
-    else if (ntiles(128, 256) >= 180) cfg = 0;
-    else if (ntiles(128, 128) >= 180) cfg = 1;
-    else if (ntiles(64, 64) >= 2048 && ntiles(128, 64) >= 512) cfg = 2;
-    else cfg = 3;
-  } else {
-    if (ntiles(128, 256) >= 150) cfg = 0;
-    else if (ntiles(128, 128) >= 256) cfg = 1;
-    else if (ntiles(64, 64) >= 2048 && ntiles(128, 64) >= 512) cfg = 2;
-    else cfg = 3;
-  }
-  if (cfg == 6) return v2a_detail::launch_gemm_8phase(p, a->epilogue, a->out_dtype, s);
-  switch (cfg) {
-    case 5: return dispatch_dma<256, 256, 2, 4, 2>(a, p, s); // 8 waves, 128x64 wave tiles, 2-deep ring of 64 KB stages
-    case 0: return dispatch_dma<128, 256, 2, 4>(a, p, s);   // 8 waves, 144 KB LDS, 1 workgroup/CU
-    case 1: return dispatch_dma<128, 128, 2, 2>(a, p, s);   // 4 waves,  96 KB
-    case 2: return dispatch_dma<128, 64, 2, 2>(a, p, s);    // 4 waves,  72 KB, 2 workgroups/CU
-    case 7: return dispatch_dma<64, 128, 2, 2, 6>(a, p, s); // 4 waves, 144 KB: 6-deep ring, 1 workgroup/CU (<= 256 tiles)
-    case 8: return dispatch_dma<64, 64, 2, 2, 6>(a, p, s);  // 4 waves,  96 KB: 6-deep ring, 1 workgroup/CU (<= 256 tiles)
-    default: return dispatch_dma<64, 64, 2, 2>(a, p, s);    // 4 waves,  48 KB, 3 workgroups/CU
-  }
+  const bool forced = tune.force_tile >= 0 && (tune.force_tile != kTile8Phase || dense);
+  const int k = hinted ? a->tile_hint - 1 : (forced ? tune.force_tile : plain_tile_by_shape(a->M, a->N, dense, tune));
+  if (k == kTile8Phase) return v2a_detail::launch_gemm_8phase(p, a->epilogue, a->out_dtype, to);
+  return launch_ring_tile(false, k, a, p, to);
 }
+
+extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) { return gemm_dispatch(a, {(hipStream_t)stream, nullptr}); }
+
+extern "C" int v2a_gemm_choose(const v2a_gemm_args* a, v2a_gemm_choice* choice) {
+  V2A_REQUIRE(choice != nullptr, "v2a_gemm_choose: null choice");
+  *choice = {};
+  return gemm_dispatch(a, {nullptr, choice});
+}
+

@@ -304,52 +304,51 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmParams p) {
 }
 
 template <int EPI, typename OutT>
-int launch_8ph(const GemmParams& p_in, hipStream_t s) {
+int launch_8ph(const GemmParams& p_in, GemmTarget to) {
   GemmParams p = p_in;
   v2a_detail::fill_tile_map(p, 256, 256);
   constexpr size_t smem = 2 * 4 * 128 * 128 + 256 * 4;     // two buffers of four half tiles + one row scale per tile row (folded RMSNorm)
   const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
   const int mode = v2a_detail::g_gemm_tuning.use_8phase;
-  auto go = [&](auto kern) -> int {
+  // SPLIT: a stage is 32 logical k of the hi and the lo plane, otherwise 64 k (the kernel's KS); 2 x 4 waves with 128x64 wave tiles, two buffers
+  auto go = [&](auto kern, bool split) -> int {
+    if (to.chosen(p, V2A_GEMM_8PHASE, split, 256, 256, split ? 32 : 64, 2, 4, 2, tiles)) return 0;
     static std::atomic<uint64_t> lds_set{0};
     if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(kern), smem, lds_set, "v2a_gemm(8-phase)")) return rc;
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), smem, s, p);
-    return 0;
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), smem, to.stream, p);
+    return v2a_check_launch("v2a_gemm(8-phase)");
   };
-  int rc;
   if (p.s3_kl != 0) {
-    if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2, true>);
-    else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1, true>);
+    if (mode == 2) return go(gemm_bf16_8ph_kernel<EPI, OutT, 2, true>, true);
+    return go(gemm_bf16_8ph_kernel<EPI, OutT, 1, true>, true);
   } else if constexpr (EPI == V2A_EPI_GELU || EPI == V2A_EPI_SWIGLU) {
     return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): GELU / SWIGLU need split operands");
   } else {
-    if (mode == 2) rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 2, false>);
-    else rc = go(gemm_bf16_8ph_kernel<EPI, OutT, 1, false>);
+    if (mode == 2) return go(gemm_bf16_8ph_kernel<EPI, OutT, 2, false>, false);
+    return go(gemm_bf16_8ph_kernel<EPI, OutT, 1, false>, false);
   }
-  if (rc) return rc;
-  return v2a_check_launch("v2a_gemm(8-phase)");
 }
 
 }  // namespace
 
-int v2a_detail::launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dtype, hipStream_t s) {
+int v2a_detail::launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dtype, GemmTarget to) {
   const bool out_f32 = out_dtype == V2A_F32;
   switch (epilogue) {
     case V2A_EPI_STORE:
-      return out_f32 ? launch_8ph<V2A_EPI_STORE, float>(p, s) : launch_8ph<V2A_EPI_STORE, bf16_t>(p, s);
+      return out_f32 ? launch_8ph<V2A_EPI_STORE, float>(p, to) : launch_8ph<V2A_EPI_STORE, bf16_t>(p, to);
     case V2A_EPI_GEGLU:
-      return out_f32 ? launch_8ph<V2A_EPI_GEGLU, float>(p, s) : launch_8ph<V2A_EPI_GEGLU, bf16_t>(p, s);
+      return out_f32 ? launch_8ph<V2A_EPI_GEGLU, float>(p, to) : launch_8ph<V2A_EPI_GEGLU, bf16_t>(p, to);
     case V2A_EPI_GELU:     // v2a_gemm admits it here with split operands only (fp32 output, or hi | lo planes through bf16_t + out_split)
-      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_GELU, float>(p, s) : launch_8ph<V2A_EPI_GELU, bf16_t>(p, s);
+      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_GELU, float>(p, to) : launch_8ph<V2A_EPI_GELU, bf16_t>(p, to);
       break;
     case V2A_EPI_SWIGLU:   // likewise: split operands only
-      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_SWIGLU, float>(p, s) : launch_8ph<V2A_EPI_SWIGLU, bf16_t>(p, s);
+      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_SWIGLU, float>(p, to) : launch_8ph<V2A_EPI_SWIGLU, bf16_t>(p, to);
       break;
     case V2A_EPI_RESID:
-      if (out_f32) return launch_8ph<V2A_EPI_RESID, float>(p, s);
+      if (out_f32) return launch_8ph<V2A_EPI_RESID, float>(p, to);
       break;
     case V2A_EPI_GATE_RESID:
-      if (out_f32) return launch_8ph<V2A_EPI_GATE_RESID, float>(p, s);
+      if (out_f32) return launch_8ph<V2A_EPI_GATE_RESID, float>(p, to);
       break;
   }
   return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): unsupported epilogue %d / out_dtype %d", epilogue, out_dtype);

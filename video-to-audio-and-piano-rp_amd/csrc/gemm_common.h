@@ -81,8 +81,20 @@ extern int g_dwconv_rows_per_wave;   // 4 or 8 (v2a_set_tuning)
 extern int g_probe_dbg;              // v2a_tuning.reserved[0] (probe builds)
 extern int g_dwconv_stream;          // 0: never use the streaming depthwise conv (v2a_tuning.dwconv_rows_per_wave = -1)
 
+// Where a launcher sends its instantiation: to a stream, or -- v2a_gemm_choose -- into a report.  Every launcher calls chosen() with its
+// own template constants after its last argument check and in front of its first HIP call, and returns at once when that answers true:
+// what is reported is what that very code would have launched.
+struct GemmTarget {
+  hipStream_t stream;
+  v2a_gemm_choice* report;   // null: launch
+  bool chosen(const GemmParams& p, int family, bool split, int bm, int bn, int bk, int waves_m, int waves_n, int stages, int tiles) const {
+    if (report) *report = {family, split, bm, bn, bk, waves_m, waves_n, stages, tiles, p.xcd_gm, p.xcd_gn, p.vec_epi};
+    return report != nullptr;
+  }
+};
+
 // 256x256 8-phase kernel (gemm_8phase.hip)
-int launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dtype, hipStream_t stream);
+int launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dtype, GemmTarget to);
 
 // host: the gm x gn rectangles of the tile space for a BM x BN tile shape (xcd_gm / xcd_gn chosen by v2a_gemm)
 inline void fill_tile_map(GemmParams& p, int BM, int BN) {
@@ -108,6 +120,7 @@ inline void fill_tile_map(GemmParams& p, int BM, int BN) {
 namespace {
 
 using v2a_detail::GemmParams;
+using v2a_detail::GemmTarget;
 
 // Workgroup -> output tile, XCD-aware.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the L2 a block
 // uses), every XCD has its own 4 MB L2, and an operand panel shared by workgroups on different XCDs is fetched once per XCD.

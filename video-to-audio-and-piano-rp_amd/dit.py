@@ -223,7 +223,7 @@ class PackedWeights:
 # ---- measured tile choices, in ONE place -----------------------------------------------------------------------------------------
 # key: (compute mode, regime, (dim, dim_text, dim_frames, ff_mult)); regime as DiTEngine._regime(): 0 = a launch cannot fill the chip (one
 # clip at these widths), 1 = about fills it (two clips), 2 = fills it several times over.  value: {(stream, op): (tile, log)} where
-# `tile` is a tile configuration of v2a_gemm (bf16: the k of tile_hint = k + 1; bf16x3: the split-operand shape 1..5 = tile_hint) and `log`
+# `tile` is a tile id of v2a_gemm by its name in _lib (bf16: L.TILE_*, the k of tile_hint = k + 1; bf16x3: L.SPLIT_TILE_*, the tile_hint) and `log`
 # names the A/B record under profiles/ that justifies the entry.  streams a / t / f; ops: x_tfa skip qkv out q2 out2 ff1 ff2 (audio),
 # cross qkv out ff1 ff2 (text, frames).  A (mode, regime, widths) without a row, and an op without an entry, take the stream's policy
 # tile (DiTEngine.side_tile / main_tile: fat 128x256 tiles on the side streams, the library's choice on the audio stream) -- correct
@@ -231,15 +231,17 @@ class PackedWeights:
 SHIPPED_WIDTHS = (1024, 1280, 512, 4)
 _R2, _R3 = "profiles/r02 A/B runs (DESIGN.md appendix A, `scripts/gpu_ci.sh sidetiles`)", "profiles/r03_tile_sweep.txt"
 _R5 = "profiles/r05_bf16x3_tile_sweeps.txt"
+_W8, _NARROW, _PH8 = L.TILE_128x128_8WAVES, L.TILE_128x64_8WAVES, L.TILE_8PHASE     # plain tiles: the k of tile_hint = k + 1
+_S_PH8, _S_FAT = L.SPLIT_TILE_8PHASE, L.SPLIT_TILE_128x256_K32                    # split-operand tiles: the tile_hint itself
 TUNED_TILES = {
     ("bf16", 0, SHIPPED_WIDTHS): {
         # text stream co-critical with the audio stream: its 1280-wide GEMMs on 128x128 tiles with eight waves (tile 12), feed-forward in on
         # the 256x256 8-phase kernel (tile 6)
-        ("t", "cross"): (12, _R3), ("t", "out"): (12, _R3), ("t", "ff2"): (12, _R3), ("t", "ff1"): (6, _R2),
-        ("f", "cross"): (12, _R3), ("f", "out"): (12, _R3), ("f", "ff2"): (12, _R3), ("f", "ff1"): (6, _R2), ("f", "qkv"): (6, _R2),
+        ("t", "cross"): (_W8, _R3), ("t", "out"): (_W8, _R3), ("t", "ff2"): (_W8, _R3), ("t", "ff1"): (_PH8, _R2),
+        ("f", "cross"): (_W8, _R3), ("f", "out"): (_W8, _R3), ("f", "ff2"): (_W8, _R3), ("f", "ff1"): (_PH8, _R2), ("f", "qkv"): (_PH8, _R2),
         # audio stream: narrow outputs on 128x64 tiles with eight waves (tile 14), QKV on 128x128 (tile 1), feed-forward in on the 8-phase kernel
-        ("a", "x_tfa"): (14, _R3), ("a", "skip"): (14, _R3), ("a", "out"): (14, _R3), ("a", "out2"): (14, _R3), ("a", "ff2"): (14, _R3),
-        ("a", "qkv"): (1, _R2), ("a", "ff1"): (6, _R2),
+        ("a", "x_tfa"): (_NARROW, _R3), ("a", "skip"): (_NARROW, _R3), ("a", "out"): (_NARROW, _R3), ("a", "out2"): (_NARROW, _R3),
+        ("a", "ff2"): (_NARROW, _R3), ("a", "qkv"): (L.TILE_128x128, _R2), ("a", "ff1"): (_PH8, _R2),
     },
     # two clips: the one-clip table costs 4 % here (6214 vs 6467 mel-frames/s, round 2): policy tiles only
     ("bf16", 1, SHIPPED_WIDTHS): {},
@@ -254,8 +256,9 @@ TUNED_TILES = {
     # ... and, once the 8-phase kernel's K loop had lost its address bookkeeping, the frames stream's two WIDE GEMMs on it: QKV
     # (N = 1552: 49 workgroups instead of 91) and feed-forward in (N = 4096: 112 instead of 208), the cheapest tile per flop in chip-time: +0.9 %
     # (sweep 7 of the same file).  Its narrow GEMMs stay on the ring: 14 tiles of 256x256 take 125 us each and the chain's slack is gone.
-    ("bf16x3", 0, SHIPPED_WIDTHS): {("a", "qkv"): (5, "profiles/r04_bf16x3_qkv_8phase_ab.txt"), ("t", "qkv"): (5, "profiles/r04_bf16x3_qkv_8phase_ab.txt"),
-                                    ("f", "qkv"): (5, _R5), ("f", "ff1"): (5, _R5), ("f", "cross"): (6, _R5), ("f", "out"): (6, _R5), ("f", "ff2"): (6, _R5)},
+    ("bf16x3", 0, SHIPPED_WIDTHS): {("a", "qkv"): (_S_PH8, "profiles/r04_bf16x3_qkv_8phase_ab.txt"), ("t", "qkv"): (_S_PH8, "profiles/r04_bf16x3_qkv_8phase_ab.txt"),
+                                    ("f", "qkv"): (_S_PH8, _R5), ("f", "ff1"): (_S_PH8, _R5), ("f", "cross"): (_S_FAT, _R5), ("f", "out"): (_S_FAT, _R5),
+                                    ("f", "ff2"): (_S_FAT, _R5)},
     # bf16x3, launches that fill the chip several times over (8 clips per GPU): no entry.  The QKV projections on 128x256 tiles with 32-wide K
     # stages are 4-12 % faster stand-alone than on the 8-phase kernel (228 / 280 / 80 against 240 / 290 / 91 us: 637 tiles of 256x256 are 2.49
     # rounds, the 13th tile column holds 16 gate columns) and 1.2 % SLOWER in the sampler (3566 against 3608 mel-frames/s,
@@ -315,8 +318,8 @@ class DiTEngine:
         # policy tile: `side_tile` on the text / frames streams (set above), `main_tile` on the audio stream's narrow GEMMs (-1 = library).
         widths = (cfg.dim, cfg.dim_text, cfg.dim_frames, cfg.ff_mult)
         one_clip = tuned_tiles("bf16", 0, widths)
-        self.side_tiles = {k: v for k, v in one_clip.items() if not (k[0] == "a" and v == 14)}
-        self.main_tile = 14 if any(k[0] == "a" and v == 14 for k, v in one_clip.items()) else -1
+        self.side_tiles = {k: v for k, v in one_clip.items() if not (k[0] == "a" and v == _NARROW)}
+        self.main_tile = _NARROW if any(k[0] == "a" and v == _NARROW for k, v in one_clip.items()) else -1
         self.big_tiles = tuned_tiles("bf16", 2, widths)
         self.split_tiles = tuned_tiles("bf16x3", 0, widths)      # bf16x3 mode: split-operand tile shape 1..7 of v2a_gemm per (stream, op), up to two clips
         self.split_big_tiles = tuned_tiles("bf16x3", 2, widths)  # ... for launches that fill the chip several times over
