@@ -1,12 +1,13 @@
-"""Launch-trace guard of the DiT, Video2Roll and image-encoder (CLIP, DINOv2) engines: what the GPU is asked to do, pinned on the CPU.
+"""Launch-trace guard of the DiT, Video2Roll, Roll2Midi, Encodec and image-encoder (CLIP, DINOv2) engines: what the GPU is asked to
+do, pinned on the CPU.
 
 The real Python engines run on device="cpu" against a fake libv2a_cfm that records every entry-point call: its name, its
 scalars, every ctypes.Structure argument field by field, and the (key, flops, bytes) that `_lib._launch` hands to a
 profiler (bench.py's roofline accounting).  Device pointers are written as (allocation index, byte offset, allocation size):
 allocations are the storages reachable from the engine (plans, packed weights, Video2Roll maps and tables) and the case's own
 inputs, numbered in the order they first appear in the trace; any other pointer is "tmp" (the CPU allocator reuses freed
-addresses, so temporaries have no stable identity).  Nothing is computed: the DiT and Video2Roll weights are zeros, the image
-encoders' are the seeded ones of synth.py (their host-side weight preparation runs).
+addresses, so temporaries have no stable identity).  Nothing is computed: the DiT, Video2Roll and Roll2Midi weights are zeros, the
+image encoders' and Encodec's are the seeded ones of synth.py (their host-side weight preparation runs).
 
 tests/golden/launch_trace.json.gz holds the trace of every case below and the tile-hint decisions of the DiT engine.  A change
 that means to alter the launch sequence regenerates it with `python tests/test_launch_trace.py --write [PATH]` and says so."""
@@ -30,6 +31,8 @@ from v2a_amd import _lib as L, synth  # noqa: E402
 from v2a_amd.clip import CLIPImageEncoder  # noqa: E402
 from v2a_amd.dinov2 import DINOv2ImageEncoder  # noqa: E402
 from v2a_amd.dit import DiTConfig, DiTEngine  # noqa: E402
+from v2a_amd.encodec import EncodecDecoder, EncodecEncoder  # noqa: E402
+from v2a_amd.roll2midi import Roll2MidiEngine, expected_state_dict_shapes as r2m_shapes  # noqa: E402
 from v2a_amd.video2roll import Video2RollEngine, expected_state_dict_shapes as v2r_shapes  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "launch_trace.json.gz")
@@ -212,6 +215,39 @@ def _v2r_case(mode, t=5, chunk=None):
     return lambda: _traced(run)
 
 
+def _r2m_case(mode, tail=None):
+    """Three 12 x 20 windows at chunk 2: a chunk of 2 and a chunk of 1, so maps and tables are built for two sizes.  tail: `refine`
+    of 2 x 25 frames in windows of 10 instead (the window cutting and the width of the last, shorter window)."""
+    def run(roots):
+        eng = Roll2MidiEngine({k: torch.zeros(s) for k, s in r2m_shapes().items()}, device="cpu", compute=mode, chunk=2)
+        x = torch.zeros(3, 1, 12, 20) if tail is None else torch.zeros(2, 25, 12)
+        roots += [eng, x]
+        if tail is None:
+            eng.forward(x)
+        else:
+            eng.refine(x, window=10, tail=tail)
+    return lambda: _traced(run)
+
+
+def _encodec_dec_case():
+    def run(roots):
+        dec = EncodecDecoder(synth.random_encodec_decoder_state_dict(0), "cpu")
+        emb = torch.zeros(2, 128, 9)
+        roots += [dec, emb]
+        dec.decoder(emb)
+    return lambda: _traced(run)
+
+
+def _encodec_enc_case(fused):
+    """Two clips of different lengths: ragged padding and different buffer sizes."""
+    def run(roots):
+        enc = EncodecEncoder(synth.random_encodec_encoder_state_dict(0), "cpu", fused_stem=fused)
+        waves = [torch.zeros(2500), torch.zeros(3207)]
+        roots += [enc, waves]
+        enc.encode_list(waves)
+    return lambda: _traced(run)
+
+
 # the small configs of test_clip_host.py (dp = 256 > d = 208 and kp = 640 > 588: both K paddings live) and test_dinov2_host.py
 CLIP_SMALL = dict(hidden_size=208, intermediate_size=832, num_hidden_layers=2, num_attention_heads=2, image_size=56, patch_size=14,
                   projection_dim=128, layer_norm_eps=1e-5, hidden_act="gelu", num_channels=3)
@@ -277,6 +313,13 @@ for _m in MODES:
     CASES[f"dit_small/{_m}/B2"] = _dit_case(SMALL, _m, 2, T=40, nc=5)
     CASES[f"v2r/{_m}"] = _v2r_case(_m)
     CASES[f"v2r/{_m}/chunk2"] = _v2r_case(_m, chunk=2)
+    CASES[f"r2m/{_m}"] = _r2m_case(_m)
+for _m in ("bf16x3", "fp32"):
+    for _t in ("pad", "own"):
+        CASES[f"r2m/{_m}/refine_{_t}"] = _r2m_case(_m, tail=_t)
+CASES["encodec/dec"] = _encodec_dec_case()
+CASES["encodec/enc/fused"] = _encodec_enc_case(True)
+CASES["encodec/enc/composed"] = _encodec_enc_case(False)
 
 
 # ---- tile hints -------------------------------------------------------------------------------------------------------------

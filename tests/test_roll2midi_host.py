@@ -1,6 +1,6 @@
 """CPU: the host side of the Roll2Midi generator (roll2midi.py): ABI agreement of its three entry points, the state-dict layout,
-the BatchNorm fold (eps = 0.8), the transposed-convolution weight transform, the offset tables of a channel-slice convolution,
-refine's window cutting, the refusal of the attention-gate variant and the CLI wiring.  No GPU is touched."""
+the BatchNorm fold (eps = 0.8), the transposed-convolution weight transform, refine's window cutting, the refusal of the
+attention-gate variant and the CLI wiring.  No GPU is touched.  The offset tables are conv2d.py's: test_conv2d_host.py."""
 import ctypes
 import os
 import re
@@ -90,7 +90,8 @@ def test_bn_fold_uses_eps_0_8(params):
 
 
 def test_transposed_conv_is_a_plain_conv_of_the_transformed_weight():
-    from v2a_amd.roll2midi import gemm_weight, transposed_conv_weight
+    from v2a_amd.conv2d import gemm_weight
+    from v2a_amd.roll2midi import transposed_conv_weight
     g = torch.Generator().manual_seed(0)
     x = torch.randn(2, 6, 5, 4, generator=g, dtype=torch.float64)
     w = torch.randn(6, 3, 3, 3, generator=g, dtype=torch.float64)              # ConvTranspose2d layout [ci][co][ky][kx]
@@ -105,36 +106,6 @@ def test_transposed_conv_is_a_plain_conv_of_the_transformed_weight():
     two = torch.cat([patch[..., :2].reshape(2, 5, 4, 18), patch[..., 2:].reshape(2, 5, 4, 36)], -1)
     assert torch.allclose((two @ gemm_weight(wc, (2, 4)).t()).permute(0, 3, 1, 2), ref, atol=1e-12)
     assert gemm_weight(wc, None, 8).shape == (8, 54) and not bool(gemm_weight(wc, None, 8)[3:].any())
-
-
-def test_slice_tables_stay_inside_the_map_and_are_a_convolution():
-    from v2a_amd.roll2midi import slice_conv_tables
-    n, H, W, sp, so, ci, dp = 2, 5, 3, 192, 64, 128, 384
-    a_row, a_k, o_row = slice_conv_tables(n, H, W, sp, so, ci, dp)
-    Hp, Wp = H + 2, W + 2
-    assert a_row.dtype == a_k.dtype == o_row.dtype == torch.int32
-    assert a_row.shape == o_row.shape == (n * H * W,) and a_k.shape == (9 * ci // 64,)
-    assert int(a_row.min()) >= 0 and so + int(a_row.max()) + int(a_k.max()) + 64 <= n * Hp * Wp * sp
-    assert int(o_row.max()) + dp <= n * Hp * Wp * dp
-    assert all(int(v) % 8 == 0 for t in (a_row, a_k, o_row) for v in t)
-    # gathering through the tables is the convolution's patch matrix of the slice
-    g = torch.Generator().manual_seed(1)
-    m = torch.zeros(n, Hp, Wp, sp, dtype=torch.float64)
-    m[:, 1:-1, 1:-1] = torch.randn(n, H, W, sp, generator=g, dtype=torch.float64)
-    flat = m.view(-1)[so:]
-    idx = a_row[:, None, None].long() + a_k[None, :, None].long() + torch.arange(64)[None, None, :]
-    patch = flat[idx].reshape(n * H * W, 9 * ci)
-    w = torch.randn(4, ci, 3, 3, generator=g, dtype=torch.float64)
-    ref = F.conv2d(m[:, 1:-1, 1:-1, so:so + ci].permute(0, 3, 1, 2), w, padding=1).permute(0, 2, 3, 1).reshape(-1, 4)
-    assert torch.allclose(patch @ w.permute(0, 2, 3, 1).reshape(4, -1).t(), ref, atol=1e-10)
-    # output rows are the interior pixels of the destination map
-    dst = torch.zeros(n, Hp, Wp, dp)
-    dst.view(-1)[o_row.long()] = 1
-    assert int(dst.sum()) == n * H * W and float(dst[:, 1:-1, 1:-1, 0].sum()) == n * H * W
-    with pytest.raises(AssertionError):
-        slice_conv_tables(n, H, W, sp, 128, ci, dp)                 # the slice would leave the map's channels
-    with pytest.raises(AssertionError):
-        slice_conv_tables(n, H, W, sp, so, ci, dp, border=0)        # the border must cover the padding
 
 
 class _FakeRun:

@@ -19,7 +19,8 @@ Conv1d(k = 2r, stride r)] stages for r = 2, 4, 5, 8, the LSTM, ELU, Conv1d(512->
 whose A rows overlap with lda = r*C (K = k*C, M = ceil(T/r)) over a buffer that `v2a_elu_pad_lr` padded on both sides: the library
 reflects k - r samples in front and, where the length is not a multiple of r, up to r - 1 behind (`encoder_padding_plan`).  The
 wide, thin end -- stem + the C = 32 block over 240 000 time steps -- is one fused VALU kernel (`v2a_encodec_stage0`);
-`fused_stem=False` keeps the generic composition of it reachable for A/B runs.
+`fused_stem=False` keeps the generic composition of it reachable for A/B runs.  What the two engines share -- buffers, the LSTM and the
+convolution, the decoder's being the encoder's at stride 1 -- is `_SEANet`; each calls its own pad kernel.
 
 `EncodecQuantizer` is the third part of `EncodecModel`, the residual vector quantizer between the two (`EncodecModel.encode` / `.decode`):
 `v2a_encodec_rvq_encode` searches every stage's codebook in one launch (exact-fp32 MFMA scores, the residual in registers) and
@@ -80,18 +81,84 @@ def _resolve_weight(sd, p):
     raise KeyError(f"Encodec: no weight for {p}.conv (looked for .weight, parametrizations.weight.original0/1, weight_g/v)")
 
 
-class EncodecDecoder:
+def conv_padding(length: int, k: int, stride: int = 1) -> tuple[int, int, int]:
+    """(pad_left, pad_right, out_len) of a causal `EncodecConv1d(k, stride)` on `length` samples: k - stride reflected samples in
+    front, and behind as many as make the last window full (`_get_extra_padding_for_conv1d`, in integers)."""
+    pad_left = k - stride
+    n_frames = -((length - k + pad_left) // -stride)              # ceil((length - k + pad_total) / stride + 1) - 1
+    pad_right = n_frames * stride + k - pad_left - length
+    return pad_left, pad_right, (length + pad_left + pad_right - k) // stride + 1
+
+
+class _SEANet:
+    """What the decoder and the encoder share: named fp32 buffers, the 2-layer LSTM (weight packing, launch, timeout check) and the
+    causal convolution as one GEMM over overlapping rows.  The two differ in the kernel that pads: `_pad`."""
+
+    def _load(self, state_dict, device, part):
+        """Device, buffers and the state dict on the host, `part.` (decoder / encoder of an `EncodecModel`) stripped."""
+        L.lib()                                                   # fail loudly without the HIP library
+        self.dev = torch.device(device)
+        self._bufs: dict = {}
+        sd = {k: v.detach().cpu() for k, v in state_dict.items()}
+        if any(k.startswith(f"{part}.layers.") for k in sd):
+            sd = {k[len(part) + 1:]: v for k, v in sd.items() if k.startswith(f"{part}.")}
+        return sd
+
+    def _f32(self, t):
+        return t.float().contiguous().to(self.dev)
+
+    def _load_lstm(self, sd, p, H):
+        self.H = H
+        self.lstm = []
+        for l in range(2):
+            self.lstm.append(dict(wih=self._f32(sd[f"{p}.lstm.weight_ih_l{l}"]), whh=self._f32(sd[f"{p}.lstm.weight_hh_l{l}"]),
+                                  b=self._f32(sd[f"{p}.lstm.bias_ih_l{l}"].float() + sd[f"{p}.lstm.bias_hh_l{l}"].float())))
+        self._ws = torch.zeros(8 * H + 2, dtype=torch.int32, device=self.dev)      # exchange tables of both LSTM layers + error flag
+
+    def _buf(self, name, rows, C):
+        key = (name, rows, C)
+        t = self._bufs.get(key)
+        if t is None:
+            t = self._bufs[key] = torch.empty(rows, C, device=self.dev, dtype=torch.float32)
+        return t
+
+    def _conv(self, cv, src, T, name, *, act, resid=None):
+        """Causal Conv1d(k, stride r) on time-major src (T, ci): ELU (optional) + reflect pads, then one GEMM over overlapping rows
+        (lda = r*ci) -> (`conv_padding`'s out_len, co).  The decoder's convolutions have stride 1: k - 1 rows in front, none behind."""
+        k, ci, co, r = cv["k"], cv["ci"], cv["co"], cv.get("r", 1)
+        pl, pr, To = conv_padding(T, k, r)
+        a = src
+        if act or pl or pr:
+            a = self._buf(name + ".in", T + pl + pr, ci)
+            self._pad(src, a, T, ci, pl, pr, act)
+        out = self._buf(name, To, co)
+        L.gemm([(a, r * ci, k * ci)], cv["w"], out, M=To, N=co, compute=L.F32, bias=cv["b"], ldo=co,
+               epilogue=L.EPI_RESID if resid is not None else L.EPI_STORE, resid=resid, ldr=co)
+        return out
+
+    def _lstm2(self, x, T):
+        """2-layer LSTM + skip on x (T, H): one GEMM for layer 0's input projection, then both recurrences in one persistent kernel."""
+        H = self.H
+        l0, l1 = self.lstm
+        gx = self._buf("gx0", T, 4 * H)
+        L.gemm([(x, H, H)], l0["wih"], gx, M=T, N=4 * H, compute=L.F32, bias=l0["b"], ldo=4 * H)
+        y = self._buf("lstm_out", T, H)
+        L.lstm2(gx, l0["whh"], l1["wih"], l1["b"], l1["whh"], y, self._ws, T=T, H=H, resid=x)
+        return y
+
+    def _check_lstm(self):
+        if int(self._ws[8 * self.H].item()):                                       # one host sync per clip
+            raise L.V2AError("v2a_lstm2: a workgroup timed out at the step barrier (GPU oversubscribed?); result discarded")
+
+
+class EncodecDecoder(_SEANet):
     """HIP mirror of `EncodecWrapper.decode` / `EncodecModel.decoder`.
 
     state_dict: an `EncodecModel` state dict (keys `decoder.layers...`) or the decoder's own (`layers...`)."""
 
     def __init__(self, state_dict, device="cuda:0"):
-        L.lib()                                                   # fail loudly without the HIP library
-        self.dev = dev = torch.device(device)
-        sd = {k: v.detach().cpu() for k, v in state_dict.items()}
-        if any(k.startswith("decoder.layers.") for k in sd):
-            sd = {k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}
-        f32 = lambda t: t.float().contiguous().to(dev)
+        sd = self._load(state_dict, device, "decoder")
+        f32 = self._f32
 
         def conv(p):
             w = _resolve_weight(sd, p)                            # (co, ci, k)
@@ -108,11 +175,7 @@ class EncodecDecoder:
             return dict(w=f32(wp), b=f32(sd[f"{p}.conv.bias"].float().repeat(r)), co=co, ci=ci, r=r)
 
         self.c0 = conv("layers.0")
-        self.H = self.c0["co"]
-        self.lstm = []
-        for l in range(2):
-            self.lstm.append(dict(wih=f32(sd[f"layers.1.lstm.weight_ih_l{l}"]), whh=f32(sd[f"layers.1.lstm.weight_hh_l{l}"]),
-                                  b=f32(sd[f"layers.1.lstm.bias_ih_l{l}"].float() + sd[f"layers.1.lstm.bias_hh_l{l}"].float())))
+        self._load_lstm(sd, "layers.1", self.c0["co"])
         self.stages = []
         idx = 3
         for r in RATIOS:
@@ -121,46 +184,20 @@ class EncodecDecoder:
             assert self.stages[-1]["up"]["r"] == r
             idx += 3
         self.cf = conv(f"layers.{idx}")
-        self.hop = 1
-        for r in RATIOS:
-            self.hop *= r
-        self._bufs: dict = {}
-        self._ws = torch.zeros(8 * self.H + 2, dtype=torch.int32, device=dev)      # exchange tables of both LSTM layers + error flag
+        self.hop = math.prod(RATIOS)
 
-    def _buf(self, name, rows, C):
-        key = (name, rows, C)
-        t = self._bufs.get(key)
-        if t is None:
-            t = self._bufs[key] = torch.empty(rows, C, device=self.dev, dtype=torch.float32)
-        return t
-
-    def _conv(self, cv, src, T, name, *, act, resid=None):
-        """Causal Conv1d on time-major src (T, ci): ELU (optional) + reflect pad, then one GEMM over overlapping rows."""
-        k, ci, co = cv["k"], cv["ci"], cv["co"]
-        a = src
-        if act or k > 1:
-            a = self._buf(name + ".in", T + k - 1, ci)
-            L.elu_pad(src, a, T=T, C_=ci, pad=k - 1, reflect=True, act=act)
-        out = self._buf(name, T, co)
-        L.gemm([(a, ci, k * ci)], cv["w"], out, M=T, N=co, compute=L.F32, bias=cv["b"], ldo=co,
-               epilogue=L.EPI_RESID if resid is not None else L.EPI_STORE, resid=resid, ldr=co)
-        return out
+    def _pad(self, src, a, T, C, pl, pr, act):
+        assert pr == 0                                             # stride 1: k - 1 reflected rows in front, none behind
+        L.elu_pad(src, a, T=T, C_=C, pad=pl, reflect=True, act=act)
 
     def _decode_one(self, emb, taps=None):
         """emb (128, T) on the device -> waveform (T * 320,)."""
         T = emb.shape[1]
-        H = self.H
         x0 = emb.t().contiguous()                                                  # time-major (T, 128)
-        h0 = self._conv(self.c0, x0, T, "c0", act=False)
-        # 2-layer LSTM + skip: one GEMM for layer 0's input projection, then both recurrences in one persistent kernel
-        l0, l1 = self.lstm
-        gx = self._buf("gx0", T, 4 * H)
-        L.gemm([(h0, H, H)], l0["wih"], gx, M=T, N=4 * H, compute=L.F32, bias=l0["b"], ldo=4 * H)
-        x = self._buf("lstm_out", T, H)
-        L.lstm2(gx, l0["whh"], l1["wih"], l1["b"], l1["whh"], x, self._ws, T=T, H=H, resid=h0)
+        x = self._lstm2(self._conv(self.c0, x0, T, "c0", act=False), T)
         if taps is not None:
             taps["lstm"] = x.t().clone()
-        Lc, C = T, H
+        Lc, C = T, self.H
         for si, st in enumerate(self.stages):
             up = st["up"]
             r, co = up["r"], up["co"]
@@ -188,8 +225,7 @@ class EncodecDecoder:
         out = torch.empty(emb.shape[0], 1, emb.shape[2] * self.hop, device=self.dev, dtype=torch.float32)
         for i in range(emb.shape[0]):
             out[i, 0].copy_(self._decode_one(emb[i], taps if i == 0 else None))
-            if int(self._ws[8 * self.H].item()):                                   # one host sync per clip
-                raise L.V2AError("v2a_lstm2: a workgroup timed out at the step barrier (GPU oversubscribed?); result discarded")
+            self._check_lstm()
         return out
 
     def decode(self, emb):
@@ -229,15 +265,6 @@ def expected_encoder_state_dict_shapes() -> dict[str, tuple]:
     return s
 
 
-def conv_padding(length: int, k: int, stride: int = 1) -> tuple[int, int, int]:
-    """(pad_left, pad_right, out_len) of a causal `EncodecConv1d(k, stride)` on `length` samples: k - stride reflected samples in
-    front, and behind as many as make the last window full (`_get_extra_padding_for_conv1d`, in integers)."""
-    pad_left = k - stride
-    n_frames = -((length - k + pad_left) // -stride)              # ceil((length - k + pad_total) / stride + 1) - 1
-    pad_right = n_frames * stride + k - pad_left - length
-    return pad_left, pad_right, (length + pad_left + pad_right - k) // stride + 1
-
-
 def encoder_padding_plan(n: int) -> list[tuple[str, int, int, int]]:
     """(conv prefix, pad_left, pad_right, out_len) of every convolution of the encoder, in execution order, for n samples: `conv_padding`,
     which the engine sizes every buffer and launch with, walked over the stack."""
@@ -271,7 +298,7 @@ def encoder_frames(n: int) -> int:
     return T
 
 
-class EncodecEncoder:
+class EncodecEncoder(_SEANet):
     """HIP mirror of `EncodecWrapper.forward` / `EncodecModel.encoder` (no quantizer).
 
     state_dict: an `EncodecModel` state dict (keys `encoder.layers...`) or the encoder's own (`layers...`).
@@ -279,13 +306,9 @@ class EncodecEncoder:
     like the later stages (the stem as a GEMM over a zero-padded K = 16 patch buffer) -- kept for A/B timing and value comparison."""
 
     def __init__(self, state_dict, device="cuda:0", fused_stem=True):
-        L.lib()                                                   # fail loudly without the HIP library
-        self.dev = dev = torch.device(device)
+        sd = self._load(state_dict, device, "encoder")
         self.fused_stem = bool(fused_stem)
-        sd = {k: v.detach().cpu() for k, v in state_dict.items()}
-        if any(k.startswith("encoder.layers.") for k in sd):
-            sd = {k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")}
-        f32 = lambda t: t.float().contiguous().to(dev)
+        f32 = self._f32
 
         def conv(p, stride=1):
             w = _resolve_weight(sd, p)                            # (co, ci, k)
@@ -304,12 +327,8 @@ class EncodecEncoder:
                                     down=conv(f"layers.{idx + 2}", r)))
             assert self.stages[-1]["down"]["k"] == 2 * r
             idx += 3
-        self.lstm = []
-        for l in range(2):
-            self.lstm.append(dict(wih=f32(sd[f"layers.{idx}.lstm.weight_ih_l{l}"]), whh=f32(sd[f"layers.{idx}.lstm.weight_hh_l{l}"]),
-                                  b=f32(sd[f"layers.{idx}.lstm.bias_ih_l{l}"].float() + sd[f"layers.{idx}.lstm.bias_hh_l{l}"].float())))
         self.cf = conv(f"layers.{idx + 2}")
-        self.H = self.cf["ci"]
+        self._load_lstm(sd, f"layers.{idx}", self.cf["ci"])
         self.hop = math.prod(RATIOS)
         s0 = self.stages[0]
         # parameter block of v2a_encodec_stage0 (include/v2a_cfm.h)
@@ -317,28 +336,14 @@ class EncodecEncoder:
                                      s0["sc"]["b_cpu"] + s0["b3"]["b_cpu"], s0["b1"]["w3"].permute(0, 2, 1).reshape(-1), s0["b1"]["b_cpu"],
                                      s0["b3"]["w3"].reshape(-1)]))
         assert self.stage0.numel() == L.ENCODEC_STAGE0_PARAMS
-        self._bufs: dict = {}
-        self._ws = torch.zeros(8 * self.H + 2, dtype=torch.int32, device=dev)      # exchange tables of both LSTM layers + error flag
 
-    _buf = EncodecDecoder._buf
-
-    def _conv(self, cv, src, T, name, *, act, resid=None):
-        """Causal Conv1d(k, stride r) on time-major src (T, ci): ELU (optional) + reflect pads, then one GEMM over overlapping rows."""
-        k, ci, co, r = cv["k"], cv["ci"], cv["co"], cv["r"]
-        pl, pr, To = conv_padding(T, k, r)
-        a = src
-        if act or pl or pr:
-            a = self._buf(name + ".in", T + pl + pr, ci)
-            L.elu_pad_lr(src, a, T=T, C_=ci, pad_left=pl, pad_right=pr, act=act)
-        out = self._buf(name, To, co)
-        L.gemm([(a, r * ci, k * ci)], cv["w"], out, M=To, N=co, compute=L.F32, bias=cv["b"], ldo=co,
-               epilogue=L.EPI_RESID if resid is not None else L.EPI_STORE, resid=resid, ldr=co)
-        return out, To
+    def _pad(self, src, a, T, C, pl, pr, act):
+        L.elu_pad_lr(src, a, T=T, C_=C, pad_left=pl, pad_right=pr, act=act)
 
     def _resblock(self, st, x, T, name):
-        h1, _ = self._conv(st["b1"], x, T, name + ".b1", act=True)
-        h2, _ = self._conv(st["b3"], h1, T, name + ".b3", act=True)
-        return self._conv(st["sc"], x, T, name + ".out", act=False, resid=h2)[0]
+        h1 = self._conv(st["b1"], x, T, name + ".b1", act=True)
+        h2 = self._conv(st["b3"], h1, T, name + ".b3", act=True)
+        return self._conv(st["sc"], x, T, name + ".out", act=False, resid=h2)
 
     def _stage0(self, wave, n):
         """Layers 0 and 1: wave (n,) -> (n, 32) time-major."""
@@ -364,18 +369,14 @@ class EncodecEncoder:
         for si, st in enumerate(self.stages):
             if si:
                 x = self._resblock(st, x, T, f"s{si}")
-            x, T = self._conv(st["down"], x, T, f"s{si}.down", act=True)
+            x = self._conv(st["down"], x, T, f"s{si}.down", act=True)
+            T = x.shape[0]
             if taps is not None:
                 taps[f"layer{3 * si + 3}"] = x.t().clone()
-        H = self.H
-        l0, l1 = self.lstm
-        gx = self._buf("gx0", T, 4 * H)
-        L.gemm([(x, H, H)], l0["wih"], gx, M=T, N=4 * H, compute=L.F32, bias=l0["b"], ldo=4 * H)
-        y = self._buf("lstm_out", T, H)
-        L.lstm2(gx, l0["whh"], l1["wih"], l1["b"], l1["whh"], y, self._ws, T=T, H=H, resid=x)
+        y = self._lstm2(x, T)
         if taps is not None:
             taps["layer13"] = y.t().clone()
-        z, _ = self._conv(self.cf, y, T, "final", act=True)                        # (T, 128)
+        z = self._conv(self.cf, y, T, "final", act=True)                           # (T, 128)
         return z.t().contiguous()
 
     @torch.no_grad()
@@ -388,8 +389,7 @@ class EncodecEncoder:
             z = self._encode_one(w.to(self.dev, torch.float32).contiguous(), taps if i == 0 else None)
             assert z.shape == (HIDDEN, T), (tuple(z.shape), T)
             out.append(z)
-            if int(self._ws[8 * self.H].item()):                                   # one host sync per clip
-                raise L.V2AError("v2a_lstm2: a workgroup timed out at the step barrier (GPU oversubscribed?); result discarded")
+            self._check_lstm()
         return out
 
     def encoder(self, wave, taps=None):

@@ -15,13 +15,16 @@ Design (not a translation of the reference's NCHW module tree):
   * three row kernels complete it (csrc/roll2midi.hip): `v2a_roll2midi_stem` (down1: K = 9 fills no K tile), `v2a_leaky_shadow`
     (LeakyReLU(0.2), which the GEMM epilogue lacks, + the bf16 / hi | lo copy the next GEMM reads) and `v2a_roll2midi_head`
     (conv1d 80 -> 1 + sigmoid + threshold).
-There is no CPU fallback: without libv2a_cfm.so every call raises.
+The BatchNorm fold, the weight packing, the bordered maps with their channel slices and the offset tables are conv2d.py's, shared with
+video2roll.py.  There is no CPU fallback: without libv2a_cfm.so every call raises.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
+from . import conv2d
+from .conv2d import ConvMemory, gemm_weight, split_args
 
 KEYS = 51
 BN_EPS = 0.8                # nn.BatchNorm2d(out_size, 0.8): the second positional argument is eps (r2m:12,28)
@@ -56,13 +59,7 @@ def check_state_dict(sd: dict) -> None:
     if any(k.startswith("att") for k in sd):
         raise NotImplementedError("Roll2MidiEngine: the state dict holds attention gates (att1.* ...): that is Roll2MidiNet_enhance.py, "
                                   "which has no HIP path; only the plain Generator of Roll2MidiNet.py is built")
-    want = expected_state_dict_shapes()
-    missing = [k for k in want if k not in sd and not k.endswith("num_batches_tracked")]
-    if missing:
-        raise KeyError(f"Roll2MidiEngine: state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
-    bad = [k for k, shp in want.items() if k in sd and not k.endswith("num_batches_tracked") and tuple(sd[k].shape) != tuple(shp)]
-    if bad:
-        raise ValueError(f"Roll2MidiEngine: shape mismatch for {bad[:4]}")
+    conv2d.check_state_dict(sd, expected_state_dict_shapes(), "Roll2MidiEngine")
 
 
 def transposed_conv_weight(w: torch.Tensor) -> torch.Tensor:
@@ -79,71 +76,12 @@ def folded_conv(sd: dict, name: str) -> tuple[torch.Tensor, torch.Tensor | None]
     bn = f"{name}.model.1"
     if f"{bn}.weight" not in sd:
         return w, None
-    s = sd[f"{bn}.weight"].float() / torch.sqrt(sd[f"{bn}.running_var"].float() + BN_EPS)
-    return w * s[:, None, None, None], sd[f"{bn}.bias"].float() - sd[f"{bn}.running_mean"].float() * s
-
-
-def gemm_weight(w: torch.Tensor, segments: tuple[int, ...] | None = None, pad_to: int = 0) -> torch.Tensor:
-    """[co][ci][3][3] -> GEMM rows [co][K], K in (ky, kx, c) order (NHWC sources).  segments (fp32 mode): the input channels are the
-    concatenation of maps with these widths, each its own patch matrix: K = [(ky, kx, c of map 0) | (ky, kx, c of map 1) ...]."""
-    co = w.shape[0]
-    parts, c0 = [], 0
-    for c in segments or (w.shape[1],):
-        parts.append(w[:, c0:c0 + c].permute(0, 2, 3, 1).reshape(co, -1))
-        c0 += c
-    assert c0 == w.shape[1]
-    wk = torch.cat(parts, 1)
-    if pad_to > co:
-        wk = torch.cat([wk, torch.zeros(pad_to - co, wk.shape[1])], 0)
-    return wk.contiguous()
-
-
-def slice_conv_tables(n, H, W, src_pitch, src_off, ci, dst_pitch, border=1, device="cpu"):
-    """Offset tables (elements, int32) of a 3x3 / pad 1 convolution for v2a_gemm's implicit-GEMM mode, reading the ci channels at
-    channel offset src_off of a bordered NHWC map of src_pitch channels and writing into a bordered map of dst_pitch channels.
-    The A pointer is map + src_off and the out pointer map + the destination slice's offset, so the tables hold pixel offsets only:
-    a_row[m] = the top-left tap of output pixel m, a_k[kt] = (ky*Wp + kx)*src_pitch + c0, o_row[m] = the interior pixel m."""
-    assert border >= 1, "the source map's zero border must cover the convolution's padding"
-    assert ci % 64 == 0 and src_off % 8 == 0 and src_pitch % 8 == 0 and dst_pitch % 8 == 0, "whole 64-element K tiles, 16-byte aligned slices"
-    assert src_off + ci <= src_pitch
-    Hp, Wp = H + 2 * border, W + 2 * border
-    ni = torch.arange(n, device=device, dtype=torch.int64)[:, None, None]
-    yo = torch.arange(H, device=device, dtype=torch.int64)[None, :, None]
-    xo = torch.arange(W, device=device, dtype=torch.int64)[None, None, :]
-    a_row = ((ni * Hp + yo + border - 1) * Wp + xo + border - 1) * src_pitch
-    k0 = torch.arange(0, 9 * ci, 64, device=device, dtype=torch.int64)
-    tap, c0 = k0 // ci, k0 % ci
-    a_k = ((tap // 3) * Wp + tap % 3) * src_pitch + c0
-    o_row = ((ni * Hp + yo + border) * Wp + xo + border) * dst_pitch
-    # every 64-element read of the hi plane stays inside the map (the lo plane starts one whole map further)
-    assert src_off + int(a_row.max()) + int(a_k.max()) + 64 <= n * Hp * Wp * src_pitch < 2 ** 31
-    assert int(o_row.max()) + dst_pitch <= n * Hp * Wp * dst_pitch < 2 ** 31
-    i32 = lambda t: t.reshape(-1).to(torch.int32).contiguous()
-    return i32(a_row), i32(a_k), i32(o_row)
+    return conv2d.fold_batchnorm(w, None, *(sd[f"{bn}.{k}"].float() for k in ("weight", "bias", "running_mean", "running_var")), BN_EPS)
 
 
 def window_spans(t: int, window: int) -> list[tuple[int, int]]:
     """[start, stop) of the windows `refine` cuts t frames into: whole windows, then the shorter rest."""
     return [(s, min(s + window, t)) for s in range(0, t, window)]
-
-
-class _Slice:
-    """C channels at channel offset `off` of an NHWC fp32 map (n, H + 2b, W + 2b, pitch) and of its shadow."""
-    __slots__ = ("f32", "sh", "off", "C", "pitch", "plane")
-
-    def __init__(self, f32, sh, off, C):
-        self.f32, self.sh, self.off, self.C = f32, sh, off, C
-        self.pitch, self.plane = f32.shape[-1], f32.numel()
-
-    def base(self):
-        return self.f32.view(-1)[self.off:]
-
-    def shadow(self):
-        return None if self.sh is None else self.sh.view(-1)[self.off:]
-
-    def nchw(self, border, C=None):
-        v = self.f32 if border == 0 else self.f32[:, border:-border, border:-border]
-        return v[..., self.off:self.off + (C or self.C)].permute(0, 3, 1, 2)
 
 
 class Roll2MidiEngine:
@@ -181,8 +119,7 @@ class Roll2MidiEngine:
         self.stem_wt = folded_conv(sd, "down1")[0].reshape(64, 9).t().contiguous().to(dev)        # [tap][co]
         self.head_w = sd["conv1d.weight"].float().reshape(80).contiguous().to(dev)
         self.head_b = float(sd["conv1d.bias"].float()[0])
-        self._bufs: dict = {}
-        self._tabs: dict = {}
+        self.mem = ConvMemory(dev, self.split)              # activation maps, offset tables, patch-matrix scratch
 
     @staticmethod
     def _layers():
@@ -195,38 +132,22 @@ class Roll2MidiEngine:
 
     # ---- buffers ------------------------------------------------------------------------------------
     def _maps(self, n, H, W):
-        """The slices d1..d6 (down outputs) and p1..p5 (up outputs) for n windows of H x W, cached by geometry: a bordered map
-        relies on its border staying zero."""
-        key = ("maps", n, H, W)
-        m = self._bufs.get(key)
-        if m is not None:
-            return m
-        dev, b = self.dev, 1 if self.implicit else 0
-        f = lambda C: torch.zeros(n, H + 2 * b, W + 2 * b, C, device=dev, dtype=torch.float32)
-        s = lambda C: torch.zeros(((2,) if self.split else ()) + (n, H + 2 * b, W + 2 * b, C), device=dev, dtype=torch.bfloat16) if self.implicit else None
+        """The slices d1..d6 (down outputs) and p1..p5 (up outputs) for n windows of H x W."""
+        b = 1 if self.implicit else 0
+        new = lambda name, C: self.mem.map(name, n, H, W, C, b, self.implicit)
         m = {}
         if self.implicit:
             # concatenated maps [p_k | d_(6-k)]: r2m:38 without the copy
             for k, (cu, cd) in enumerate(((512, 1024), (256, 512), (128, 256), (64, 128), (UP5_PAD, 64)), 1):
-                f32, sh = f(cu + cd), s(cu + cd)
-                m[f"p{k}"] = _Slice(f32, sh, 0, cu)
-                m[f"d{6 - k}"] = _Slice(f32, sh, cu, cd)
-                m[f"u{k}"] = _Slice(f32, sh, 0, cu + cd)
-            m["d6"] = _Slice(f(1024), s(1024), 0, 1024)
+                m[f"u{k}"] = u = new(f"u{k}", cu + cd)
+                m[f"p{k}"], m[f"d{6 - k}"] = u.slice(0, cu), u.slice(cu, cd)
+            m["d6"] = new("d6", 1024)
         else:
             for k, (_, co) in enumerate(_DOWN, 1):
-                m[f"d{k}"] = _Slice(f(co), None, 0, co)
+                m[f"d{k}"] = new(f"d{k}", co)
             for k, (_, co) in enumerate(_UP, 1):
-                m[f"p{k}"] = _Slice(f(max(co, UP5_PAD)), None, 0, max(co, UP5_PAD))
-        self._bufs[key] = m
+                m[f"p{k}"] = new(f"p{k}", max(co, UP5_PAD))
         return m
-
-    def _col(self, which, rows, K):
-        need = rows * K
-        buf = self._bufs.get(("col", which))
-        if buf is None or buf.numel() < need:
-            buf = self._bufs[("col", which)] = torch.empty(need, device=self.dev, dtype=torch.float32)
-        return buf[:need].view(rows, K)
 
     # ---- one convolution ----------------------------------------------------------------------------
     def _conv(self, name, srcs, dst, n, H, W, *, relu):
@@ -235,41 +156,31 @@ class Roll2MidiEngine:
         assert N == dst.C
         if self.implicit:
             (src,) = srcs
-            key = (n, H, W, src.pitch, src.off, src.C, dst.pitch)
-            t = self._tabs.get(key)
-            if t is None:
-                t = self._tabs[key] = slice_conv_tables(n, H, W, src.pitch, src.off, src.C, dst.pitch, 1, self.dev)
-            K = 9 * src.C
-            sp = {}
-            shadow = dst.shadow() if relu else None           # down blocks: v2a_leaky_shadow writes the shadow after the activation
-            if self.split:
-                sp["a_split"] = True
-                if shadow is not None:
-                    sp.update(out_bf16_split=True, out_bf16_lo_offset=dst.plane)
-            L.gemm([L.Operand(src.shadow(), K, K, src.plane if self.split else 0)], w, dst.base(), M=rows, N=N, compute=self.code,
-                   bias=bias, relu=relu, ldo=dst.pitch, out_bf16=shadow, ld_out_bf16=dst.pitch,
-                   a_row_offset=t[0], a_ktile_offset=t[1], out_row_offset=t[2], **sp)
+            t = self.mem.tables(src, dst, 3, 3, 1, 1)
+            shadowed = dst if relu else None                  # down blocks: v2a_leaky_shadow writes the shadow after the activation
+            L.gemm([src.operand(9 * src.C)], w, dst.base(), M=rows, N=N, compute=self.code,
+                   bias=bias, relu=relu, ldo=dst.pitch, out_bf16=dst.shadow() if relu else None, ld_out_bf16=dst.pitch,
+                   a_row_offset=t[0], a_ktile_offset=t[1], out_row_offset=t[2], **split_args(self.split, shadowed))
             return
         segs = []
         for i, src in enumerate(srcs):
             K = 9 * src.C
-            col = self._col(i, rows, K)
+            col = self.mem.col(rows, K, i)
             L.im2col(src.f32, col, B=n, H=H, W=W, C_=src.C, kh=3, kw=3, stride=1, pad=1, Ho=H, Wo=W, ldo=K)
             segs.append((col, K, K))
         L.gemm(segs, w, dst.f32, M=rows, N=N, compute=self.code, bias=bias, relu=relu, ldo=dst.pitch)
 
     def _leaky(self, sl, n, H, W):
-        L.leaky_shadow(sl.base(), sl.shadow(), n=n, H=H, W=W, C_=sl.C, shadow_mode=self.mode, lo_offset=sl.plane if self.split else 0,
-                       pitch=sl.pitch, border=1 if self.implicit else 0)
+        L.leaky_shadow(sl.base(), sl.shadow(), n=n, H=H, W=W, C_=sl.C, shadow_mode=self.mode, lo_offset=sl.lo,
+                       pitch=sl.pitch, border=sl.border)
 
     def _pass(self, x, logits, probs, midi, threshold, taps=None):
         """x (n, H, W) fp32 on the device -> the dense (n, H, W) outputs that are not None."""
         n, H, W = x.shape
         m = self._maps(n, H, W)
-        b = 1 if self.implicit else 0
         d1 = m["d1"]
         L.roll2midi_stem(x, self.stem_wt, d1.base(), d1.shadow(), n=n, H=H, W=W, co=64, shadow_mode=self.mode,
-                         lo_offset=d1.plane if self.split else 0, pitch=d1.pitch, border=b)
+                         lo_offset=d1.lo, pitch=d1.pitch, border=d1.border)
         for k in range(2, 7):                                        # r2m:64-72
             self._conv(f"down{k}", [m[f"d{k - 1}"]], m[f"d{k}"], n, H, W, relu=False)
             self._leaky(m[f"d{k}"], n, H, W)
@@ -279,13 +190,13 @@ class Roll2MidiEngine:
             self._conv(f"up{k}", srcs, m[f"p{k}"], n, H, W, relu=True)
         p5 = m["p5"]
         L.roll2midi_head(p5.base(), d1.base(), self.head_w, u_pitch=p5.pitch, nu=16, d_pitch=d1.pitch, nd=64, bias=self.head_b,
-                         threshold=threshold, n=n, H=H, W=W, border=b, logits=logits, probs=probs, midi=midi)
+                         threshold=threshold, n=n, H=H, W=W, border=d1.border, logits=logits, probs=probs, midi=midi)
         if taps is not None:
             for k in range(1, 7):
-                taps.setdefault(f"d{k}", []).append(m[f"d{k}"].nchw(b).clone())
+                taps.setdefault(f"d{k}", []).append(m[f"d{k}"].nchw().clone())
             for k in range(1, 6):
-                up = m[f"p{k}"].nchw(b, _UP[k - 1][1])
-                taps.setdefault(f"u{k}", []).append(torch.cat([up, m[f"d{6 - k}"].nchw(b)], 1))
+                up = m[f"p{k}"].nchw(_UP[k - 1][1])
+                taps.setdefault(f"u{k}", []).append(torch.cat([up, m[f"d{6 - k}"].nchw()], 1))
 
     def _run(self, x, threshold, want_logits=False, want_midi=False, taps=None):
         """x (n, keys, w) -> (probs or logits (n, keys, w) fp32, midi (n, keys, w) uint8 or None), chunk windows per pass."""

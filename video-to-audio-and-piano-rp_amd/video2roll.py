@@ -5,9 +5,11 @@ Mirrors `E2TTS.encode_frames` (src/e2_tts_pytorch/e2_tts_crossatt3.py:1525-1553)
 100x900 grey frames -> 51 key probabilities per frame, repeated x3 in time and cropped / padded to the latent length.
 
 Design (not a translation of the reference's NCHW module tree):
-  * activations NHWC fp32; every convolution is `v2a_im2col` (patch matrix in the compute dtype, the 5-frame window
-    of the first layer gathered on the fly) + `v2a_gemm` -- the same MFMA GEMM the sampler uses -- with the eval-mode
-    BatchNorm folded into weight / bias at load time and ReLU / residual add in the GEMM epilogue;
+  * activations NHWC fp32; every convolution is one `v2a_gemm` -- the same MFMA GEMM the sampler uses -- with the eval-mode
+    BatchNorm folded into weight / bias at load time and ReLU / residual add in the GEMM epilogue: an implicit GEMM over
+    zero-bordered maps in the bf16 / bf16x3 modes, `v2a_im2col` patch matrices (the 5-frame window of the first layer gathered on
+    the fly) in fp32 mode.  The fold, the weight packing, the maps and the offset tables are conv2d.py's, shared with roll2midi.py;
+    the first layer's packed column patches and their tables are this engine's own;
   * FRB gates, spatial softmax, the last 1x1 conv, global pooling, fc and sigmoid are one fused kernel per window
     (`v2a_roll_head`; pooling commutes with the 1x1 conv, so only per-channel position sums are formed);
   * windows are processed in chunks so the patch matrix of the first layer (28 MB per window in bf16) stays bounded.
@@ -15,11 +17,11 @@ There is no CPU fallback: without libv2a_cfm.so every call raises.
 """
 from __future__ import annotations
 
-import math
-
 import torch
+import torch.nn.functional as F
 
 from . import _lib as L
+from .conv2d import ConvMemory, Map, check_state_dict, fold_batchnorm, gemm_weight, split_args
 
 NOTES = 51
 BN_EPS = 1e-5
@@ -79,17 +81,11 @@ class _Conv:
         co, ci, kh, kw = w.shape
         bias = sd[conv_bias].float() if conv_bias else None
         if bnkey is not None:
-            s = sd[f"{bnkey}.weight"].float() / torch.sqrt(sd[f"{bnkey}.running_var"].float() + BN_EPS)
-            shift = sd[f"{bnkey}.bias"].float() - sd[f"{bnkey}.running_mean"].float() * s
-            w = w * s[:, None, None, None]
-            bias = shift if bias is None else bias * s + shift
-        # K order: (c, ky, kx) for the windowed first layer (weight's own order), (ky, kx, c) for NHWC sources
-        wk = w.reshape(co, -1) if window else w.permute(0, 2, 3, 1).reshape(co, -1)
-        K = wk.shape[1]
+            w, bias = fold_batchnorm(w, bias, *(sd[f"{bnkey}.{k}"].float() for k in ("weight", "bias", "running_mean", "running_var")), BN_EPS)
+        # K order: (c, ky, kx) for the windowed first layer (weight's own order), (ky, kx, c) for NHWC sources; K padded to the granule
         kq = 64 if cd == torch.bfloat16 else 16
-        self.Kpad = (K + kq - 1) // kq * kq
-        wp = torch.zeros(co, self.Kpad)
-        wp[:, :K] = wk
+        wp = F.pad(w.reshape(co, -1), (0, -(ci * kh * kw) % kq)) if window else gemm_weight(w, k_granule=kq)
+        self.Kpad = wp.shape[1]
         self.w = (L.split_planes(wp) if split else wp.to(cd)).to(dev).contiguous()
         self.w_pack = None
         if window and cd == torch.bfloat16:
@@ -129,13 +125,7 @@ class Video2RollEngine:
         self.code = L.F32 if compute == "fp32" else L.BF16
         self.chunk = int(chunk) if chunk else (16 if compute == "fp32" else 256)
         sd = {k[len(prefix):]: v.detach().cpu() for k, v in sd.items() if k.startswith(prefix)}
-        want = expected_state_dict_shapes(sd["fc.weight"].shape[0] if "fc.weight" in sd else NOTES)
-        missing = [k for k in want if k not in sd and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError(f"Video2RollEngine: state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
-        bad = [k for k, shp in want.items() if k in sd and not k.endswith("num_batches_tracked") and tuple(sd[k].shape) != tuple(shp)]
-        if bad:
-            raise ValueError(f"Video2RollEngine: shape mismatch for {bad[:4]}")
+        check_state_dict(sd, expected_state_dict_shapes(sd["fc.weight"].shape[0] if "fc.weight" in sd else NOTES), "Video2RollEngine")
         self.notes = sd["fc.weight"].shape[0]
         dev, cd = self.dev, self.cd
         _Cv = lambda *a, **k: _Conv(*a, split=self.split, **k)
@@ -167,75 +157,12 @@ class Video2RollEngine:
         self.head_w["conv2_b"] = f32("conv2.bias")
         self.head_w["fc_wt"] = t32("fc.weight")
         self.head_w["fc_b"] = f32("fc.bias")
-        self._maps: dict = {}
-        self._tabs: dict = {}
-        self._col = None
+        self.mem = ConvMemory(dev, self.split)              # activation maps, offset tables, patch-matrix scratch
+        self._bufs: dict = {}                               # this engine's own: head buffers, packed column patches and their tables
         # bf16: implicit GEMM (the MFMA kernel gathers patch rows from zero-bordered NHWC bf16 maps through offset tables);
         # bf16x3: the same over hi | lo planes of the maps (split shadows) and of the weights, the first layer included;
         # fp32 parity mode: explicit patch matrix + the exact-fp32 GEMM, the windowed first layer through im2col.
         self.implicit = compute != "fp32"
-
-    # ---- activation maps --------------------------------------------------------------------------
-    class _Map:
-        """NHWC fp32 activation (n, H + 2b, W + 2b, C) with a zero border of b pixels, plus its bf16 copy when a
-        convolution reads it (the DMA GEMM moves raw bf16 bytes): `sh`, an operand record of rows of C.  bf16x3 mode: the copy
-        is a split shadow (2, n, H + 2b, W + 2b, C) -- plane 0 hi, plane 1 lo (sh.lo = one plane further), both zero-bordered."""
-        __slots__ = ("f32", "sh", "n", "H", "W", "C", "border")
-
-        def __init__(self, f32, sh, n, H, W, C, border):
-            self.f32, self.sh, self.n, self.H, self.W, self.C, self.border = f32, sh, n, H, W, C, border
-
-        @property
-        def b16(self):
-            return None if self.sh is None else self.sh.t
-
-        def interior(self):
-            b = self.border
-            return self.f32 if b == 0 else self.f32[:, b:-b, b:-b, :]
-
-    def _map(self, name, n, H, W, C, border=0, shadow=False):
-        """Cached by full geometry: a bordered map relies on its border staying zero, so two geometries never share memory
-        (nor does a split shadow share memory with a plain one)."""
-        split = shadow and self.split
-        key = (name, n, H, W, C, border, shadow, split)
-        m = self._maps.get(key)
-        if m is None:
-            shp = (n, H + 2 * border, W + 2 * border, C)
-            f32 = torch.zeros(shp, device=self.dev, dtype=torch.float32)
-            b16 = torch.zeros(((2,) if split else ()) + shp, device=self.dev, dtype=torch.bfloat16) if shadow else None
-            sh = None if b16 is None else L.Operand(b16, C, C, b16[0].numel() if split else 0)
-            m = self._maps[key] = self._Map(f32, sh, n, H, W, C, border)
-        return m
-
-    def _colbuf(self, rows, kpad):
-        n = rows * kpad
-        if self._col is None or self._col.numel() < n:
-            self._col = torch.empty(n, device=self.dev, dtype=self.cd)
-        return self._col[:n].view(rows, kpad)
-
-    def _tables(self, cv, src, Ho, Wo, out_border):
-        """Offset tables of one convolution geometry for v2a_gemm's implicit-GEMM mode (elements, int32)."""
-        key = (cv.kh, cv.kw, cv.stride, cv.pad, cv.ci, cv.co, src.n, src.H, src.W, src.border, out_border)
-        t = self._tabs.get(key)
-        if t is None:
-            b, C = src.border, cv.ci
-            assert b >= cv.pad, "the source map's zero border must cover the convolution's padding"
-            Hp, Wp = src.H + 2 * b, src.W + 2 * b
-            dev = self.dev
-            ni = torch.arange(src.n, device=dev, dtype=torch.int64)[:, None, None]
-            yo = torch.arange(Ho, device=dev, dtype=torch.int64)[None, :, None]
-            xo = torch.arange(Wo, device=dev, dtype=torch.int64)[None, None, :]
-            a_row = ((ni * Hp + yo * cv.stride - cv.pad + b) * Wp + xo * cv.stride - cv.pad + b) * C
-            k0 = torch.arange(0, cv.kh * cv.kw * C, 64, device=dev, dtype=torch.int64)
-            tap, c0 = k0 // C, k0 % C
-            a_k = ((tap // cv.kw) * Wp + tap % cv.kw) * C + c0
-            o_row = None
-            if out_border:
-                o_row = (((ni * (Ho + 2 * out_border) + yo + out_border) * (Wo + 2 * out_border) + xo + out_border) * cv.co)
-                o_row = o_row.reshape(-1).to(torch.int32).contiguous()
-            assert int(a_row.max()) + int(a_k.max()) + 64 <= src.n * Hp * Wp * C < 2 ** 31
-            t = self._tabs[key] = (a_row.reshape(-1).to(torch.int32).contiguous(), a_k.to(torch.int32).contiguous(), o_row)
-        return t
 
     # ---- one convolution (+bias, +residual, +ReLU in the GEMM epilogue) ---------------------------------
     def _conv(self, name, src, dst_name, *, relu=False, resid=None, border=None, shadow=None, window=None, dst=None):
@@ -251,20 +178,17 @@ class Video2RollEngine:
         if shadow is None:
             shadow = self.implicit
         if dst is None:
-            dst = self._map(dst_name, n, Ho, Wo, cv.co, border, shadow)
+            dst = self.mem.map(dst_name, n, Ho, Wo, cv.co, border, shadow)
         assert (dst.n, dst.H, dst.W, dst.C) == (n, Ho, Wo, cv.co)
         if resid is not None:
             assert (resid.n, resid.H, resid.W, resid.C, resid.border) == (dst.n, dst.H, dst.W, dst.C, dst.border)
         epi = L.EPI_RESID if resid is not None else L.EPI_STORE
         rs = None if resid is None else resid.f32
-        # bf16x3: the A operand's lo plane is a whole map (plane) after its hi plane; weight rows are [W_hi | W_lo]
-        sp = dict(a_split=True) if self.split else {}
-        if self.split and dst.sh is not None:
-            sp.update(out_bf16_split=True, out_bf16_lo_offset=dst.sh.lo)
+        sp = split_args(self.split, dst)
         if cv.window and patches is not None:
             # first layer over the packed column patches of this clip (v2a_frames_pack): windows [first, first + n) of the clip
             key = ("c1", T, first, n, H, W)
-            t = self._tabs.get(key)
+            t = self._bufs.get(key)
             if t is None:
                 Hp = H + 2 * cv.pad
                 dev = self.dev
@@ -275,21 +199,21 @@ class Video2RollEngine:
                 kt = torch.arange(cv.ci * cv.g, device=dev, dtype=torch.int64)
                 a_k = (kt // cv.g) * (Wo * Hp * 16) + (kt % cv.g) * 64
                 assert int(a_row.max()) + int(a_k.max()) + 64 <= (patches.lo or patches.t.numel()) < 2 ** 31      # within the hi plane
-                t = self._tabs[key] = (a_row.reshape(-1).to(torch.int32).contiguous(), a_k.to(torch.int32).contiguous())
+                t = self._bufs[key] = (a_row.reshape(-1).to(torch.int32).contiguous(), a_k.to(torch.int32).contiguous())
             L.gemm([patches], cv.w_pack, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
                    relu=relu, ldo=cv.co, ldr=cv.co, a_row_offset=t[0], a_ktile_offset=t[1], **sp)
             return dst
         if self.implicit and not cv.window:
-            a_row, a_k, o_row = self._tables(cv, src, Ho, Wo, dst.border)
+            a_row, a_k, o_row = self.mem.tables(src, dst, cv.kh, cv.kw, cv.stride, cv.pad)
             K = cv.kh * cv.kw * cv.ci
-            assert K == cv.Kpad, "NHWC convolutions have whole 64-element K tiles (C % 64 == 0)"
-            L.gemm([src.sh._replace(ld=K, k=K)], cv.w, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
-                   relu=relu, ldo=cv.co, ldr=cv.co, out_bf16=dst.b16, ld_out_bf16=cv.co,
+            assert K == cv.Kpad and src.C == cv.ci, "NHWC convolutions have whole 64-element K tiles (C % 64 == 0)"
+            L.gemm([src.operand(K)], cv.w, dst.f32, M=rows, N=cv.co, compute=self.code, epilogue=epi, bias=cv.bias, resid=rs,
+                   relu=relu, ldo=cv.co, ldr=cv.co, out_bf16=dst.sh, ld_out_bf16=cv.co,
                    a_row_offset=a_row, a_ktile_offset=a_k, out_row_offset=o_row, **sp)
             return dst
         # explicit patch matrix
         assert dst.border == 0 or cv.window is False
-        col = self._colbuf(rows, cv.Kpad)
+        col = self.mem.col(rows, cv.Kpad)
         if cv.window:
             L.im2col(frames, col, B=n, H=H, W=W, C_=5, kh=cv.kh, kw=cv.kw, stride=cv.stride, pad=cv.pad, Ho=Ho, Wo=Wo,
                      ldo=cv.Kpad, window_t=T, window_first=first)
@@ -304,13 +228,13 @@ class Video2RollEngine:
     def _pool(self, src, dst_name, k, stride, pad, mode, *, border=0, shadow=False, dst=None):
         Ho, Wo = (src.H + 2 * pad - k) // stride + 1, (src.W + 2 * pad - k) // stride + 1
         if dst is None:
-            dst = self._map(dst_name, src.n, Ho, Wo, src.C, border, shadow)
+            dst = self.mem.map(dst_name, src.n, Ho, Wo, src.C, border, shadow)
         if self.split and dst.sh is not None:
-            L.pool2d_split(src.f32, dst.f32, dst.b16, lo_offset=dst.sh.lo, B=src.n, H=src.H, W=src.W, C_=src.C, k=k,
+            L.pool2d_split(src.f32, dst.f32, dst.sh, lo_offset=dst.lo, B=src.n, H=src.H, W=src.W, C_=src.C, k=k,
                            stride=stride, pad=pad, mode=mode, Ho=Ho, Wo=Wo, in_border=src.border, out_border=dst.border)
             return dst
         L.pool2d(src.f32, dst.f32, B=src.n, H=src.H, W=src.W, C_=src.C, k=k, stride=stride, pad=pad, mode=mode, Ho=Ho, Wo=Wo,
-                 out_bf16=dst.b16, in_border=src.border, out_border=dst.border)
+                 out_bf16=dst.sh, in_border=src.border, out_border=dst.border)
         return dst
 
     def _block(self, p, x):
@@ -344,7 +268,7 @@ class Video2RollEngine:
             feats.append(h)
         x1, x2, x3, x4 = feats
         P = x4.H * x4.W
-        view = lambda k, C: self._Map(head[k][row:row + n].view(n, x4.H, x4.W, C), None, n, x4.H, x4.W, C, 0)
+        view = lambda k, C: Map(head[k][row:row + n].view(n, x4.H, x4.W, C), None, x4.H, x4.W)
         x5 = self._conv("toplayer", x4, "x5", relu=True, dst=view("x5", 64))
         t = self._ftb("FTB2_1", x2, to_conv=True)
         shapes = []
@@ -357,9 +281,8 @@ class Video2RollEngine:
         x3_ = self._ftb("FTB3", x3, dst=view("x3", 128))
         x4_ = self._ftb("FTB4", x4, avg=False, dst=view("x4", 128))
         if taps is not None:
-            nchw = lambda m: m.interior().permute(0, 3, 1, 2).clone()
             for k, v in dict(c1=c1, x1=x1, x2=x2, x3=x3, x4=x4, x5=x5, x2_=x2_, x3_=x3_, x4_=x4_).items():
-                taps.setdefault(k, []).append(nchw(v))
+                taps.setdefault(k, []).append(v.nchw().clone())
         return P
 
     def _head_buffers(self, total, H, W):
@@ -370,10 +293,10 @@ class Video2RollEngine:
             hc, wc = (hc + 2 - 3) // 2 + 1, (wc + 2 - 3) // 2 + 1
         P = hc * wc
         key = ("head", total, P)
-        hb = self._maps.get(key)
+        hb = self._bufs.get(key)
         if hb is None:
             e = lambda C: torch.empty(total, P, C, device=self.dev, dtype=torch.float32)
-            hb = self._maps[key] = dict(x2=e(128), x3=e(128), x4=e(128), x5=e(64))
+            hb = self._bufs[key] = dict(x2=e(128), x3=e(128), x4=e(128), x5=e(64))
         return hb, P
 
     def _pack(self, clip_frames, T, H, W):
@@ -383,11 +306,11 @@ class Video2RollEngine:
         _, Wo = cv.out_hw(H, W)
         key = ("patches", T, H, W, self.split)
         plane = (T + 4) * Wo * (H + 2 * cv.pad) * 16
-        op = self._maps.get(key)
+        op = self._bufs.get(key)
         if op is None:
             K = cv.ci * cv.g * 64
             buf = torch.empty(plane * (2 if self.split else 1), device=self.dev, dtype=torch.bfloat16)
-            op = self._maps[key] = L.Operand(buf, K, K, plane if self.split else 0)
+            op = self._bufs[key] = L.Operand(buf, K, K, plane if self.split else 0)
         if self.split:
             L.frames_pack_split(clip_frames, op.t, lo_offset=op.lo, T=T, H=H, W=W, kw=cv.kw, stride=cv.stride, pad=cv.pad, Wo=Wo)
         else:
