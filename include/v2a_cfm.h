@@ -344,6 +344,59 @@ int v2a_attention(const v2a_attn_args* args, v2a_stream_t stream);
 int v2a_qproj_xattn(const v2a_gemm_args* gemm, const v2a_attn_args* attn, v2a_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Cross-attention with the context absorbed into the weights (bf16x3 mode; additive entry points, ABI 9).  Without rotary in
+ * cross-attention and with bias-free to_q / to_k / to_v / to_out, for clip b, layer l, head h and key slot j
+ *   logits[n,h,j] = x[n,:] . Wqk[b,l][(h,j),:]      Wqk[(h,j),c] = sum_d K[b,j,l,h,d] * to_q[l][h*64+d, c]
+ *   out[n,o] = sum_{h,j} P[n,h,j] * sigmoid(gate[n,h]) * Wvo[b,l][o,(h,j)]      Wvo[o,(h,j)] = sum_d to_out[l][o, h*64+d] * V[b,j,l,h,d]
+ * and K, V of the context are constants of a sample() call.  KP = key slots per head: 16 (nc <= 16) or 32 (nc <= 32).
+ *
+ * v2a_xattn_absorb_prepare (once per sample(), two launches for all clips, layers and heads): from the fp32 context K / V rows
+ * (row b*nc + j; K of layer l at columns k_col + l*H*64, V at v_col + l*H*64) and fp32 masters wq [L][H*64 + H][D] (to_q rows, then
+ * the to_v_head_gate rows) and wo [L][D][H*64] writes, as V2A_BF16_SPLIT rows [hi | lo] of the fp32 results (fma chains over the 64
+ * head dimensions in order),
+ *   wqk [B][L][H*KP + H][2 D]   row h*KP + j as above, zero for nc <= j < KP; the last H rows are the planes of the gate rows
+ *   wvo [B][L][D][2 H*KP]       columns h*KP + j as above, zero for nc <= j < KP
+ * ------------------------------------------------------------------------------------- */
+typedef struct v2a_xattn_prepare_args {
+  const float* ctx_kv;
+  int64_t ctx_ld;        /* floats per context row */
+  int32_t k_col, v_col;
+  const float* wq;
+  const float* wo;
+  void* wqk;
+  void* wvo;             /* 8-byte aligned */
+  int32_t B, L, H, D, nc, KP;
+} v2a_xattn_prepare_args;
+int v2a_xattn_absorb_prepare(const v2a_xattn_prepare_args* args, v2a_stream_t stream);
+
+/* v2a_xattn_absorbed (per evaluation): rows of `a` (V2A_BF16_SPLIT, [hi K | lo K], K a multiple of 512, <= 2048) times Wqk of the
+ * row's clip (row / rows_per_batch; clips w_batch_stride elements apart, rows ldw >= 2 K apart) as the split GEMM computes it (per
+ * 32 k: A_lo W_hi + A_hi W_lo + A_hi W_hi), then per row and head: x 1/rms of the row when row_ssq is given (the folded-norm
+ * consumer of v2a_gemm_args), soft clamp clamp*tanh(scale*s/clamp) (softclamp > 0), key slots >= min(kv_len[b], KP) masked, softmax
+ * over the KP slots, times sigmoid(gate logit (x 1/rms) + gate_bias[h]); rows at or beyond q_len[b] in their clip and rows of a clip
+ * with kv_len[b] = 0 are exactly zero.  out: (M, [hi H*KP | lo H*KP]) bf16 rows ldo apart, the A operand of
+ * v2a_gemm(V2A_EPI_GATE_RESID) with W = Wvo of the clip, K = H*KP.  H*KP must be a multiple of 64; kv_len is required.
+ * Replaces, together with that GEMM: v2a_qproj_xattn (or v2a_gemm + v2a_attention) and the out-projection at call site x3:1126. */
+typedef struct v2a_xattn_absorbed_args {
+  const void* a;
+  int64_t lda;
+  int32_t K, M;
+  const void* wqk;
+  int64_t ldw, w_batch_stride;
+  const float* gate_bias;   /* [H] or NULL */
+  void* out;
+  int64_t ldo;
+  int32_t rows_per_batch, B, H, KP;
+  const int32_t* kv_len;    /* [B] */
+  const int32_t* q_len;     /* [B] or NULL (= rows_per_batch) */
+  float scale, softclamp;
+  const float* row_ssq;     /* as v2a_gemm_args: row_ssq, ld_row_ssq, row_ssq_parts, row_norm_dim */
+  int64_t ld_row_ssq;
+  int32_t row_ssq_parts, row_norm_dim;
+} v2a_xattn_absorbed_args;
+int v2a_xattn_absorbed(const v2a_xattn_absorbed_args* args, v2a_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Small fp32 linear with output row scatter (1 <= K <= 2048, VALU; V2A_ERR_ARG beyond):
  *   out[(m / T)*out_batch_stride + (row_off + m % T)*d + n] =
  *        bias[n] + add[(m % T)*d + n] + sum_k a[m*K + k] * wt[k*d + n]

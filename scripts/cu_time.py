@@ -32,7 +32,7 @@ def num(r, *names):
 
 def short(n):
     n = re.sub(r"\(anonymous namespace\)::|void ", "", n)
-    m = re.search(r"(gemm_bf16_dma_kernel<[^>]*>|gemm_bf16_dma_kernelI\w+?E{2}|gemm_bf16_8ph_kernel<[^>]*>|gemm_bf16_8ph_kernelI\w+?E{2}|attn_mfma\w*<[^>]*>|qproj_xattn\w*|dwconv\w*|rmsnorm\w*|cfg_euler|linear_small|split_bf16)", n)
+    m = re.search(r"(gemm_bf16_dma_kernel<[^>]*>|gemm_bf16_dma_kernelI\w+?E{2}|gemm_bf16_8ph_kernel<[^>]*>|gemm_bf16_8ph_kernelI\w+?E{2}|attn_mfma\w*<[^>]*>|qproj_xattn\w*|xattn_absorbed\w*|absorb_w\w*|dwconv\w*|rmsnorm\w*|cfg_euler|linear_small|split_bf16)", n)
     return (m.group(1) if m else n)[:60]
 
 
@@ -55,6 +55,8 @@ def dyn_lds(name):
         return int(m.group(1)) * 2 * 2 * (64 * 64 + 64 * 64) * 2
     if "qproj_xattn_kernel" in n:
         return 100 * 1024 if "true" in n else 52 * 1024
+    if "xattn_absorbed_kernel" in n:        # ring + the gate rows of the workgroup's heads (K = 1024: 64 / KP rows of 4 KB + 64 B)
+        return 96 * 1024 + (4 if re.search(r"<\d+, 16>|ELi16EE", n) else 2) * 4160 + 256
     if "dwconv_stream_kernel" in n:
         return 135 * 1024
     return 0

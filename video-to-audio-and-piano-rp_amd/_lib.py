@@ -95,6 +95,23 @@ class AttnArgs(C.Structure):
     ]
 
 
+class XattnPrepareArgs(C.Structure):
+    """Mirror of `v2a_xattn_prepare_args`."""
+    _fields_ = [("ctx_kv", C.c_void_p), ("ctx_ld", C.c_int64), ("k_col", C.c_int32), ("v_col", C.c_int32),
+                ("wq", C.c_void_p), ("wo", C.c_void_p), ("wqk", C.c_void_p), ("wvo", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("B", "L", "H", "D", "nc", "KP")]
+
+
+class XattnAbsorbedArgs(C.Structure):
+    """Mirror of `v2a_xattn_absorbed_args`."""
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int64), ("K", C.c_int32), ("M", C.c_int32),
+                ("wqk", C.c_void_p), ("ldw", C.c_int64), ("w_batch_stride", C.c_int64), ("gate_bias", C.c_void_p),
+                ("out", C.c_void_p), ("ldo", C.c_int64),
+                ("rows_per_batch", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("KP", C.c_int32),
+                ("kv_len", C.c_void_p), ("q_len", C.c_void_p), ("scale", C.c_float), ("softclamp", C.c_float),
+                ("row_ssq", C.c_void_p), ("ld_row_ssq", C.c_int64), ("row_ssq_parts", C.c_int32), ("row_norm_dim", C.c_int32)]
+
+
 class T5AttnArgs(C.Structure):
     """Mirror of `v2a_t5_attn_args`."""
     _fields_ = [
@@ -131,6 +148,7 @@ EXPORTS = [
     "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode", "v2a_cfm_interp", "v2a_masked_sqerr", "v2a_roll_metrics",
     "v2a_wave_resample", "v2a_wave_stats", "v2a_wave_normalize",
     "v2a_roll2midi_stem", "v2a_leaky_shadow", "v2a_roll2midi_head",
+    "v2a_xattn_absorb_prepare", "v2a_xattn_absorbed",
 ]
 
 
@@ -161,6 +179,8 @@ def _declare(lib):
     lib.v2a_set_tuning.argtypes = [C.POINTER(Tuning)]
     lib.v2a_attention.argtypes = [C.POINTER(AttnArgs), vp]
     lib.v2a_qproj_xattn.argtypes = [C.POINTER(GemmArgs), C.POINTER(AttnArgs), vp]
+    lib.v2a_xattn_absorb_prepare.argtypes = [C.POINTER(XattnPrepareArgs), vp]
+    lib.v2a_xattn_absorbed.argtypes = [C.POINTER(XattnAbsorbedArgs), vp]
     lib.v2a_rmsnorm.argtypes = [vp, i64, vp, i64, i32, i64, i32, vp, vp, i64, i64, i32, vp]
     lib.v2a_dwconv_silu_residual.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     lib.v2a_dwconv_silu_residual_norm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, C.POINTER(DwconvNorm), vp]
@@ -539,6 +559,44 @@ def qproj_xattn(a, lda, K, w, *, bias, M, N, rows_per_batch, k, v, out, kv_strid
     _launch("qproj_xattn<%s>" % ("bf16x3" if split else "bf16"), (3.0 if split else 1.0) * (2.0 * M * (H * 65) * K + 4.0 * B * H * rows_per_batch * Nk * 64),
             M * K * 2 + H * 65 * K * 2 + M * H * 64 * 2 + 2 * B * Nk * H * 64 * 2,
             lambda: lib().v2a_qproj_xattn(C.byref(g), C.byref(t), stream_ptr()))
+
+
+def xattn_kp(nc):
+    """Key slots per head of the absorbed cross-attention: 16 up to 16 context tokens, 32 up to 32."""
+    return 16 if nc <= 16 else 32
+
+
+def xattn_absorb_prepare(ctx_kv, wq, wo, wqk, wvo, *, B, L, H, D, nc, KP, k_col, v_col):
+    """Absorbed cross-attention operands of every (clip, layer), once per sample() (v2a_xattn_absorb_prepare).  ctx_kv: fp32 (B*nc, ld)
+    context K / V rows, K of layer l at columns k_col + l*H*64, V at v_col + l*H*64; wq: fp32 [L][H*64 + H][D] (to_q rows, gate rows);
+    wo: fp32 [L][D][H*64]; wqk: bf16 [B][L][H*KP + H][2 D]; wvo: bf16 [B][L][D][2 H*KP] (hi | lo planes)."""
+    a = XattnPrepareArgs()
+    a.ctx_kv, a.ctx_ld, a.k_col, a.v_col = ctx_kv.data_ptr(), ctx_kv.stride(-2), k_col, v_col
+    a.wq, a.wo, a.wqk, a.wvo = wq.data_ptr(), wo.data_ptr(), wqk.data_ptr(), wvo.data_ptr()
+    a.B, a.L, a.H, a.D, a.nc, a.KP = B, L, H, D, nc, KP
+    _launch("xattn_absorb_prepare", 4.0 * B * L * H * KP * 64 * D,
+            L * (2 * H * 64 + H) * D * 4 + B * L * ((H * KP + H) * D + D * H * KP) * 4 + 2 * B * nc * L * H * 64 * 4,
+            lambda: lib().v2a_xattn_absorb_prepare(C.byref(a), stream_ptr()))
+
+
+def xattn_absorbed(a, lda, K, wqk, out, *, ldw, w_batch_stride, ldo, M, rows_per_batch, B, H, KP, kv_len, q_len=None, gate_bias=None,
+                   scale, softclamp, row_ssq=None, row_norm_dim=0):
+    """Logits, softmax and head gate of the absorbed cross-attention in one launch (v2a_xattn_absorbed).  a: (M, [hi K | lo K]) bf16
+    rows; wqk: bf16 [B][H*KP + H][2 K] of the clips (w_batch_stride elements apart); out: (M, [hi H*KP | lo H*KP]) bf16 rows."""
+    g = XattnAbsorbedArgs()
+    g.a, g.lda, g.K, g.M = a.data_ptr(), lda, K, M
+    g.wqk, g.ldw, g.w_batch_stride, g.gate_bias = wqk.data_ptr(), ldw, w_batch_stride, _p(gate_bias)
+    g.out, g.ldo = out.data_ptr(), ldo
+    g.rows_per_batch, g.B, g.H, g.KP = rows_per_batch, B, H, KP
+    g.kv_len, g.q_len = _p(kv_len), _p(q_len)
+    g.scale, g.softclamp = scale, softclamp
+    g.row_ssq = _p(row_ssq)
+    g.ld_row_ssq = row_ssq.stride(-2) if row_ssq is not None else 0
+    g.row_ssq_parts = row_norm_dim // 32 if row_ssq is not None else 0
+    g.row_norm_dim = row_norm_dim
+    n = H * KP + H
+    _launch("xattn_absorbed<bf16x3>", 6.0 * M * n * K, (M * K + B * n * K + M * H * KP) * 4,
+            lambda: lib().v2a_xattn_absorbed(C.byref(g), stream_ptr()))
 
 
 def linear_small(a, wt, bias, add, out, *, M, K, T, out_batch_stride, row_off, d, dup=0, regs=None, out_bf16=None):

@@ -1,5 +1,5 @@
-// The arithmetic that the four MFMA attention kernels share (attn_mfma_kernel, attn_mfma_split_kernel, attn_mfma_f32_kernel in
-// attention.hip, qproj_xattn_kernel in qproj_xattn.hip), each piece defined once: the kernels differ in how an operand becomes an
+// The arithmetic that the MFMA attention kernels share (attn_mfma_kernel, attn_mfma_split_kernel, attn_mfma_f32_kernel in
+// attention.hip, qproj_xattn_kernel in qproj_xattn.hip; the clamp / softmax step also xattn_absorbed_kernel in xattn_absorbed.hip), each piece defined once: the kernels differ in how an operand becomes an
 // MFMA fragment, not in what happens between S^T = K Q^T and O^T += V^T P^T or after the key loop.  The one-launch cross attention
 // promises the bits of the two-launch path; it keeps that promise by calling these functions, not by repeating their text.
 //
@@ -64,12 +64,13 @@ __device__ __forceinline__ AttnLogitScale attn_logit_scale(float scale, float cl
 // CLAMP: 0 = plain logits, 1 = soft clamp, 2 = soft clamp with bounded weights, p = 2^(C - 2C / (..)) directly: no maximum (see
 // attn_clamp_mode).  ONLINE: the tile is one of several -- m is the running maximum, l and o are rescaled to the new one.  A
 // single-tile caller passes ONLINE = false: m, l and o are left alone (0 * alpha is not dropped without fast-math, so a call
-// with dummy state would not be the same code).
-template <int CLAMP, bool ONLINE>
-__device__ __forceinline__ void attn_weights(f32x4 (&s)[4], float& m, float& l, f32x4 (&o)[4], int j0, int kvn, int g, AttnLogitScale sc) {
+// with dummy state would not be the same code).  NT (deduced) = 16-key register tiles of the key tile: 4 in the attention kernels, 1 or 2
+// tiles of key slots per head in the absorbed cross-attention (xattn_absorbed.hip).
+template <int CLAMP, bool ONLINE, int NT>
+__device__ __forceinline__ void attn_weights(f32x4 (&s)[NT], float& m, float& l, f32x4 (&o)[4], int j0, int kvn, int g, AttnLogitScale sc) {
   const float zc = sc.zc, c2 = sc.c2;
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if constexpr (CLAMP == 2) {
@@ -82,9 +83,9 @@ __device__ __forceinline__ void attn_weights(f32x4 (&s)[4], float& m, float& l, 
         s[t][j] = s[t][j] * zc;
       }
     }
-  if (j0 + 64 > kvn) {             // only the last tile can be partial (wave-uniform branch)
+  if (j0 + 16 * NT > kvn) {             // only the last tile can be partial (wave-uniform branch)
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (j0 + 16 * t + 4 * g + j >= kvn) s[t][j] = CLAMP == 2 ? 0.f : -INFINITY;
@@ -92,7 +93,7 @@ __device__ __forceinline__ void attn_weights(f32x4 (&s)[4], float& m, float& l, 
   if constexpr (CLAMP != 2) {
     float mn = -INFINITY;            // row maximum: 16 keys of the lane, then the four key groups of the wave
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int j = 0; j < 4; ++j) mn = fmaxf(mn, s[t][j]);
     mn = fmaxf(mn, __shfl_xor(mn, 16, 64));
@@ -108,7 +109,7 @@ __device__ __forceinline__ void attn_weights(f32x4 (&s)[4], float& m, float& l, 
         for (int j = 0; j < 4; ++j) o[dt][j] *= alpha;
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int j = 0; j < 4; ++j) s[t][j] = __builtin_amdgcn_exp2f(s[t][j] - mn);
   }

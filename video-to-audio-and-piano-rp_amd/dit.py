@@ -24,6 +24,7 @@ dtype (bf16, or fp32 in parity mode) and live in per-stream scratch buffers size
 from __future__ import annotations
 
 import math
+import os
 from collections import OrderedDict
 from dataclasses import dataclass, asdict
 from typing import NamedTuple
@@ -113,6 +114,9 @@ class _Attn:
         self.b_in = b.to(dev)
         self.w_out = pack_weight(sd[f"{prefix}.to_out.weight"], dev, cd, split)
         self.wk, self.wv = (wk, wv) if cross else (None, None)
+        # bf16x3 mode: fp32 masters of [to_q | head gate] and to_out, the inputs of the absorbed cross-attention operands (PackedWeights
+        # stacks them over the layers and drops these references)
+        self.wq32, self.wo32 = (torch.cat([wq.float(), wg.float()], 0), sd[f"{prefix}.to_out.weight"].float()) if cross and split else (None, None)
 
 
 class _FF:
@@ -216,8 +220,14 @@ class PackedWeights:
         self.gate_b = torch.cat([b.float() for b in gb], 0).to(dev).contiguous()
         # cross-attention K/V projections of every layer stacked: [K_0..K_{L-1} | V_0..V_{L-1}]
         self.ctx_kv_w = pk(torch.cat([w.float() for w in kw] + [w.float() for w in vw], 0))
+        # bf16x3 mode: fp32 masters of the cross-attention [to_q | gate] and to_out weights of every layer, [L][inner + H][d] and
+        # [L][d][inner]: what v2a_xattn_absorb_prepare folds the context K / V into once per sample() (DiTEngine.absorb_xattn)
+        self.xattn_wq = self.xattn_wo = None
+        if split:
+            self.xattn_wq = torch.stack([ly["a_attn2"].wq32 for ly in self.layers]).to(dev).contiguous()
+            self.xattn_wo = torch.stack([ly["a_attn2"].wo32 for ly in self.layers]).to(dev).contiguous()
         for ly in self.layers:
-            ly["a_attn2"].wk = ly["a_attn2"].wv = None
+            ly["a_attn2"].wk = ly["a_attn2"].wv = ly["a_attn2"].wq32 = ly["a_attn2"].wo32 = None
 
 
 # ---- measured tile choices, in ONE place -----------------------------------------------------------------------------------------
@@ -330,6 +340,11 @@ class DiTEngine:
         # bf16 and bf16x3 modes, up to three clips (bf16 stand-alone: 19.5 vs 23.2 us at three, 26.7 vs 25.7 at four): the audio stream's cross-attention as ONE launch (v2a_qproj_xattn: q-projection, RoPE, attention over
         # the <= 64 context keys and the head gate without the [q | gate] buffer in between); equal bit for bit to the two launches
         self.fuse_xattn = True
+        # bf16x3 mode without rotary in cross-attention, nc <= 32, up to three clips: the context K / V folded into to_q and to_out once per
+        # sample() (v2a_xattn_absorb_prepare), an evaluation runs logits + softmax + head gate over KP = 16 / 32 key slots per head
+        # (v2a_xattn_absorbed) and one K = H*KP out-projection per clip: see _absorb().  Independent of fuse_xattn, which chooses the form
+        # of the unabsorbed path.  V2A_ABSORB_XATTN=0 in the environment turns the default off (A/B runs of an unchanged bench.py).
+        self.absorb_xattn = os.environ.get("V2A_ABSORB_XATTN", "1") != "0"
         # x_at / x_af cross-condition GEMMs on the side streams (True: all three on the main stream, -2.2 %)
         self.cross_on_main = False
         # capture order: audio {cross .. self-attention}, sides {conv, norm, attention}, audio {cross-attention, feed-forward},
@@ -366,6 +381,7 @@ class DiTEngine:
         if p is not None:
             self.plans.move_to_end(key)
             self.plan = p
+            self._alloc_absorbed(p)     # absorb_xattn may have been switched on since the plan was made
             return p
         c, dev, cd = self.cfg, self.dev, self.cd
         R = c.num_registers
@@ -409,6 +425,8 @@ class DiTEngine:
         p["q2"] = e(B * N, W0["a_attn2"].n_pad, dt=self.ad)
         inner = c.heads * c.dim_head
         p["ctx_kv"] = e(B * nc, 2 * c.depth * inner, dt=self.ad)
+        p["xattn_kp"] = 0
+        self._alloc_absorbed(p)
         p["ctx"] = e(B * nc, w2 * c.ctx_dim, dt=cd)
         p["ctx_len"] = torch.full((B,), nc, dtype=torch.int32, device=dev)
         p["pred"] = e(Bt, N, c.num_channels)
@@ -450,7 +468,7 @@ class DiTEngine:
         p = self.plan
         return (p["ragged"], p["has_cond"], p["per_sample_t"], self.multi_stream, self.side_tile, tuple(sorted(self.side_tiles.items())),
                 tuple(sorted(self.big_tiles.items())), tuple(sorted(self.split_tiles.items())), tuple(sorted(self.split_big_tiles.items())), self.main_tile, self.fold_norm, self.fold_gemm_all, self.fuse_skip, self.fuse_xattn, self.cross_on_main,
-                self.interleave_capture, self.rope_cross, self.zero_masked_queries)
+                self.interleave_capture, self.rope_cross, self.zero_masked_queries, self.absorb_xattn, p["xattn_kp"])
 
     # --------------------------------------------------------------------------- primitives
     def _rows(self, t):
@@ -621,11 +639,64 @@ class DiTEngine:
                 self._norm_plain(x, hn, rows, d, ly[f"{s}_g2"])
             self._ff(ly[f"{s}_ff"], x, s, nseq, d, dict(epilogue=L.EPI_RESID, tile_hint=h2, shadow=dst.sh), cons2)
 
+    def _absorb(self, B, N, nc):
+        """Whether a plan of B clips with N rows and nc context tokens takes the absorbed cross-attention: the identity needs no rotary
+        in cross-attention (the rotation depends on the query position and does not factor); the kernels are built for the bf16x3 mode,
+        KP = 16 / 32 key slots per head with whole 64-column groups of heads, and the sizes of the one-launch form (D a multiple of 512, no
+        q bias rows besides the gates, at most 704 workgroups of 64 tokens x one head: three clips at the shipped widths -- beyond that
+        one out-projection launch per clip stops paying)."""
+        c = self.cfg
+        A2 = self.W.layers[0]["a_attn2"]
+        return (self.absorb_xattn and self.split and not self.rope_cross and 0 < nc <= 32 and (c.heads * L.xattn_kp(nc)) % 64 == 0
+                and c.dim % 512 == 0 and c.dim <= 2048 and A2.gate_col == A2.inner and B * -(-N // 64) * A2.heads <= 704)
+
+    def _alloc_absorbed(self, p):
+        """Buffers of the absorbed cross-attention, only for a plan that takes it: Wqk / Wvo of every (clip, layer) as hi | lo planes
+        (filled by prepare()) and P * sigmoid(gate) of an evaluation.  p["xattn_kp"] = the plan's key slots per head, 0 = not absorbed."""
+        c = self.cfg
+        if p["xattn_kp"] or not self._absorb(p["B"], p["N"], p["nc"]):
+            return
+        kp = p["xattn_kp"] = L.xattn_kp(p["nc"])
+        e = lambda *s: torch.empty(*s, dtype=self.cd, device=self.dev)
+        p["wqk"] = e(p["B"], c.depth, c.heads * kp + c.heads, 2 * c.dim)
+        p["wvo"] = e(p["B"], c.depth, c.dim, 2 * c.heads * kp)
+        p["xp"] = e(p["B"] * p["N"], 2 * c.heads * kp)
+
+    def _audio_cross_attention_absorbed(self, i, ly, x, nctx, cons2, fold2, lens):
+        """The absorbed form of _audio_cross_attention: P sigmoid(gate) over the key slots (one launch), then per clip the K = H*KP
+        out-projection against Wvo of (clip, layer) with the gate / residual / folded-norm epilogue of the unabsorbed out-projection."""
+        p, c = self.plan, self.cfg
+        N, D, H, kp = p["N"], c.dim, c.heads, p["xattn_kp"]
+        A2 = ly["a_attn2"]
+        r2 = nctx * N
+        if not fold2:
+            self._norm_ada(x, p["hn_a"], r2, D, i, 1)
+        nk = dict(row_ssq=cons2["row_ssq"], row_norm_dim=cons2["row_norm_dim"]) if cons2 else {}
+        wqk, wvo, xp = p["wqk"], p["wvo"], p["xp"]
+        L.xattn_absorbed(p["hn_a"], p["hn_a"].stride(-2), D, wqk[0, i], xp, ldw=wqk.stride(-2), w_batch_stride=wqk.stride(0), ldo=xp.stride(-2),
+                         M=r2, rows_per_batch=N, B=nctx, H=H, KP=kp, kv_len=p["ctx_len"], q_len=lens if self.zero_masked_queries else None,
+                         gate_bias=A2.b_in[A2.gate_col:], scale=c.dim_head ** -0.5, softclamp=self.softclamp, **nk)
+        xr, hn = x.reshape(-1, D), p["hn_a"]
+        for b in range(nctx):                   # W differs per clip: one launch each, the rows of the clip by offset pointers
+            rows = slice(b * N, (b + 1) * N)
+            kw = dict(self._gate_kw(i, 1))
+            if fold2:
+                kw.update(self._nprod_ada(i, 2))
+                kw.update(norm_ssq=p["ssq_a"][rows], shadow=self._rows(hn[rows]))
+            if p["per_sample_t"]:               # the tables' batch stride counts from the launch's first row
+                kw["gate"] = p["gate_tab"][b, i, 1]
+                if fold2:
+                    kw["norm_gamma"] = p["norm_tab"][b, i, 2]
+            self._mm([self._rows(xp[rows])], wvo[b, i], xr[rows], M=N, N=D, resid=xr[rows], ldo=D, ldr=D, epilogue=L.EPI_GATE_RESID,
+                     tile_hint=self._tile_hint("a", "out2"), **kw)
+
     def _audio_cross_attention(self, i, ly, x, nctx, cons2, fold2, lens):
         """x[:nctx] += gate * to_out(attend(q(x), K_ctx, V_ctx)) of layer i (x3:1126-1133) on the current stream: one launch
         (v2a_qproj_xattn) + the out-projection, or q-projection, (RoPE,) attention, out-projection."""
         p, c, W = self.plan, self.cfg, self.W
         N, D = p["N"], c.dim
+        if p["xattn_kp"] and self.absorb_xattn:
+            return self._audio_cross_attention_absorbed(i, ly, x, nctx, cons2, fold2, lens)
         inner = c.heads * c.dim_head
         nkv = 2 * c.depth * inner
         r2 = nctx * N
@@ -755,6 +826,9 @@ class DiTEngine:
             assert 0 <= off and off + nc <= p["rope"].shape[0], (off, nc, N)
             L.rope(p["ctx_kv"], rows=B * nc, row_stride=nkv, nheads=c.depth * c.heads, rows_per_batch=nc,
                    pos_offset=off, table=p["rope"], layout=self.rope_layout)
+        if p["xattn_kp"] and self.absorb_xattn:               # the context folded into to_q / to_out, re-armed by every call
+            L.xattn_absorb_prepare(p["ctx_kv"], W.xattn_wq, W.xattn_wo, p["wqk"], p["wvo"], B=B, L=c.depth, H=c.heads, D=D, nc=nc,
+                                   KP=p["xattn_kp"], k_col=0, v_col=c.depth * inner)
         # -- hoisted layer-0 text / frames blocks
         ly = W.layers[0]
         self._side_block(ly, "t", p["t0"], p["tL0"], Bt, Dt)
