@@ -826,6 +826,18 @@ int v2a_leaky_shadow(float* x, void* shadow, int32_t shadow_mode, int64_t lo_off
 int v2a_roll2midi_head(const float* u, int64_t u_pitch, int32_t nu, const float* d, int64_t d_pitch, int32_t nd, const float* w,
                        float bias, float threshold, int32_t n, int32_t H, int32_t W, int32_t border, float* logits, float* probs,
                        uint8_t* midi, v2a_stream_t stream);
+/* Attention gate of Roll2MidiNet_enhance.py (`AttentionGate.forward`, enh:49-55) with theta_x, phi_g and psi folded into one weight
+ * vector w (C0 + C1) fp32 and a bias (roll2midi.folded_gate).  Per pixel of the (n, H, W) grid, over the concatenation of segment 0
+ * (C0 channels at x0, pitch0) and segment 1 (C1 channels at x1, pitch1; C1 = 0 with x1 = shadow1 = NULL: one segment), both with the
+ * geometry above and one border; C0, C1 multiples of 8, C0 + C1 <= 2048 (one wave holds the pixel in registers):
+ *   z = sum + bias, sum = xor butterfly over 64 lanes of the lanes' chains fma(w[c], x[c], acc) from 0 over channels
+ *       c = 512 j + 8 lane + e (j, e ascending): the order depends on (C0, C1) alone, never on n, the grid or the other pixels
+ *   alpha = 1 / (1 + expf(-z));   x[c] = x[c] * alpha in place (one fp32 multiply), and the shadow of the stored value at the same
+ *   offsets of shadow0 / shadow1 (shadow_mode as above, lo_offset per segment).  Borders and other channels are not touched.
+ *   logits[i] = z, alpha[i] = alpha   dense (n, H, W) fp32; NULL = not written.  Additive: the ABI version does not change. */
+int v2a_roll2midi_gate(float* x0, int64_t pitch0, int32_t C0, void* shadow0, int64_t lo_offset0, float* x1, int64_t pitch1, int32_t C1,
+                       void* shadow1, int64_t lo_offset1, const float* w, float bias, int32_t shadow_mode, int32_t n, int32_t H, int32_t W,
+                       int32_t border, float* logits, float* alpha, v2a_stream_t stream);
 
 #ifdef __cplusplus
 }

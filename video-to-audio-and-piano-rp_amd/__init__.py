@@ -11,7 +11,7 @@ from .features import (feature_cache_path, save_clip_cache, load_clip_cache, res
                        resample_clip_features, encode_video_cached, piano_frames_cache_path, save_piano_frames_cache,
                        piano_frame_indices, load_piano_frames, piano_frames_from_video, load_midi_ground_truth)
 from .video2roll import Video2RollEngine  # noqa: F401
-from .roll2midi import Roll2MidiEngine  # noqa: F401
+from .roll2midi import Roll2MidiEngine, Roll2MidiEnhanceEngine  # noqa: F401
 from .encodec import EncodecDecoder, EncodecEncoder, EncodecQuantizer  # noqa: F401
 from .t5 import T5Encoder  # noqa: F401
 from .clip import CLIPImageEncoder  # noqa: F401
@@ -22,5 +22,5 @@ from . import _lib  # noqa: F401
 
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
            "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "val_span_mask", "E2TTSReturn", "LossBreakdown", "load_midi_ground_truth", "expected_state_dict_shapes", "NOTES",
-           "Video2RollEngine", "Roll2MidiEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor",
+           "Video2RollEngine", "Roll2MidiEngine", "Roll2MidiEnhanceEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor",
            "WaveFrontEnd", "sinc_resample_table"]

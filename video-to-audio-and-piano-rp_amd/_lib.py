@@ -147,7 +147,7 @@ EXPORTS = [
     "v2a_elu_pad_lr", "v2a_encodec_stage0", "v2a_piano_resize_h", "v2a_piano_resize_v",
     "v2a_encodec_rvq_encode", "v2a_encodec_rvq_decode", "v2a_cfm_interp", "v2a_masked_sqerr", "v2a_roll_metrics",
     "v2a_wave_resample", "v2a_wave_stats", "v2a_wave_normalize",
-    "v2a_roll2midi_stem", "v2a_leaky_shadow", "v2a_roll2midi_head",
+    "v2a_roll2midi_stem", "v2a_leaky_shadow", "v2a_roll2midi_head", "v2a_roll2midi_gate",
     "v2a_xattn_absorb_prepare", "v2a_xattn_absorbed",
 ]
 
@@ -226,6 +226,7 @@ def _declare(lib):
     lib.v2a_roll2midi_stem.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i64, i64, i32, vp]
     lib.v2a_leaky_shadow.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, i64, i32, vp]
     lib.v2a_roll2midi_head.argtypes = [vp, i64, i32, vp, i64, i32, vp, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.v2a_roll2midi_gate.argtypes = [vp, i64, i32, vp, i64, vp, i64, i32, vp, i64, vp, f32, i32, i32, i32, i32, i32, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -699,6 +700,16 @@ def roll2midi_head(u, d, w, *, u_pitch, nu, d_pitch, nd, bias, threshold, n, H, 
     _launch("roll2midi_head", 2.0 * n * H * W * (nu + nd), n * H * W * (4.0 * (nu + nd) + 9),
             lambda: lib().v2a_roll2midi_head(u.data_ptr(), u_pitch, nu, d.data_ptr(), d_pitch, nd, w.data_ptr(), float(bias), float(threshold),
                                              n, H, W, border, _p(logits), _p(probs), _p(midi), stream_ptr()))
+
+
+def roll2midi_gate(seg0, seg1, w, *, bias, shadow_mode, n, H, W, border, logits=None, alpha=None):
+    """The folded attention gate in place on one or two segments (x, pitch, C, shadow, lo_offset); seg1 None: one segment.  x and
+    shadow start at the segment's first channel."""
+    x0, p0, c0, s0, l0 = seg0
+    x1, p1, c1, s1, l1 = seg1 if seg1 is not None else (None, 0, 0, None, 0)
+    _launch("roll2midi_gate", 2.0 * n * H * W * (c0 + c1), n * H * W * (c0 + c1) * (8.0 + 2 * shadow_mode) + 4.0 * (c0 + c1),
+            lambda: lib().v2a_roll2midi_gate(x0.data_ptr(), p0, c0, _p(s0), l0, _p(x1), p1, c1, _p(s1), l1, w.data_ptr(), float(bias),
+                                             shadow_mode, n, H, W, border, _p(logits), _p(alpha), stream_ptr()))
 
 
 # ---- N1: Encodec decoder (vocoder) ---------------------------------------------------------------

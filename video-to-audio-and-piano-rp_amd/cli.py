@@ -37,8 +37,9 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
                      trainer_multigpus_alldatas3.py:1047-1050, 1427-1431) into the HIP Encodec encoder.  Under --validate a video without
                      `<video>.latent.npy` takes its ground truth from `<video>.wav` (an existing `.latent.npy` wins); under
                      --audio-prompt-seconds the prompt is the first S seconds of the front end's output.
-  --roll2midi CKPT   (with --piano) the Roll2Midi generator of the reference's Audeo chain (src/audeo/Roll2MidiNet.py, run as in
-                     Roll2Midi_inference.py): a torch-saved checkpoint holding `state_dict_G`, or that state dict.  The per-frame key
+  --roll2midi CKPT   (with --piano) the Roll2Midi generator of the reference's Audeo chain, run as in Roll2Midi_inference.py: a
+                     torch-saved checkpoint holding `state_dict_G`, or that state dict -- the plain net (src/audeo/Roll2MidiNet.py) or
+                     the attention-gated one its trainer writes (Roll2MidiNet_enhance.py); the keys tell which.  The per-frame key
                      probabilities of the Video2Roll encoder go through it on the GPU and `<name>.midi.npz` is written next to each output:
                      `midi` (t, 51) uint8, the reference's key name (Roll2Midi_inference.py:79), and `prob` (t, 51) float32.
 The moviepy mux of audio and video stays outside (out of scope).
@@ -243,7 +244,7 @@ def build_parser() -> argparse.ArgumentParser:
                     "(resample to 24 kHz, normalize_wav) into the HIP Encodec encoder: the ground truth of --validate for a video without "
                     "<video>.latent.npy, and the prompt of --audio-prompt-seconds")
     ap.add_argument("--roll2midi", default=None, metavar="CKPT", help="with --piano: checkpoint (or state dict) of the Roll2Midi generator "
-                    "(`state_dict_G`): also write <name>.midi.npz with `midi` (t, 51) uint8 and `prob` (t, 51) float32 per video frame")
+                    "(`state_dict_G` of Roll2MidiNet.py or of Roll2MidiNet_enhance.py, told apart by its keys): also write <name>.midi.npz with `midi` (t, 51) uint8 and `prob` (t, 51) float32 per video frame")
     ap.add_argument("--roll2midi-dtype", default="bf16x3", choices=["fp32", "bf16", "bf16x3"], help="compute mode of the Roll2Midi generator")
     return ap
 

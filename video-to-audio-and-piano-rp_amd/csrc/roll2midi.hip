@@ -1,4 +1,5 @@
-// Roll2Midi generator (src/audeo/Roll2MidiNet.py:42-87, `r2m`): the three memory-bound kernels around its conv-as-GEMM path.
+// Roll2Midi generator (src/audeo/Roll2MidiNet.py:42-87, `r2m`): the three memory-bound kernels around its conv-as-GEMM path, and the
+//   attention gate of its enhanced variant (src/audeo/Roll2MidiNet_enhance.py:41-55, `enh`) as a fourth.
 //   The U-Net keeps the roll's size (every convolution is 3x3, stride 1, pad 1), so all maps share one (n, H, W) pixel grid:
 //   NHWC fp32, optionally stored with a zero border (the implicit-GEMM layout of v2a_gemm's offset tables) and optionally as a
 //   channel slice of a wider map (the skip concatenations r2m:38 are never materialised).  A pixel (n, y, x) of a slice is at
@@ -119,7 +120,83 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ u, 
   if (midi) midi[gid] = p >= threshold ? 1 : 0;
 }
 
-// geometry shared by the three entry points; `what` prefixes the message
+// ---- attention gate of Roll2MidiNet_enhance.py (enh:41-55), folded into one weight vector: one wave per pixel ------------------------
+// The pixel's C = C0 + C1 channels are the concatenation of two segments.  Lane l owns the 8 channels [512 j + 8 l, + 8) of chunk j
+// (NCH chunks, held in registers between the dot and the scaling: every element is read once).  Per lane one fma chain from 0 over
+// its channels in ascending order, then an xor butterfly (32, 16, 8, 4, 2, 1) after which every lane holds the same sum; z = sum +
+// bias.  The order depends on (C0, C1) alone.  8 channels per lane, as in leaky_shadow_kernel, so that the shadow goes out 16 bytes
+// wide through store8.
+constexpr int GATE_MAX_C = 2048;      // 4 chunks x 64 lanes x 8 channels: 32 data registers per lane
+
+template <int MODE, int NCH>
+__global__ __launch_bounds__(256) void gate_kernel(float* x0, int64_t pitch0, int C0, bf16_t* sh0, int64_t lo0, float* x1, int64_t pitch1,
+                                                   int C1, bf16_t* sh1, int64_t lo1, const float* __restrict__ w, float bias,
+                                                   int64_t total, int H, int W, int border, float* __restrict__ logits,
+                                                   float* __restrict__ alpha_out) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // one wave per pixel: uniform over the wave
+  if (t >= total) return;
+  const int lane = threadIdx.x & 63;
+  const int C = C0 + C1;
+  const int64_t px = pixel_of(t, H, W, border);
+  float v[NCH][8];
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const int c = j * 512 + lane * 8;                                    // C0 % 8 == 0: the 8 channels lie in one segment
+    if (c < C) {
+      const float* p = c < C0 ? x0 + px * pitch0 + c : x1 + px * pitch1 + (c - C0);
+      const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+      const f32x4 wa = *reinterpret_cast<const f32x4*>(w + c), wb = *reinterpret_cast<const f32x4*>(w + c + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[j][e] = a[e];
+        v[j][4 + e] = b[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = fmaf(wa[e], a[e], acc);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = fmaf(wb[e], b[e], acc);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  const float z = acc + bias;
+  const float al = 1.0f / (1.0f + expf(-z));         // libm expf, IEEE division: the parity form of head_kernel
+  if (lane == 0) {
+    if (logits) logits[t] = z;
+    if (alpha_out) alpha_out[t] = al;
+  }
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const int c = j * 512 + lane * 8;
+    if (c < C) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[j][e] *= al;      // one fp32 multiply of the stored x; store8 splits the STORED product
+      if (c < C0)
+        store8<MODE>(x0, sh0, px * pitch0 + c, lo0, v[j]);
+      else
+        store8<MODE>(x1, sh1, px * pitch1 + (c - C0), lo1, v[j]);
+    }
+  }
+}
+
+template <int MODE>
+void launch_gate(int nch, dim3 grid, hipStream_t s, float* x0, int64_t pitch0, int C0, bf16_t* sh0, int64_t lo0, float* x1, int64_t pitch1,
+                 int C1, bf16_t* sh1, int64_t lo1, const float* w, float bias, int64_t total, int H, int W, int border, float* logits,
+                 float* alpha) {
+  dim3 block(256);
+  if (nch == 1)
+    hipLaunchKernelGGL((gate_kernel<MODE, 1>), grid, block, 0, s, x0, pitch0, C0, sh0, lo0, x1, pitch1, C1, sh1, lo1, w, bias, total, H, W,
+                       border, logits, alpha);
+  else if (nch == 2)
+    hipLaunchKernelGGL((gate_kernel<MODE, 2>), grid, block, 0, s, x0, pitch0, C0, sh0, lo0, x1, pitch1, C1, sh1, lo1, w, bias, total, H, W,
+                       border, logits, alpha);
+  else
+    hipLaunchKernelGGL((gate_kernel<MODE, 4>), grid, block, 0, s, x0, pitch0, C0, sh0, lo0, x1, pitch1, C1, sh1, lo1, w, bias, total, H, W,
+                       border, logits, alpha);
+}
+
+// geometry shared by the entry points; `what` prefixes the message
 int check_slice(const char* what, const void* base, const void* shadow, int32_t mode, int64_t lo_offset, int32_t n, int32_t H, int32_t W,
                 int32_t C, int64_t pitch, int32_t border) {
   V2A_REQUIRE(base != nullptr && ((uintptr_t)base & 15) == 0, "%s: null or misaligned map pointer", what);
@@ -172,6 +249,36 @@ extern "C" int v2a_leaky_shadow(float* x, void* shadow, int32_t shadow_mode, int
   else
     hipLaunchKernelGGL(leaky_shadow_kernel<SH_SPLIT>, grid, block, 0, s, x, sh, total, H, W, C, pitch, border, lo_offset);
   return v2a_check_launch("v2a_leaky_shadow");
+}
+
+extern "C" int v2a_roll2midi_gate(float* x0, int64_t pitch0, int32_t C0, void* shadow0, int64_t lo_offset0, float* x1, int64_t pitch1,
+                                  int32_t C1, void* shadow1, int64_t lo_offset1, const float* w, float bias, int32_t shadow_mode, int32_t n,
+                                  int32_t H, int32_t W, int32_t border, float* logits, float* alpha, v2a_stream_t stream) {
+  V2A_REQUIRE(w != nullptr && ((uintptr_t)w & 15) == 0, "v2a_roll2midi_gate: null or misaligned weight vector");
+  V2A_REQUIRE(C1 >= 0, "v2a_roll2midi_gate: bad geometry (C1=%d)", C1);
+  if (int rc = check_slice("v2a_roll2midi_gate", x0, shadow0, shadow_mode, lo_offset0, n, H, W, C0, pitch0, border)) return rc;
+  if (C1 > 0) {
+    if (int rc = check_slice("v2a_roll2midi_gate (second segment)", x1, shadow1, shadow_mode, lo_offset1, n, H, W, C1, pitch1, border)) return rc;
+  } else {
+    V2A_REQUIRE(x1 == nullptr && shadow1 == nullptr && lo_offset1 == 0, "v2a_roll2midi_gate: C1 = 0 takes no second segment");
+  }
+  V2A_REQUIRE((int64_t)C0 + C1 <= GATE_MAX_C, "v2a_roll2midi_gate: C0 + C1 = %lld channels, one wave holds at most %d in registers (4 chunks of 64 lanes x 8)",
+              (long long)C0 + C1, GATE_MAX_C);
+  V2A_REQUIRE(((uintptr_t)logits & 3) == 0 && ((uintptr_t)alpha & 3) == 0, "v2a_roll2midi_gate: misaligned logits / alpha");
+  const int64_t total = (int64_t)n * H * W;
+  V2A_REQUIRE((total + 3) / 4 < 0x7fffffffLL, "v2a_roll2midi_gate: too many pixels for one launch");
+  const int C = C0 + C1;
+  const int nch = C <= 512 ? 1 : (C <= 1024 ? 2 : 4);
+  dim3 grid((unsigned)((total + 3) / 4));
+  hipStream_t s = (hipStream_t)stream;
+  bf16_t *s0 = (bf16_t*)shadow0, *s1 = (bf16_t*)shadow1;
+  if (shadow_mode == SH_NONE)
+    launch_gate<SH_NONE>(nch, grid, s, x0, pitch0, C0, s0, lo_offset0, x1, pitch1, C1, s1, lo_offset1, w, bias, total, H, W, border, logits, alpha);
+  else if (shadow_mode == SH_BF16)
+    launch_gate<SH_BF16>(nch, grid, s, x0, pitch0, C0, s0, lo_offset0, x1, pitch1, C1, s1, lo_offset1, w, bias, total, H, W, border, logits, alpha);
+  else
+    launch_gate<SH_SPLIT>(nch, grid, s, x0, pitch0, C0, s0, lo_offset0, x1, pitch1, C1, s1, lo_offset1, w, bias, total, H, W, border, logits, alpha);
+  return v2a_check_launch("v2a_roll2midi_gate");
 }
 
 extern "C" int v2a_roll2midi_head(const float* u, int64_t u_pitch, int32_t nu, const float* d, int64_t d_pitch, int32_t nd, const float* w,

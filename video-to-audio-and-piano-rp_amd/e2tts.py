@@ -354,18 +354,20 @@ class E2TTS:
         return self._v2r
 
     def load_roll2midi(self, src, **kw):
-        """The Roll2Midi generator behind `frames_to_midi` (src/audeo/Roll2MidiNet.py, run as in Roll2Midi_inference.py): a
-        `Roll2MidiEngine`, a state dict in the layout of the reference's `checkpoint['state_dict_G']`, a checkpoint dict holding
-        `state_dict_G`, or a path to a torch-saved one of either.  `kw` go to the engine's constructor (compute, chunk)."""
-        from .roll2midi import Roll2MidiEngine
-        if isinstance(src, Roll2MidiEngine):
+        """The Roll2Midi generator behind `frames_to_midi`, run as in Roll2Midi_inference.py: the plain net of src/audeo/Roll2MidiNet.py
+        or the attention-gated one of Roll2MidiNet_enhance.py (what Roll2Midi_train.py writes), told apart by the state dict's keys
+        (`roll2midi.engine_for`).  src: a `Roll2MidiEngine` or `Roll2MidiEnhanceEngine`, a state dict in the layout of the reference's
+        `checkpoint['state_dict_G']`, a checkpoint dict holding `state_dict_G`, or a path to a torch-saved one of either.  `kw` go to
+        the engine's constructor (compute, chunk)."""
+        from .roll2midi import Roll2MidiEngine, engine_for
+        if isinstance(src, Roll2MidiEngine):                      # the enhanced engine is a subclass
             self._r2m = src
             return src
         if isinstance(src, (str, Path)):
             src = torch.load(str(src), map_location="cpu")
         if not isinstance(src, dict):
             raise TypeError(f"load_roll2midi: a Roll2MidiEngine, a state dict, a checkpoint dict or a path, got {type(src).__name__}")
-        self._r2m = Roll2MidiEngine(src.get("state_dict_G", src), self._device, **kw)
+        self._r2m = engine_for(src.get("state_dict_G", src), self._device, **kw)
         return self._r2m
 
     def frames_to_midi(self, frames, window: int = 100, threshold: float = 0.5, tail: str = "own"):

@@ -15,6 +15,9 @@ Design (not a translation of the reference's NCHW module tree):
   * three row kernels complete it (csrc/roll2midi.hip): `v2a_roll2midi_stem` (down1: K = 9 fills no K tile), `v2a_leaky_shadow`
     (LeakyReLU(0.2), which the GEMM epilogue lacks, + the bf16 / hi | lo copy the next GEMM reads) and `v2a_roll2midi_head`
     (conv1d 80 -> 1 + sigmoid + threshold).
+`Roll2MidiEnhanceEngine` is the attention-gated generator of src/audeo/Roll2MidiNet_enhance.py (`enh`), the one the reference's trainer
+and evaluator import: the same walk over wider up blocks, with a fourth row kernel, `v2a_roll2midi_gate`, behind up1..up4 (`folded_gate`).
+`engine_for` picks the class from a state dict's keys.
 The BatchNorm fold, the weight packing, the bordered maps with their channel slices and the offset tables are conv2d.py's, shared with
 video2roll.py.  There is no CPU fallback: without libv2a_cfm.so every call raises.
 """
@@ -32,6 +35,8 @@ LEAKY = 0.2
 _DOWN = ((1, 64), (64, 128), (128, 256), (256, 512), (512, 1024), (1024, 1024))             # down1..down6: (ci, co)   r2m:46-51
 _UP = ((1024, 512), (1024 + 512, 256), (512 + 256, 128), (256 + 128, 64), (128 + 64, 16))   # up1..up5: (ci, co)       r2m:53-57
 UP5_PAD = 64                # up5's 16 output channels as a GEMM of 64 (zero weight rows): the head reads the first 16
+_UP_ENH = ((1024, 1024), (1024 + 1024, 512), (512 + 512, 256), (256 + 256, 128), (128 + 128, 64))      # up1..up5 of enh:74-78
+_GATES = ((2048, 1024, 512), (1024, 512, 256), (512, 256, 128), (256, 128, 64))    # att1..att4: (in, g, out) channels   enh:69-72
 
 
 def expected_state_dict_shapes() -> dict[str, tuple]:
@@ -55,11 +60,49 @@ def expected_state_dict_shapes() -> dict[str, tuple]:
     return s
 
 
+def expected_enhance_state_dict_shapes() -> dict[str, tuple]:
+    """Key layout of `Roll2MidiNet_enhance.Generator((1, 51, 100)).state_dict()`, in the module's own order (the gates are registered
+    between the down and the up blocks, enh:61-79)."""
+    plain = expected_state_dict_shapes()
+    s = {k: v for k, v in plain.items() if k.startswith("down")}
+    for i, (c, cg, co) in enumerate(_GATES, 1):
+        for name, shp in (("theta_x", (co, c, 1, 1)), ("phi_g", (co, cg, 1, 1)), ("psi", (1, co, 1, 1))):
+            s[f"att{i}.{name}.weight"] = shp
+            s[f"att{i}.{name}.bias"] = (shp[0],)
+    for i, (ci, co) in enumerate(_UP_ENH, 1):
+        s[f"up{i}.model.0.weight"] = (ci, co, 3, 3)
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            s[f"up{i}.model.1.{k}"] = (co,)
+        s[f"up{i}.model.1.num_batches_tracked"] = ()
+    s["conv1d.weight"] = (1, 128, 1, 1)
+    s["conv1d.bias"] = (1,)
+    return s
+
+
 def check_state_dict(sd: dict) -> None:
     if any(k.startswith("att") for k in sd):
         raise NotImplementedError("Roll2MidiEngine: the state dict holds attention gates (att1.* ...): that is Roll2MidiNet_enhance.py, "
-                                  "which has no HIP path; only the plain Generator of Roll2MidiNet.py is built")
+                                  "which Roll2MidiEnhanceEngine runs (roll2midi.engine_for picks the class); this class is the plain "
+                                  "Generator of Roll2MidiNet.py")
     conv2d.check_state_dict(sd, expected_state_dict_shapes(), "Roll2MidiEngine")
+
+
+def check_enhance_state_dict(sd: dict) -> None:
+    conv2d.check_state_dict(sd, expected_enhance_state_dict_shapes(), "Roll2MidiEnhanceEngine")
+
+
+def folded_gate(sd: dict, k: int) -> tuple[torch.Tensor, float]:
+    """Gate att{k} (`AttentionGate.forward`, enh:49-55) as one weight vector: there is no nonlinearity between theta_x + phi_g and psi,
+    and the gate input g = d_(6-k) is the last Cg channels of x = u_k, so per pixel
+        psi(theta_x(x) + phi_g(g)) = w . x + b,   w = psi_w theta_w + [0 ... 0 | psi_w phi_w],   b = psi_w . (theta_b + phi_b) + psi_b.
+    Computed in float64 and rounded once: (w fp32 (C,), b as a Python float)."""
+    g = lambda name: sd[f"att{k}.{name}"].double()
+    psi = g("psi.weight").reshape(-1)                                       # (Co,)
+    theta, phi = g("theta_x.weight").flatten(1), g("phi_g.weight").flatten(1)      # (Co, C), (Co, Cg)
+    w = psi @ theta
+    w[theta.shape[1] - phi.shape[1]:] += psi @ phi
+    b = psi @ (g("theta_x.bias") + g("phi_g.bias")) + g("psi.bias").reshape(())
+    return w.float().contiguous(), float(b)
 
 
 def transposed_conv_weight(w: torch.Tensor) -> torch.Tensor:
@@ -94,6 +137,10 @@ class Roll2MidiEngine:
     plus 44 / 87 MB of shadows) and 2 in fp32 mode (the patch matrices of up2, K = 13 824, take 282 MB per window).  A window's
     output does not depend on the chunk it ran in."""
 
+    _UPS, _PAD = _UP, UP5_PAD                # (ci, co) of up1..up5; the GEMM width a narrower up block is padded to
+    _FP32_CHUNK = 2
+    _check = staticmethod(check_state_dict)
+
     def __init__(self, sd, device="cuda:0", compute="bf16x3", prefix="", chunk=None):
         L.lib()                                                   # fail loudly without the HIP library
         if compute not in ("bf16", "bf16x3", "fp32"):
@@ -104,9 +151,9 @@ class Roll2MidiEngine:
         self.implicit = compute != "fp32"
         self.code = L.F32 if compute == "fp32" else L.BF16
         self.mode = L.SH_NONE if compute == "fp32" else (L.SH_SPLIT if self.split else L.SH_BF16)
-        self.chunk = int(chunk) if chunk else (8 if self.implicit else 2)
+        self.chunk = int(chunk) if chunk else (8 if self.implicit else self._FP32_CHUNK)
         sd = {k[len(prefix):]: v.detach().cpu() for k, v in sd.items() if k.startswith(prefix)}
-        check_state_dict(sd)
+        self._check(sd)
         dev = self.dev
         self.w, self.bias = {}, {}
         for name, segs, pad in self._layers():
@@ -117,17 +164,21 @@ class Roll2MidiEngine:
             self.w[name] = (L.split_planes(wk) if self.split else wk.to(torch.bfloat16 if self.implicit else torch.float32)).to(dev).contiguous()
             self.bias[name] = None if b is None else b.to(dev).contiguous()
         self.stem_wt = folded_conv(sd, "down1")[0].reshape(64, 9).t().contiguous().to(dev)        # [tap][co]
-        self.head_w = sd["conv1d.weight"].float().reshape(80).contiguous().to(dev)
+        self.head_w = sd["conv1d.weight"].float().reshape(-1).contiguous().to(dev)
         self.head_b = float(sd["conv1d.bias"].float()[0])
         self.mem = ConvMemory(dev, self.split)              # activation maps, offset tables, patch-matrix scratch
+        self._load_more(sd)
 
-    @staticmethod
-    def _layers():
+    def _load_more(self, sd):
+        """What a subclass keeps of the state dict besides the convolutions."""
+
+    @classmethod
+    def _layers(cls):
         """(block, widths of the concatenated inputs, padded output width) of the convolutions that run as GEMMs."""
         out = [(f"down{i}", (ci,), 0) for i, (ci, _) in enumerate(_DOWN, 1) if i > 1]
-        skips = (0, 1024, 512, 256, 128)                            # d5, d4, d3, d2 behind up1..up4's outputs (r2m:74-82)
-        for i, (ci, co) in enumerate(_UP, 1):
-            out.append((f"up{i}", (ci,) if i == 1 else (ci - skips[i - 1], skips[i - 1]), UP5_PAD if co < 64 else 0))
+        for i, (ci, co) in enumerate(cls._UPS, 1):
+            skip = 0 if i == 1 else _DOWN[6 - i][1]                 # d5, d4, d3, d2 behind up1..up4's outputs (r2m:74-82)
+            out.append((f"up{i}", (ci,) if i == 1 else (ci - skip, skip), cls._PAD if co < cls._PAD else 0))
         return out
 
     # ---- buffers ------------------------------------------------------------------------------------
@@ -138,28 +189,31 @@ class Roll2MidiEngine:
         m = {}
         if self.implicit:
             # concatenated maps [p_k | d_(6-k)]: r2m:38 without the copy
-            for k, (cu, cd) in enumerate(((512, 1024), (256, 512), (128, 256), (64, 128), (UP5_PAD, 64)), 1):
+            for k, (_, co) in enumerate(self._UPS, 1):
+                cu, cd = max(co, self._PAD), _DOWN[5 - k][1]
                 m[f"u{k}"] = u = new(f"u{k}", cu + cd)
                 m[f"p{k}"], m[f"d{6 - k}"] = u.slice(0, cu), u.slice(cu, cd)
             m["d6"] = new("d6", 1024)
         else:
             for k, (_, co) in enumerate(_DOWN, 1):
                 m[f"d{k}"] = new(f"d{k}", co)
-            for k, (_, co) in enumerate(_UP, 1):
-                m[f"p{k}"] = new(f"p{k}", max(co, UP5_PAD))
+            for k, (_, co) in enumerate(self._UPS, 1):
+                m[f"p{k}"] = new(f"p{k}", max(co, self._PAD))
         return m
 
     # ---- one convolution ----------------------------------------------------------------------------
-    def _conv(self, name, srcs, dst, n, H, W, *, relu):
-        """srcs: the slices whose concatenation the convolution reads (implicit GEMM: ONE slice of a concatenated map)."""
+    def _conv(self, name, srcs, dst, n, H, W, *, relu, shadow=None):
+        """srcs: the slices whose concatenation the convolution reads (implicit GEMM: ONE slice of a concatenated map).  shadow: whether
+        the GEMM epilogue writes dst's shadow (default: behind a ReLU, where nothing else follows)."""
+        shadow = relu if shadow is None else shadow
         w, bias, rows, N = self.w[name], self.bias[name], n * H * W, self.w[name].shape[0]
         assert N == dst.C
         if self.implicit:
             (src,) = srcs
             t = self.mem.tables(src, dst, 3, 3, 1, 1)
-            shadowed = dst if relu else None                  # down blocks: v2a_leaky_shadow writes the shadow after the activation
+            shadowed = dst if shadow else None                # down blocks: v2a_leaky_shadow writes the shadow after the activation
             L.gemm([src.operand(9 * src.C)], w, dst.base(), M=rows, N=N, compute=self.code,
-                   bias=bias, relu=relu, ldo=dst.pitch, out_bf16=dst.shadow() if relu else None, ld_out_bf16=dst.pitch,
+                   bias=bias, relu=relu, ldo=dst.pitch, out_bf16=dst.shadow() if shadow else None, ld_out_bf16=dst.pitch,
                    a_row_offset=t[0], a_ktile_offset=t[1], out_row_offset=t[2], **split_args(self.split, shadowed))
             return
         segs = []
@@ -252,3 +306,65 @@ class Roll2MidiEngine:
             probs[:, first:first + nw * keep] = p.transpose(1, 2)[:, :keep].reshape(b, nw * keep, keys)
             midi[:, first:first + nw * keep] = mi.transpose(1, 2)[:, :keep].reshape(b, nw * keep, keys)
         return probs, midi
+
+
+class Roll2MidiEnhanceEngine(Roll2MidiEngine):
+    """`Generator` of Roll2MidiNet_enhance.py in eval mode on HIP kernels: the checkpoint Roll2Midi_train.py writes and
+    Roll2Midi_evaluate.py reads.  Constructor, `forward`, `refine`, `chunk` and the three compute modes are `Roll2MidiEngine`'s.
+
+    The down path is the plain net's; the up blocks are wider (up1 1024 -> 1024 ... up5 256 -> 64, conv1d 128 -> 1) and an attention
+    gate follows up1..up4 (enh:95-105): u_k = cat(up_k(.), d_(6-k)), u_k <- u_k * sigmoid(psi(theta_x(u_k) + phi_g(d_(6-k)))).  The
+    three 1x1 convolutions fold into one weight vector (`folded_gate`), so a gate is one `v2a_roll2midi_gate` launch: a dot per pixel
+    over the map the next convolution reads anyway, the scaling in place, and the shadow of the whole u_k (a gated up block asks its
+    GEMM epilogue for none).  Gating d_(6-k) in place is sound: down_(7-k), its only other reader, ran before any up block.
+    chunk: default 8 in the bf16 / bf16x3 modes (the maps of a 51x100 window take 108 MB in fp32 plus 54 / 108 MB of shadows) and 2 in
+    fp32 mode: the two patch matrices of up2 (K = 18 432 over two segments) take 376 MB per window, 752 MB at the default."""
+
+    _UPS = _UP_ENH
+    _check = staticmethod(check_enhance_state_dict)
+
+    def _load_more(self, sd):
+        self.gate_w, self.gate_b = {}, {}
+        for k in range(1, 5):
+            w, b = folded_gate(sd, k)
+            self.gate_w[k], self.gate_b[k] = w.to(self.dev), b
+
+    def _gate(self, k, m, n, H, W, alpha=None):
+        """u_k <- u_k * alpha in place, with its shadow: segment 0 is up_k's output, segment 1 the skip d_(6-k) behind it."""
+        seg = lambda sl: (sl.base(), sl.pitch, sl.C, sl.shadow(), sl.lo)
+        p = m[f"p{k}"]
+        L.roll2midi_gate(seg(p), seg(m[f"d{6 - k}"]), self.gate_w[k], bias=self.gate_b[k], shadow_mode=self.mode, n=n, H=H, W=W,
+                         border=p.border, alpha=alpha)
+
+    def _pass(self, x, logits, probs, midi, threshold, taps=None):
+        n, H, W = x.shape
+        m = self._maps(n, H, W)
+        d1 = m["d1"]
+        L.roll2midi_stem(x, self.stem_wt, d1.base(), d1.shadow(), n=n, H=H, W=W, co=64, shadow_mode=self.mode,
+                         lo_offset=d1.lo, pitch=d1.pitch, border=d1.border)
+        for k in range(2, 7):                                        # enh:83-93
+            self._conv(f"down{k}", [m[f"d{k - 1}"]], m[f"d{k}"], n, H, W, relu=False)
+            self._leaky(m[f"d{k}"], n, H, W)
+        if taps is not None:                                         # the skips as the down blocks left them: the gates scale them in place
+            for k in range(1, 7):
+                taps.setdefault(f"d{k}", []).append(m[f"d{k}"].nchw().clone())
+        for k in range(1, 6):                                        # enh:95-107: up_k, then att_k over cat(up_k, d_(6-k))
+            srcs = [m["d6"]] if k == 1 else ([m[f"u{k - 1}"]] if self.implicit else [m[f"p{k - 1}"], m[f"d{7 - k}"]])
+            self._conv(f"up{k}", srcs, m[f"p{k}"], n, H, W, relu=True, shadow=k == 5)
+            if k < 5:
+                alpha = None if taps is None else torch.empty(n, H, W, device=self.dev, dtype=torch.float32)
+                self._gate(k, m, n, H, W, alpha)
+                if taps is not None:
+                    taps.setdefault(f"a{k}", []).append(alpha.unsqueeze(1))
+            if taps is not None:
+                taps.setdefault(f"u{k}", []).append(torch.cat([m[f"p{k}"].nchw(), m[f"d{6 - k}"].nchw()], 1))
+        p5 = m["p5"]
+        L.roll2midi_head(p5.base(), d1.base(), self.head_w, u_pitch=p5.pitch, nu=64, d_pitch=d1.pitch, nd=64, bias=self.head_b,
+                         threshold=threshold, n=n, H=H, W=W, border=d1.border, logits=logits, probs=probs, midi=midi)
+
+
+def engine_for(sd: dict, device="cuda:0", **kw) -> Roll2MidiEngine:
+    """The engine of a `state_dict_G`: `Roll2MidiEnhanceEngine` if it holds the attention gates (`att1.theta_x.weight`), else
+    `Roll2MidiEngine`.  kw (compute, prefix, chunk) go to the constructor."""
+    cls = Roll2MidiEnhanceEngine if kw.get("prefix", "") + "att1.theta_x.weight" in sd else Roll2MidiEngine
+    return cls(sd, device, **kw)

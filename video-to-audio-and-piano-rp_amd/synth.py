@@ -124,6 +124,41 @@ def random_roll2midi_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
     return sd
 
 
+def random_roll2midi_enhance_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `Roll2MidiNet_enhance.Generator((1, 51, 100)).state_dict()`, drawn in that order from numpy's
+    legacy RandomState (tests/golden/roll2midi_enhance.npz).  The scaling of `random_roll2midi_state_dict`; the gates' 1x1 weights
+    are N(0, (3 / sqrt(ci))^2), so the gate logits spread over about a unit and alpha is neither 0, 1 nor 0.5 everywhere, and
+    conv1d.bias = -2.0, so that about half of the thresholded cells are on (four gates shrink the maps the head reads)."""
+    import numpy as np
+
+    from .roll2midi import expected_enhance_state_dict_shapes
+
+    rs = np.random.RandomState(seed)
+    sd = {}
+    for k, shp in expected_enhance_state_dict_shapes().items():
+        if k.endswith("num_batches_tracked"):
+            v = np.array(1000, dtype=np.int64)
+        elif k.endswith("running_var"):
+            v = rs.uniform(0.5, 2.0, shp).astype(np.float32)
+        elif k.endswith("running_mean"):
+            v = (0.1 * rs.standard_normal(shp)).astype(np.float32)
+        elif k.endswith("model.1.weight"):
+            v = rs.uniform(0.8, 1.6, shp).astype(np.float32)
+        elif k == "conv1d.weight":
+            v = (rs.standard_normal(shp) * 2.0).astype(np.float32)
+        elif k == "conv1d.bias":
+            v = np.full(shp, -2.0, np.float32)
+        elif k.endswith(".bias"):
+            v = (0.1 * rs.standard_normal(shp)).astype(np.float32)
+        elif k.startswith("att"):
+            v = (rs.standard_normal(shp) * (3.0 / math.sqrt(shp[1]))).astype(np.float32)
+        else:
+            ci = shp[0] if k.startswith("up") else shp[1]
+            v = (rs.standard_normal(shp) * math.sqrt(2.0 / (9 * ci))).astype(np.float32)
+        sd[k] = torch.from_numpy(v) if v.ndim else torch.tensor(int(v))
+    return sd
+
+
 def synthetic_key_roll(b: int, t: int, keys: int = 51, seed: int = 0, logits: bool = False) -> torch.Tensor:
     """(b, t, keys) fp32 key probabilities as a Video2Roll encoder would give them: a few held notes (high) on a low, noisy floor.
     numpy RandomState and float64 arithmetic rounded once, reproducible across machines.  logits: the values in front of the sigmoid."""
