@@ -13,7 +13,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused
 mkdir -p $BUILD
 pids=()
 for f in gemm gemm_8phase rowops attention conv vocoder qproj_xattn xattn_absorbed t5 clip encodec_enc piano_frames encodec_rvq cfm_loss wave roll2midi; do
-  if [ ! -f $BUILD/$f.o ] || [ $f.hip -nt $BUILD/$f.o ] || [ v2a_common.h -nt $BUILD/$f.o ] || [ gemm_common.h -nt $BUILD/$f.o ] || [ attn_core.h -nt $BUILD/$f.o ] || [ ../../include/v2a_cfm.h -nt $BUILD/$f.o ]; then
+  if [ ! -f $BUILD/$f.o ] || [ $f.hip -nt $BUILD/$f.o ] || [ v2a_common.h -nt $BUILD/$f.o ] || [ gemm_common.h -nt $BUILD/$f.o ] || [ attn_core.h -nt $BUILD/$f.o ] || [ xattn_ring.h -nt $BUILD/$f.o ] || [ ../../include/v2a_cfm.h -nt $BUILD/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o $BUILD/$f.o &
     pids+=($!)
   fi

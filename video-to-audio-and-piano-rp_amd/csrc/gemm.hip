@@ -37,12 +37,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
   // tiles of the same M-row band, so the A band and neighbouring W panels stay in that L2.
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles_m = (p.M + BM - 1) / BM;
-  const int nwg = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_chunk_position(blockIdx.x, tiles_m * tiles_n);
   const int tm = bid / tiles_n, tn = bid % tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
 
@@ -181,18 +176,7 @@ int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
 // image linear per wave, XOR swizzle applied to the per-lane SOURCE chunk: rule 21 of the CDNA guide),
 // two K tiles stay in flight across the single raw s_barrier of each iteration (counted vmcnt),
 // and no VGPRs or ds_writes are spent on staging.
-// Wait until at most min(J, younger) of the youngest K tiles' DMAs (LPW instructions per wave each) are still outstanding:
-// the counted s_waitcnt needs an immediate, so the tail of the K loop walks down a chain of them.
-template <int J, int LPW>
-__device__ __forceinline__ void ring_wait(int younger) {
-  if constexpr (J == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    static_assert(J * LPW <= 63, "vmcnt is a 6-bit field");
-    if (younger >= J) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(J * LPW) : "memory");
-    else ring_wait<J - 1, LPW>(younger);
-  }
-}
+// (the counted wait is ring_wait of gemm_common.h; the cross-attention kernels run the 64x64 form of this ring from xattn_ring.h)
 
 // S3 (the "bf16x3" mode natively): both operands arrive as hi | lo bf16 planes (V2A_BF16_SPLIT rows of A, W rows [W_hi | W_lo]),
 // a ring stage holds the four plane tiles of a K step and every fragment pair feeds three MFMAs,
@@ -834,10 +818,6 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   p.nsw_off = a->norm_switch_offset;
   p.ssq = a->norm_ssq;
   p.ssq_ld = a->ld_norm_ssq;
-  p.rssq = a->row_ssq;
-  p.rssq_ld = a->ld_row_ssq;
-  p.rssq_parts = a->row_ssq_parts;
-  p.rnorm = sqrtf((float)a->row_norm_dim);
   if (a->norm_gamma || a->norm_ssq || a->row_ssq) {
     V2A_REQUIRE(a->compute_dtype == V2A_BF16 && (a->a_dtype == V2A_BF16 || split_in) && p.vec_epi && a->epilogue != V2A_EPI_SIGMOID && !a->out_row_offset,
                 "v2a_gemm: a folded RMSNorm needs bf16 x bf16 (or split bf16) operands, dense rows and 16-byte aligned epilogue operands");
@@ -847,12 +827,8 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
                                           a->norm_switch_offset % 4 == 0)) &&
                       (!a->norm_ssq || a->ld_norm_ssq >= a->N / 32),
                   "v2a_gemm: norm_gamma / norm_ssq go with RESID / GATE_RESID, an out_bf16 shadow and N %% 32 == 0 (N=%d)", a->N);
-    if (a->row_ssq)
-      V2A_REQUIRE(a->row_ssq_parts > 0 && a->row_ssq_parts <= 40 && a->row_norm_dim > 0 && a->ld_row_ssq >= (a->row_ssq_parts + 3) / 4 * 4 &&
-                      a->ld_row_ssq % 4 == 0 && ((uintptr_t)a->row_ssq & 15) == 0,
-                  "v2a_gemm: row_ssq needs row_ssq_parts <= 40 (%d), row_norm_dim (%d) and rows of whole float4 (zero padded)", a->row_ssq_parts,
-                  a->row_norm_dim);
   }
+  if (int rc = v2a_detail::fill_row_scale(p, a->row_ssq, a->ld_row_ssq, a->row_ssq_parts, a->row_norm_dim, "v2a_gemm")) return rc;
   p.rope = a->rope_table;
   p.rope_cols = a->rope_cols;
   p.rope_pos_off = a->rope_pos_offset;

@@ -1,5 +1,6 @@
-// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm_8phase.hip): kernel parameter block, register staging helpers
-// of the v1 kernel, the direct and the LDS-staged fused epilogues.  Everything lives in an anonymous namespace: each
+// Shared pieces of the MFMA GEMM kernels (gemm.hip, gemm_8phase.hip, and through xattn_ring.h qproj_xattn.hip and xattn_absorbed.hip): kernel
+// parameter block, XCD chunk position (all four), counted ring wait (gemm.hip and xattn_ring.h), row-scale fill and consumer, register staging
+// helpers of the v1 kernel, the direct and the LDS-staged fused epilogues.  Everything lives in an anonymous namespace: each
 // translation unit gets its own copy.
 #pragma once
 #include "v2a_common.h"
@@ -115,6 +116,20 @@ inline void fill_tile_map(GemmParams& p, int BM, int BN) {
   }
 }
 
+// host: the consumer side of a folded RMSNorm (row_ssq .. row_norm_dim of v2a_gemm_args and v2a_xattn_absorbed_args) into the parameter
+// block, with what rowscale_load needs of it.  who = the entry point that refuses.
+inline int fill_row_scale(GemmParams& p, const float* row_ssq, int64_t ld_row_ssq, int row_ssq_parts, int row_norm_dim, const char* who) {
+  p.rssq = row_ssq;
+  p.rssq_ld = ld_row_ssq;
+  p.rssq_parts = row_ssq_parts;
+  p.rnorm = sqrtf((float)row_norm_dim);
+  if (row_ssq)
+    V2A_REQUIRE(row_ssq_parts > 0 && row_ssq_parts <= 40 && row_norm_dim > 0 && ld_row_ssq >= (row_ssq_parts + 3) / 4 * 4 && ld_row_ssq % 4 == 0 &&
+                    ((uintptr_t)row_ssq & 15) == 0,
+                "%s: row_ssq needs row_ssq_parts <= 40 (%d), row_norm_dim (%d) and rows of whole float4 (zero padded)", who, row_ssq_parts, row_norm_dim);
+  return V2A_OK;
+}
+
 }  // namespace v2a_detail
 
 namespace {
@@ -149,11 +164,26 @@ __device__ __forceinline__ void tile_of_index(const GemmParams& p, int L, int& t
     }
   }
 }
-__device__ __forceinline__ void tile_of_block(const GemmParams& p, int bid, int& tm, int& tn) {
-  const int nwg = p.tiles_m * p.tiles_n;
+// workgroup bid of nwg -> position in a linear order of the launch's work: XCD x (bid & 7) takes the x-th contiguous chunk.  Bijective.
+__device__ __forceinline__ int xcd_chunk_position(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);      // bijective: position in the linear order
-  tile_of_index(p, L, tm, tn);
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+__device__ __forceinline__ void tile_of_block(const GemmParams& p, int bid, int& tm, int& tn) {
+  tile_of_index(p, xcd_chunk_position(bid, p.tiles_m * p.tiles_n), tm, tn);
+}
+
+// LDS-DMA rings: wait until at most min(J, younger) of the youngest K tiles' DMAs (LPW instructions per wave each) are still outstanding.
+// The counted s_waitcnt needs an immediate, so the tail of the K loop walks down a chain of them.
+template <int J, int LPW>
+__device__ __forceinline__ void ring_wait(int younger) {
+  if constexpr (J == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    static_assert(J * LPW <= 63, "vmcnt is a 6-bit field");
+    if (younger >= J) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(J * LPW) : "memory");
+    else ring_wait<J - 1, LPW>(younger);
+  }
 }
 
 // the gated-linear-unit epilogues share the [16 value | 16 gate] row packing and the N / 2 output columns; they differ in the gate's activation

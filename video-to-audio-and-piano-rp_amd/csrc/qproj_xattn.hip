@@ -5,7 +5,7 @@
 //
 // A workgroup = 64 consecutive tokens of ONE sequence x ONE head (64 q columns): 4 waves, each 16 tokens x all 64 head
 // dimensions, so everything after the K loop is wave-private except the shared K / V tile.
-//   K loop     the 64x64 LDS-DMA ring of gemm.hip (3 stages, counted vmcnt, one barrier per K tile), wave tile 16x64, plus ONE
+//   K loop     the 64x64 LDS-DMA ring of xattn_ring.h (3 stages, counted vmcnt, one barrier per K tile), wave tile 16x64, plus ONE
 //              extra MFMA per 32-k step for the head's gate logit: the gate row of W (row H*64 + h) is preloaded into LDS
 //              (2 KB, by LDS-DMA ahead of the ring) and read as a B fragment whose 16 columns all hold that row -- the
 //              accumulator then carries the logit of each of the wave's 16 tokens with the arithmetic of the plain GEMM.
@@ -16,11 +16,11 @@
 //              of attention.hip call -- attn_weights, attn_pack_weights, attn_vt_frag, attn_out_factor, attn_store -- and 8-byte
 //              stores of O * sigmoid(gate) / l.
 // Results equal the two-launch path bit for bit (tests/test_kernels_gpu.py::test_qproj_xattn_equals_two_launches).
-// S3 = the bf16x3 mode's arithmetic: hi | lo bf16 planes of A, W, q, K, V and P, three MFMAs per product (the split ring of gemm.hip;
-// split8, the three-product order and attn_store_split of attn_mfma_split_kernel), fp32 K / V rows and gate logit, output rows as
-// hi | lo planes for the out-projection's split GEMM.
+// S3 = the bf16x3 mode's arithmetic: hi | lo bf16 planes of A, W, q, K, V and P, three MFMAs per product (XattnRing<true>, in the
+// product order of gemm.hip's split ring; split8, the three-product order and attn_store_split of attn_mfma_split_kernel), fp32 K / V
+// rows and gate logit, output rows as hi | lo planes for the out-projection's split GEMM.
 #include "attn_core.h"
-#include "gemm_common.h"
+#include "xattn_ring.h"
 
 namespace {
 
@@ -36,28 +36,15 @@ struct QxParams {
   int32_t H, Nk, tiles_per_seq, nseq;
 };
 
-template <int J, int LPW>
-__device__ __forceinline__ void qx_ring_wait(int younger) {
-  if constexpr (J == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    if (younger >= J) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(J * LPW) : "memory");
-    else qx_ring_wait<J - 1, LPW>(younger);
-  }
-}
-
 template <int CLAMP, bool S3>
 __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
-  constexpr int BM = 64, BN = 64, NW = 4, NST = 3, TN = 4;
-  constexpr int PLANE_BYTES = (BM + BN) * 128;
-  constexpr int STAGE_BYTES = PLANE_BYTES * (S3 ? 2 : 1);     // S3: [A_hi | W_hi | A_lo | W_lo]
-  constexpr int GA = BM / 8;
-  constexpr int LPW = 4;                        // DMA instructions per wave per K tile and plane: groups wave, wave+4 (A), wave+8, wave+12 (W)
+  using Ring = XattnRing<S3>;
+  constexpr int BM = Ring::BM, BN = Ring::BN, NW = Ring::NW, TN = Ring::TN;
   constexpr int SLAB = 16 * (BN + 4) * 4;       // bytes of a wave's fp32 staging slab
   constexpr int TILE = 64 * 128;                // one bf16 64x64 tile
-  constexpr int NPL = S3 ? 2 : 1;               // planes of q, K and V
+  constexpr int NPL = Ring::NPL;                // planes of q, K and V
   constexpr int Q_OFF = NW * SLAB, K_OFF = Q_OFF + NPL * TILE, V_OFF = K_OFF + NPL * TILE, G_OFF = V_OFF + NPL * TILE;
-  static_assert(G_OFF + 64 * 4 <= NST * STAGE_BYTES, "post-loop regions alias the ring");
+  static_assert(G_OFF + 64 * 4 <= Ring::RING_BYTES, "post-loop regions alias the ring");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const GemmParams& p = P.g;
 
@@ -69,14 +56,8 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
   // workgroup -> (row tile, head): XCD x (blockIdx & 7) takes a contiguous chunk of the row-tile-fastest order, i.e. ~2 heads'
   // W panels and every A panel (3.7 MB for one clip) per L2
   const int tiles_m = P.nseq * P.tiles_per_seq;
-  int tm, h;
-  {
-    const int nwg = tiles_m * P.H;
-    const int q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-    const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + ((int)blockIdx.x >> 3);
-    h = L / tiles_m;
-    tm = L - h * tiles_m;
-  }
+  const int L = xcd_chunk_position(blockIdx.x, tiles_m * P.H);
+  const int h = L / tiles_m, tm = L - h * tiles_m;
   const int b = tm / P.tiles_per_seq, t = tm - b * P.tiles_per_seq;
   const int rpb = p.rpb;
   const int m0 = b * rpb + t * BM;              // first row of the tile; rows of the tile beyond the sequence are clamped / dropped
@@ -109,48 +90,11 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
 #pragma unroll
   for (int j = 0; j < TN; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // ---- LDS-DMA source geometry (gemm.hip): lane -> (row of the 8-row group, physical 16-B chunk), swizzle on the SOURCE chunk
-  const int srow = lane >> 3;
-  const int schunk = ((lane & 7) ^ srow) << 3;
-  uint32_t goff[LPW];
-#pragma unroll
-  for (int i = 0; i < LPW; ++i) {
-    const int g = wave + i * NW;
-    if (g < GA) {
-      int r = m0 + g * 8 + srow;
-      r = r < m_end ? r : m_end - 1;
-      goff[i] = (uint32_t)(((int64_t)r * p.lda[0] + schunk) * 2);
-    } else {
-      const int r = n0 + (g - GA) * 8 + srow;                   // always a q row: n0 + 63 < H * 64
-      goff[i] = (uint32_t)(((int64_t)r * p.ldw + schunk) * 2);
-    }
-  }
-  const char* a_run = reinterpret_cast<const char*>(p.a[0]);
-  const char* w_run = reinterpret_cast<const char*>(p.w);
-  const int64_t lo_bytes = (int64_t)p.K * 2;
-  auto issue = [&](int stage) {
-    char* st = smem_raw + stage * STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < LPW; ++i) {
-      const int g = wave + i * NW;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((g < GA ? a_run : w_run) + goff[i]),
-                                       (__attribute__((address_space(3))) void*)(st + g * 1024), 16, 0, 0);
-    }
-    if constexpr (S3) {          // the lo planes: same rows, K elements further in the A row and in the W row
-#pragma unroll
-      for (int i = 0; i < LPW; ++i) {
-        const int g = wave + i * NW;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((g < GA ? a_run : w_run) + lo_bytes + goff[i]),
-                                         (__attribute__((address_space(3))) void*)(st + PLANE_BYTES + g * 1024), 16, 0, 0);
-      }
-    }
-    a_run += 128;
-    w_run += 128;
-  };
+  Ring ring(smem_raw, p, p.w, m0, m_end, n0, wave, lane);          // W rows n0 .. n0 + 63 are q rows: n0 + 63 < H * 64
 
   // ---- the head's gate row of W, linear in LDS behind the ring: K * 2 bytes = K / 512 wave-instructions.  Issued ahead of the
   // ring's DMAs, so every counted wait of the K loop retires them first.
-  char* gate_lds = smem_raw + NST * STAGE_BYTES;
+  char* gate_lds = smem_raw + Ring::RING_BYTES;
   {
     // S3: the row is [W_hi | W_lo], 2 K contiguous elements: the same linear copy, twice as long
     const char* gsrc = reinterpret_cast<const char*>(p.w) + ((int64_t)(P.H * 64 + h) * p.ldw) * 2 + lane * 16;
@@ -159,50 +103,31 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc + i * 1024),
                                        (__attribute__((address_space(3))) void*)(gate_lds + i * 1024), 16, 0, 0);
   }
-  // folded RMSNorm (consumer): one thread per tile row
+  // folded RMSNorm (consumer): the rows' scales, behind the gate row
   float* rs_lds = reinterpret_cast<float*>(gate_lds + p.K * 2 * NPL);
   const bool scaled = p.rssq != nullptr;
-  RowScaleLoad rsl;
-  if (scaled && tid < BM) rowscale_load(p, min(m0 + tid, m_end - 1), rsl);
-  const int nk = p.K / 64;
-#pragma unroll
-  for (int s0 = 0; s0 < NST - 1; ++s0)
-    if (s0 < nk) issue(s0);
-  if (scaled && tid < BM) rs_lds[tid] = rowscale_finish(p, rsl);
+  ring.start(p, scaled, m0, m_end, tid, rs_lds);
 
-  auto tile = [&](auto stage_c, int kt) {
-    constexpr int STAGE = decltype(stage_c)::value;
-    qx_ring_wait<NST - 2, LPW * NPL>(nk - 1 - kt);
-    __builtin_amdgcn_s_barrier();
-    const bf16_t* As = reinterpret_cast<const bf16_t*>(smem_raw + STAGE * STAGE_BYTES);
-    const bf16_t* Ws = As + BM * 64;
+  // one K tile: hi fragments, (S3) lo fragments, the next tile's DMAs, then the products
+  ring.k_loop([&](auto stage, int kt) {
     bf16x8 af[2], bf[2][TN], gf[2];
-    const int row = wave * 16 + lr;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      af[kk] = *reinterpret_cast<const bf16x8*>(As + row * 64 + (((kk * 4 + lq) ^ (row & 7)) << 3));
+      af[kk] = ring.a_frag(stage, 0, kk);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int wrow = j * 16 + lr;
-        bf[kk][j] = *reinterpret_cast<const bf16x8*>(Ws + wrow * 64 + (((kk * 4 + lq) ^ (wrow & 7)) << 3));
-      }
+      for (int j = 0; j < TN; ++j) bf[kk][j] = ring.w_frag(stage, 0, kk, j);
       gf[kk] = *reinterpret_cast<const bf16x8*>(gate_lds + (kt * 64 + kk * 32 + lq * 8) * 2);     // the same row for all 16 columns
     }
     if constexpr (S3) {
-      const bf16_t* Al = As + PLANE_BYTES / 2;
-      const bf16_t* Wl = Al + BM * 64;
       bf16x8 afl[2], bfl[2][TN], gfl[2];
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        afl[kk] = *reinterpret_cast<const bf16x8*>(Al + row * 64 + (((kk * 4 + lq) ^ (row & 7)) << 3));
+        afl[kk] = ring.a_frag(stage, 1, kk);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int wrow = j * 16 + lr;
-          bfl[kk][j] = *reinterpret_cast<const bf16x8*>(Wl + wrow * 64 + (((kk * 4 + lq) ^ (wrow & 7)) << 3));
-        }
+        for (int j = 0; j < TN; ++j) bfl[kk][j] = ring.w_frag(stage, 1, kk, j);
         gfl[kk] = *reinterpret_cast<const bf16x8*>(gate_lds + (p.K + kt * 64 + kk * 32 + lq * 8) * 2);
       }
-      if (kt + NST - 1 < nk) issue((STAGE + NST - 1) % NST);
+      ring.refill(stage, kt);
       // three products per fragment pair, small terms first (the order of gemm_bf16_dma_kernel<.., S3>)
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
@@ -217,7 +142,7 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
         accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kk], gf[kk], accg, 0, 0, 0);
       }
     } else {
-      if (kt + NST - 1 < nk) issue((STAGE + NST - 1) % NST);
+      ring.refill(stage, kt);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
@@ -225,13 +150,8 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
         accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kk], gf[kk], accg, 0, 0, 0);
       }
     }
-  };
-  for (int kt = 0; kt < nk; kt += NST) {
-    tile(std::integral_constant<int, 0>{}, kt);
-    if (kt + 1 < nk) tile(std::integral_constant<int, 1>{}, kt + 1);
-    if (kt + 2 < nk) tile(std::integral_constant<int, 2>{}, kt + 2);
-  }
-  __builtin_amdgcn_s_barrier();       // every wave is done reading the ring; all DMAs were retired by the last counted wait
+  });
+  __builtin_amdgcn_s_barrier();      // every wave is done reading the ring; all DMAs were retired by the last counted wait
 
   // ---- K / V tiles into the dead ring (row-major [key][64], 16-B chunk XOR-swizzled by key & 7, as in attn_mfma_kernel)
   bf16_t* ks = reinterpret_cast<bf16_t*>(smem_raw + K_OFF);      // S3: hi plane, the lo plane one tile further
@@ -368,16 +288,9 @@ __global__ __launch_bounds__(256) void qproj_xattn_kernel(QxParams P) {
 
 template <int CLAMP, bool S3>
 int launch_qx(const QxParams& P, hipStream_t s) {
-  const size_t smem = 3 * (size_t)(64 + 64) * 128 * (S3 ? 2 : 1) + (size_t)P.g.K * 2 * (S3 ? 2 : 1) + 64 * 4;
-  // the dynamic LDS size depends on K (the preloaded gate row) while the opt-in above 64 KB is set ONCE per (kernel, device): it is set
-  // for the largest K the entry point accepts (4096), so a later launch with a larger K than the first one is not refused
-  constexpr size_t smem_max = 3 * (size_t)(64 + 64) * 128 * (S3 ? 2 : 1) + (size_t)4096 * 2 * (S3 ? 2 : 1) + 64 * 4;
-  static_assert(smem_max <= 160 * 1024, "qproj_xattn: LDS");
-  auto kern = qproj_xattn_kernel<CLAMP, S3>;
+  constexpr size_t row = 2 * (S3 ? 2 : 1);       // bytes of the gate row per k; the entry point accepts K <= 4096
   static std::atomic<uint64_t> lds_set{0};
-  if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(kern), smem_max, lds_set, "v2a_qproj_xattn")) return rc;
-  hipLaunchKernelGGL(kern, dim3(P.nseq * P.tiles_per_seq * P.H), dim3(256), smem, s, P);
-  return v2a_check_launch("v2a_qproj_xattn");
+  return xattn_ring_launch<S3, 4096 * row>(qproj_xattn_kernel<CLAMP, S3>, P, P.nseq * P.tiles_per_seq * P.H, P.g.K * row, lds_set, "v2a_qproj_xattn", s);
 }
 
 }  // namespace
@@ -408,30 +321,13 @@ extern "C" int v2a_qproj_xattn(const v2a_gemm_args* a, const v2a_attn_args* at, 
               "v2a_qproj_xattn: k / v head slices must be 16-byte aligned, out rows 8-byte aligned (split: 2 * H * 64 bf16 per row)");
   QxParams P{};
   GemmParams& p = P.g;
-  p.a[0] = a->a[0];
-  p.lda[0] = a->lda[0];
-  p.kend[0] = K;
-  p.nseg = 1;
-  p.w = a->w;
-  p.ldw = a->ldw;
-  p.bias = a->bias;
-  p.M = a->M;
-  p.N = at->H * 64;
-  p.K = K;
-  p.rpb = a->rows_per_batch;
+  xattn_ring_params(p, a->a[0], a->lda[0], a->w, a->ldw, a->bias, a->M, at->H * 64, K, a->rows_per_batch);
   p.rope = a->rope_table;
   p.rope_cols = a->rope_cols;
   p.rope_pos_off = a->rope_pos_offset;
   if (a->rope_table)
     V2A_REQUIRE(a->rope_cols % 64 == 0 && a->rope_cols <= at->H * 64 && ((uintptr_t)a->rope_table & 15) == 0, "v2a_qproj_xattn: rope_cols %d", a->rope_cols);
-  p.rssq = a->row_ssq;
-  p.rssq_ld = a->ld_row_ssq;
-  p.rssq_parts = a->row_ssq_parts;
-  p.rnorm = sqrtf((float)a->row_norm_dim);
-  if (a->row_ssq)
-    V2A_REQUIRE(a->row_ssq_parts > 0 && a->row_ssq_parts <= 40 && a->row_norm_dim > 0 && a->ld_row_ssq >= (a->row_ssq_parts + 3) / 4 * 4 &&
-                    a->ld_row_ssq % 4 == 0 && ((uintptr_t)a->row_ssq & 15) == 0,
-                "v2a_qproj_xattn: row_ssq needs row_ssq_parts <= 40 (%d), row_norm_dim (%d) and rows of whole float4", a->row_ssq_parts, a->row_norm_dim);
+  if (int rc = v2a_detail::fill_row_scale(p, a->row_ssq, a->ld_row_ssq, a->row_ssq_parts, a->row_norm_dim, "v2a_qproj_xattn")) return rc;
   P.k = at->k;
   P.v = at->v;
   P.out = reinterpret_cast<bf16_t*>(at->out);

@@ -12,13 +12,13 @@
 // slots nc .. KP-1 are zero rows / columns of the operands and masked like every slot >= kv_len[b].
 //
 // xattn_absorbed_kernel: a workgroup = 64 consecutive rows of ONE clip x 64 rows of Wqk = 64 / KP whole heads, with the gate rows of
-// those heads: 4 waves, each 16 rows x all 64 columns.  K loop: the 64x64 split LDS-DMA ring of qproj_xattn.hip / gemm.hip (3 stages,
+// those heads: 4 waves, each 16 rows x all 64 columns.  K loop: the 64x64 split LDS-DMA ring of xattn_ring.h, XattnRing<true> (3 stages,
 // counted vmcnt, one barrier per K tile; per 32 k three products A_lo W_hi + A_hi W_lo + A_hi W_hi), the product SWAPPED (W rows are the
 // MFMA's rows, the token sits on the lane) so that the accumulators have the layout attn_weights of attn_core.h works on; plus one
 // product per 32 k for the gate logits: the gate rows of the heads are preloaded into LDS by DMA ahead of the ring and read as a
 // fragment whose row r is the gate row of head r % (64 / KP).  After the loop everything is lane-private: no LDS, no barrier.
 #include "attn_core.h"
-#include "gemm_common.h"
+#include "xattn_ring.h"
 
 namespace {
 
@@ -33,25 +33,12 @@ struct XaParams {
   int32_t H, tiles_per_seq, nseq;
 };
 
-template <int J, int LPW>
-__device__ __forceinline__ void xa_ring_wait(int younger) {
-  if constexpr (J == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else {
-    if (younger >= J) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(J * LPW) : "memory");
-    else xa_ring_wait<J - 1, LPW>(younger);
-  }
-}
-
 template <int CLAMP, int KP>
 __global__ __launch_bounds__(256) void xattn_absorbed_kernel(XaParams P) {
-  constexpr int BM = 64, BN = 64, NW = 4, NST = 3, TN = 4;
+  using Ring = XattnRing<true>;
+  constexpr int BM = Ring::BM, BN = Ring::BN, NW = Ring::NW, TN = Ring::TN;
   constexpr int NH = BN / KP;                   // heads of a workgroup
   constexpr int NT = KP / 16;                   // 16-slot accumulator tiles of a head
-  constexpr int PLANE_BYTES = (BM + BN) * 128;
-  constexpr int STAGE_BYTES = PLANE_BYTES * 2;  // [A_hi | W_hi | A_lo | W_lo]
-  constexpr int GA = BM / 8;
-  constexpr int LPW = 4;                        // DMA instructions per wave per K tile and plane: groups wave, wave+4 (A), wave+8, wave+12 (W)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const GemmParams& p = P.g;
 
@@ -62,14 +49,8 @@ __global__ __launch_bounds__(256) void xattn_absorbed_kernel(XaParams P) {
 
   // workgroup -> (row tile, column group): XCD x (blockIdx & 7) takes a contiguous chunk of the row-tile-fastest order
   const int tiles_m = P.nseq * P.tiles_per_seq;
-  int tm, cg;
-  {
-    const int nwg = tiles_m * (P.H / NH);
-    const int q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-    const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + ((int)blockIdx.x >> 3);
-    cg = L / tiles_m;
-    tm = L - cg * tiles_m;
-  }
+  const int L = xcd_chunk_position(blockIdx.x, tiles_m * (P.H / NH));
+  const int cg = L / tiles_m, tm = L - cg * tiles_m;
   const int b = tm / P.tiles_per_seq, t = tm - b * P.tiles_per_seq;
   const int rpb = p.rpb;
   const int m0 = b * rpb + t * BM;              // first row of the tile; rows of the tile beyond the sequence are clamped / dropped
@@ -82,48 +63,13 @@ __global__ __launch_bounds__(256) void xattn_absorbed_kernel(XaParams P) {
 #pragma unroll
   for (int j = 0; j < TN; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // ---- LDS-DMA source geometry (gemm.hip): lane -> (row of the 8-row group, physical 16-B chunk), swizzle on the SOURCE chunk
-  const int srow = lane >> 3;
-  const int schunk = ((lane & 7) ^ srow) << 3;
-  uint32_t goff[LPW];
-#pragma unroll
-  for (int i = 0; i < LPW; ++i) {
-    const int g = wave + i * NW;
-    if (g < GA) {
-      int r = m0 + g * 8 + srow;
-      r = r < m_end ? r : m_end - 1;
-      goff[i] = (uint32_t)(((int64_t)r * p.lda[0] + schunk) * 2);
-    } else {
-      const int r = n0 + (g - GA) * 8 + srow;                   // always a key-slot row: n0 + 63 < H * KP
-      goff[i] = (uint32_t)(((int64_t)r * p.ldw + schunk) * 2);
-    }
-  }
-  const char* a_run = reinterpret_cast<const char*>(p.a[0]);
-  const char* w_run = wb;
-  const int64_t lo_bytes = (int64_t)p.K * 2;
-  auto issue = [&](int stage) {
-    char* st = smem_raw + stage * STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < LPW; ++i) {
-      const int g = wave + i * NW;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((g < GA ? a_run : w_run) + goff[i]),
-                                       (__attribute__((address_space(3))) void*)(st + g * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < LPW; ++i) {        // the lo planes: same rows, K elements further in the A row and in the W row
-      const int g = wave + i * NW;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((g < GA ? a_run : w_run) + lo_bytes + goff[i]),
-                                       (__attribute__((address_space(3))) void*)(st + PLANE_BYTES + g * 1024), 16, 0, 0);
-    }
-    a_run += 128;
-    w_run += 128;
-  };
+  Ring ring(smem_raw, p, wb, m0, m_end, n0, wave, lane);          // W rows n0 .. n0 + 63 are key-slot rows: n0 + 63 < H * KP
 
   // ---- the gate rows of the NH heads, each [W_hi | W_lo] = 2 K contiguous elements, linear in LDS behind the ring, GPITCH bytes apart
   // (64 bytes of padding: the fragment reads of the four rows and the four k chunks of a lane group fall into different banks).
   // Issued ahead of the ring's DMAs, so every counted wait of the K loop retires them first.
   const int GPITCH = p.K * 4 + 64;
-  char* gate_lds = smem_raw + NST * STAGE_BYTES;
+  char* gate_lds = smem_raw + Ring::RING_BYTES;
   {
     const int ngi = p.K >> 8;                 // 1024-byte wave instructions per gate row
     for (int i = wave; i < NH * ngi; i += NW) {
@@ -133,42 +79,28 @@ __global__ __launch_bounds__(256) void xattn_absorbed_kernel(XaParams P) {
                                        (__attribute__((address_space(3))) void*)(gate_lds + gr * GPITCH + gc * 1024), 16, 0, 0);
     }
   }
-  // folded RMSNorm (consumer): one thread per tile row
+  // folded RMSNorm (consumer): the rows' scales, behind the gate rows
   float* rs_lds = reinterpret_cast<float*>(gate_lds + NH * GPITCH);
   const bool scaled = p.rssq != nullptr;
-  RowScaleLoad rsl;
-  if (scaled && tid < BM) rowscale_load(p, min(m0 + tid, m_end - 1), rsl);
-  const int nk = p.K / 64;
-#pragma unroll
-  for (int s0 = 0; s0 < NST - 1; ++s0)
-    if (s0 < nk) issue(s0);
-  if (scaled && tid < BM) rs_lds[tid] = rowscale_finish(p, rsl);
+  ring.start(p, scaled, m0, m_end, tid, rs_lds);
 
   const char* grow = gate_lds + (lr & (NH - 1)) * GPITCH + lq * 16;      // fragment row lr = the gate row of head h0 + lr % NH
-  auto tile = [&](auto stage_c, int kt) {
-    constexpr int STAGE = decltype(stage_c)::value;
-    xa_ring_wait<NST - 2, LPW * 2>(nk - 1 - kt);
-    __builtin_amdgcn_s_barrier();
-    const bf16_t* As = reinterpret_cast<const bf16_t*>(smem_raw + STAGE * STAGE_BYTES);
-    const bf16_t* Ws = As + BM * 64;
-    const bf16_t* Al = As + PLANE_BYTES / 2;
-    const bf16_t* Wl = Al + BM * 64;
+  // one K tile: hi and lo fragments side by side, the next tile's DMAs, then the products
+  ring.k_loop([&](auto stage, int kt) {
     bf16x8 af[2], bf[2][TN], gf[2], afl[2], bfl[2][TN], gfl[2];
-    const int row = wave * 16 + lr;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      af[kk] = *reinterpret_cast<const bf16x8*>(As + row * 64 + (((kk * 4 + lq) ^ (row & 7)) << 3));
-      afl[kk] = *reinterpret_cast<const bf16x8*>(Al + row * 64 + (((kk * 4 + lq) ^ (row & 7)) << 3));
+      af[kk] = ring.a_frag(stage, 0, kk);
+      afl[kk] = ring.a_frag(stage, 1, kk);
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        const int wrow = j * 16 + lr;
-        bf[kk][j] = *reinterpret_cast<const bf16x8*>(Ws + wrow * 64 + (((kk * 4 + lq) ^ (wrow & 7)) << 3));
-        bfl[kk][j] = *reinterpret_cast<const bf16x8*>(Wl + wrow * 64 + (((kk * 4 + lq) ^ (wrow & 7)) << 3));
+        bf[kk][j] = ring.w_frag(stage, 0, kk, j);
+        bfl[kk][j] = ring.w_frag(stage, 1, kk, j);
       }
       gf[kk] = *reinterpret_cast<const bf16x8*>(grow + (kt * 64 + kk * 32) * 2);
       gfl[kk] = *reinterpret_cast<const bf16x8*>(grow + (p.K + kt * 64 + kk * 32) * 2);
     }
-    if (kt + NST - 1 < nk) issue((STAGE + NST - 1) % NST);
+    ring.refill(stage, kt);
     // three products per fragment pair, small terms first (the order of gemm_bf16_dma_kernel<.., S3>); W supplies the MFMA's rows
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
@@ -182,12 +114,7 @@ __global__ __launch_bounds__(256) void xattn_absorbed_kernel(XaParams P) {
       accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfl[kk], af[kk], accg, 0, 0, 0);
       accg = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf[kk], af[kk], accg, 0, 0, 0);
     }
-  };
-  for (int kt = 0; kt < nk; kt += NST) {
-    tile(std::integral_constant<int, 0>{}, kt);
-    if (kt + 1 < nk) tile(std::integral_constant<int, 1>{}, kt + 1);
-    if (kt + 2 < nk) tile(std::integral_constant<int, 2>{}, kt + 2);
-  }
+  });
 
   // ---- lane-private from here: register jj of acc[j] is row n0 + 16 j + 4 lq + jj of Wqk for token lr of the wave, i.e. key slot
   // 16 (j % NT) + 4 lq + jj of head h0 + j / NT (the geometry of attn_core.h with g = lq); register jj of accg is the gate logit of
@@ -241,17 +168,10 @@ __global__ __launch_bounds__(256) void xattn_absorbed_kernel(XaParams P) {
 
 template <int CLAMP, int KP>
 int launch_xa(const XaParams& P, hipStream_t s) {
-  constexpr int NH = 64 / KP;
-  constexpr size_t ring = 3 * (size_t)(64 + 64) * 128 * 2;
-  const size_t smem = ring + (size_t)NH * (P.g.K * 4 + 64) + 64 * 4;
-  // the opt-in above 64 KB is set ONCE per (kernel, device): for the largest K the entry point accepts
-  constexpr size_t smem_max = ring + (size_t)NH * (2048 * 4 + 64) + 64 * 4;
-  static_assert(smem_max <= 160 * 1024, "xattn_absorbed: LDS");
-  auto kern = xattn_absorbed_kernel<CLAMP, KP>;
+  constexpr int NH = 64 / KP;                    // gate rows of a workgroup, GPITCH = 4 K + 64 bytes apart; the entry point accepts K <= 2048
   static std::atomic<uint64_t> lds_set{0};
-  if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(kern), smem_max, lds_set, "v2a_xattn_absorbed")) return rc;
-  hipLaunchKernelGGL(kern, dim3(P.nseq * P.tiles_per_seq * (P.H / NH)), dim3(256), smem, s, P);
-  return v2a_check_launch("v2a_xattn_absorbed");
+  return xattn_ring_launch<true, NH * (2048 * 4 + 64)>(xattn_absorbed_kernel<CLAMP, KP>, P, P.nseq * P.tiles_per_seq * (P.H / NH),
+                                                       (size_t)NH * (P.g.K * 4 + 64), lds_set, "v2a_xattn_absorbed", s);
 }
 
 // ---- once per sample(): the absorbed operands -------------------------------------------------------------------------------------
@@ -429,25 +349,8 @@ extern "C" int v2a_xattn_absorbed(const v2a_xattn_absorbed_args* a, v2a_stream_t
   V2A_REQUIRE(a->kv_len != nullptr, "v2a_xattn_absorbed: kv_len is required (the padding slots are masked through it)");
   XaParams P{};
   GemmParams& p = P.g;
-  p.a[0] = a->a;
-  p.lda[0] = a->lda;
-  p.kend[0] = K;
-  p.nseg = 1;
-  p.w = a->wqk;
-  p.ldw = a->ldw;
-  p.bias = a->gate_bias;
-  p.M = a->M;
-  p.N = hkp;
-  p.K = K;
-  p.rpb = a->rows_per_batch;
-  p.rssq = a->row_ssq;
-  p.rssq_ld = a->ld_row_ssq;
-  p.rssq_parts = a->row_ssq_parts;
-  p.rnorm = sqrtf((float)a->row_norm_dim);
-  if (a->row_ssq)
-    V2A_REQUIRE(a->row_ssq_parts > 0 && a->row_ssq_parts <= 40 && a->row_norm_dim > 0 && a->ld_row_ssq >= (a->row_ssq_parts + 3) / 4 * 4 &&
-                    a->ld_row_ssq % 4 == 0 && ((uintptr_t)a->row_ssq & 15) == 0,
-                "v2a_xattn_absorbed: row_ssq needs row_ssq_parts <= 40 (%d), row_norm_dim (%d) and rows of whole float4", a->row_ssq_parts, a->row_norm_dim);
+  xattn_ring_params(p, a->a, a->lda, a->wqk, a->ldw, a->gate_bias, a->M, hkp, K, a->rows_per_batch);
+  if (int rc = v2a_detail::fill_row_scale(p, a->row_ssq, a->ld_row_ssq, a->row_ssq_parts, a->row_norm_dim, "v2a_xattn_absorbed")) return rc;
   P.wbs = a->w_batch_stride;
   P.out = reinterpret_cast<bf16_t*>(a->out);
   P.ldo = a->ldo;
