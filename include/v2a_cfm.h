@@ -530,6 +530,14 @@ int v2a_roll_head(const v2a_roll_head_args* args, v2a_stream_t stream);
 int v2a_roll_expand(const float* roll, float* out, int32_t B, int32_t t, int32_t notes, int32_t rep, int32_t l,
                     v2a_stream_t stream);
 
+/* The same by a ratio rep / group, the 88-key configuration's 5 / 2 (x3_2 = e2_tts_crossatt3_2.py:1546-1554): every row repeated
+ * `rep` times, the repeated rows cut to a whole number of groups and every `group` (1 or 2) consecutive ones averaged:
+ *   out[b][r] = (1 / group) * sum_{g < group} roll[b][(r * group + g) / rep]   for r < t * rep / group,   0 for the rows up to l.
+ * group = 2 forms (a + b) * 0.5f in fp32, which is what torch's `.mean(2)` of two rows gives bit for bit; group = 1 copies, so
+ * (rep, 1) equals v2a_roll_expand.  Replaces the repeat / reshape / mean / crop / zero-pad expression of x3_2:1546-1554. */
+int v2a_roll_expand_ratio(const float* roll, float* out, int32_t B, int32_t t, int32_t notes, int32_t rep, int32_t group, int32_t l,
+                          v2a_stream_t stream);
+
 /* =======================================================================================
  * N1: Encodec 24 kHz decoder, the vocoder behind `EncodecWrapper.decode` x3:434-437 (predict.py:277-278;
  * arithmetic: transformers EncodecDecoder, requirements.txt:20).  Activations are time-major [T][C] fp32, so every
@@ -701,6 +709,14 @@ int v2a_piano_resize_h(const uint8_t* frames, int32_t F, int32_t H, int32_t W, c
  * and the float32 cast of x3:1890. */
 int v2a_piano_resize_v(const uint8_t* tmp, int32_t n, int32_t rows, int32_t ldt, int32_t Ho, int32_t Wo, const int32_t* bounds,
                        const int32_t* coef, int32_t ksize, const float* lut, float* out, v2a_stream_t stream);
+/* The vertical pass with a transposed store, for the 88-key configuration's portrait frames: the same sums, clip and table as
+ * v2a_piano_resize_v (same arguments, same caller guarantees), stored as
+ *   out[j][x][y],  out (n, Wo, Ho) fp32 contiguous, 16-byte aligned when Ho % 4 == 0.
+ * A workgroup forms a band of 32 output rows y in LDS and writes runs along y.  Wo <= 488 (the band and the table in 64 KB of LDS).  Replaces: the
+ * vertical pass of `x.resize((100, 900))`, the reshape to (900, 100, 1), the transpose [2, 1, 0] and `x / 255.` of `transform`
+ * (x3_2 = e2_tts_crossatt3_2.py:65-68) and the float32 cast of x3_2:1906. */
+int v2a_piano_resize_vt(const uint8_t* tmp, int32_t n, int32_t rows, int32_t ldt, int32_t Ho, int32_t Wo, const int32_t* bounds,
+                        const int32_t* coef, int32_t ksize, const float* lut, float* out, v2a_stream_t stream);
 
 /* =======================================================================================
  * Encodec residual vector quantizer: the part of `EncodecModel.encode` / `.decode` between the encoder (v2a_encodec_stage0 and the

@@ -9,7 +9,8 @@ from .collate import collate_clips, ClipRequest  # noqa: F401
 from .dist import shard_range, gather_latents  # noqa: F401
 from .features import (feature_cache_path, save_clip_cache, load_clip_cache, resample_indices,  # noqa: F401
                        resample_clip_features, encode_video_cached, piano_frames_cache_path, save_piano_frames_cache,
-                       piano_frame_indices, load_piano_frames, piano_frames_from_video, load_midi_ground_truth)
+                       piano_frame_indices, load_piano_frames, piano_frames_from_video, load_midi_ground_truth,
+                       PianoConfig, PIANO_51, PIANO_88, piano_config)
 from .video2roll import Video2RollEngine  # noqa: F401
 from .roll2midi import Roll2MidiEngine, Roll2MidiEnhanceEngine  # noqa: F401
 from .encodec import EncodecDecoder, EncodecEncoder, EncodecQuantizer  # noqa: F401
@@ -23,4 +24,4 @@ from . import _lib  # noqa: F401
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
            "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "val_span_mask", "E2TTSReturn", "LossBreakdown", "load_midi_ground_truth", "expected_state_dict_shapes", "NOTES",
            "Video2RollEngine", "Roll2MidiEngine", "Roll2MidiEnhanceEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "DINOv2ImageEncoder", "PianoFramePlan", "PianoFramePreprocessor",
-           "WaveFrontEnd", "sinc_resample_table"]
+           "WaveFrontEnd", "sinc_resample_table", "PianoConfig", "PIANO_51", "PIANO_88", "piano_config"]

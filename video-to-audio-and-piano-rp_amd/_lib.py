@@ -149,6 +149,7 @@ EXPORTS = [
     "v2a_wave_resample", "v2a_wave_stats", "v2a_wave_normalize",
     "v2a_roll2midi_stem", "v2a_leaky_shadow", "v2a_roll2midi_head", "v2a_roll2midi_gate",
     "v2a_xattn_absorb_prepare", "v2a_xattn_absorbed",
+    "v2a_roll_expand_ratio", "v2a_piano_resize_vt",
 ]
 
 
@@ -200,6 +201,7 @@ def _declare(lib):
     lib.v2a_pool2d_split.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.v2a_roll_head.argtypes = [C.POINTER(RollHeadArgs), vp]
     lib.v2a_roll_expand.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.v2a_roll_expand_ratio.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.v2a_elu_pad.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
     lib.v2a_lstm_layer.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp]
     lib.v2a_lstm2.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
@@ -215,6 +217,7 @@ def _declare(lib):
     lib.v2a_encodec_stage0.argtypes = [vp, vp, vp, i64, vp]
     lib.v2a_piano_resize_h.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp]
     lib.v2a_piano_resize_v.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    lib.v2a_piano_resize_vt.argtypes = lib.v2a_piano_resize_v.argtypes
     lib.v2a_encodec_rvq_encode.argtypes = [vp, i64, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp]
     lib.v2a_encodec_rvq_decode.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, i64, i64, i64, vp]
     lib.v2a_cfm_interp.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
@@ -677,6 +680,11 @@ def roll_head(args: "RollHeadArgs"):
 
 def roll_expand(roll, out, *, B, t, notes, rep, l):
     check(lib().v2a_roll_expand(roll.data_ptr(), out.data_ptr(), B, t, notes, rep, l, stream_ptr()))
+
+
+def roll_expand_ratio(roll, out, *, B, t, notes, rep, group, l):
+    """out (B, l, notes) <- rows of roll (B, t, notes) repeated `rep` times, every `group` (1 | 2) of them averaged, zero behind."""
+    check(lib().v2a_roll_expand_ratio(roll.data_ptr(), out.data_ptr(), B, t, notes, rep, group, l, stream_ptr()))
 
 
 # ---- Roll2Midi generator (roll2midi.py) ----------------------------------------------------------

@@ -18,6 +18,9 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
   --piano            V2P (src/inference_v2p.py): the grey frames `<video>.generated_frames_raw.2.npz` (features.py; made on the GPU
                      by piano_frames.py from a moviepy decode when the cache is missing) go
                      through the HIP Video2Roll encoder; the checkpoint must hold `video2roll_net.*`
+  --piano-keys {51,88}   the piano configuration of the checkpoint (features.PianoConfig): 51 = e2_tts_crossatt3.py, 88 =
+                     e2_tts_crossatt3_2.py (trainer_multigpus_alldatas3_2.py): 88 keys, a video frame per 2.5 latent frames, portrait
+                     frames.  The frame cache has one name and one shape under both: a cache of the other configuration is silently wrong
   --encodec STATE    torch-saved state dict of `EncodecModel.from_pretrained("facebook/encodec_24khz")` (or of its decoder):
                      each clip's valid frames are decoded by the HIP vocoder and written as `<name>.wav` (24 kHz float32),
                      what the reference does with `save_to_filename` / torchaudio.save (x3:2291-2303, predict.py:279-281).
@@ -161,10 +164,11 @@ def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip
     return reqs
 
 
-def piano_frames_for(video_paths, l: int, preprocess, decode):
+def piano_frames_for(video_paths, l: int, preprocess, decode, video_multi: float = 3.0):
     """--piano: the (b, 1, t, 100, 900) stack of a batch.  Clips with a frame cache are read from it; the others are decoded by
     `decode(video_path) -> (frames, duration)` and go through `preprocess` (a PianoFramePreprocessor), which also writes their cache.
-    Without moviepy (`decode` raises ImportError) a missing cache is load_piano_frames' FileNotFoundError, as without this path."""
+    Without moviepy (`decode` raises ImportError) a missing cache is load_piano_frames' FileNotFoundError, as without this path.
+    `video_multi`: latent frames per video frame of the piano configuration (--piano-keys)."""
     from .features import load_piano_frames, piano_frames_cache_path
 
     def frames_of(vp):
@@ -175,7 +179,8 @@ def piano_frames_for(video_paths, l: int, preprocess, decode):
         except ImportError:
             return None
 
-    return load_piano_frames(video_paths, l, video_frames=[frames_of(vp) for vp in video_paths], preprocess=preprocess)
+    return load_piano_frames(video_paths, l, video_frames=[frames_of(vp) for vp in video_paths], preprocess=preprocess,
+                             video_multi=video_multi)
 
 
 def validate_batch(model, video_paths, extras, frames=None, wav: bool = False) -> dict:
@@ -194,7 +199,7 @@ def validate_batch(model, video_paths, extras, frames=None, wav: bool = False) -
             lat.append(torch.from_numpy(np.load(path)).float())
     lens = torch.tensor([min(x.shape[0], n) for x in lat])
     inp = torch.stack([torch.nn.functional.pad(x[:n], (0, 0, 0, n - min(x.shape[0], n))) for x in lat])
-    midis = None if frames is None else load_midi_ground_truth(video_paths, n)
+    midis = None if frames is None else load_midi_ground_truth(video_paths, n, model.piano)
     r = model.forward(inp, times=0.5, lens=lens, val=True, frames=frames, midis=midis, text_embed=extras["text_embed"],
                       context=extras["context"], context_mask=extras["context_mask"])
     return dict(clips=len(video_paths), loss=float(r.loss), roll_loss=model.val_stats["roll"],
@@ -230,6 +235,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the piano frames through the Video2Roll encoder; a video without "
                     "<video>.generated_frames_raw.2.npz is decoded with moviepy and resized on this rank's GPU, and the cache is written")
+    ap.add_argument("--piano-keys", type=int, default=51, choices=[51, 88],
+                    help="the piano configuration of the checkpoint: 51 (e2_tts_crossatt3.py: keys 15..65, a video frame per 3 latent frames, "
+                         "landscape frames) or 88 (e2_tts_crossatt3_2.py: all keys, a video frame per 2.5 latent frames, portrait frames "
+                         "resized to 100 x 900 and transposed).  The frame cache <video>.generated_frames_raw.2.npz has the same name and "
+                         "shapes under both, as in the reference: one written under the other value is silently wrong")
     ap.add_argument("--frames-dtype", default=None, choices=["fp32", "bf16", "bf16x3"],
                     help="compute mode of the Video2Roll encoder behind --piano (default: bf16 under --dtype bf16, else fp32); bf16x3: "
                          "split-bf16 implicit GEMM inside 1e-4 of the reference probabilities")
@@ -294,7 +304,7 @@ def main(argv=None):
                   num_channels=channels, sampling_rate=24000, if_cond_proj_in=a.audio_prompt_seconds > 0, tokenizer="phoneme_zh",
                   audiocond_drop_prob=0.3 if a.audio_prompt_seconds > 0 else 1.1,          # predict.py:71-72, 144: the two travel together
                   compute_dtype=a.dtype, device=torch.device("cuda", local), bucket_frames=a.bucket_frames, bucket_ctx=a.bucket_ctx,
-                  frames_compute_dtype=a.frames_dtype, video_encoder=a.video_encoder)
+                  frames_compute_dtype=a.frames_dtype, video_encoder=a.video_encoder, piano_keys=a.piano_keys)
     ck = torch.load(a.ckpt, map_location="cpu")
     res = model.load_state_dict(ck.get("model_state_dict", ck), strict=False)      # predict.py:161-168
     if res.missing_keys:
@@ -349,11 +359,12 @@ def main(argv=None):
         s, e, per = shard_range(len(chunk), rank, world)
         mine = chunk[s:e]
         if mine:
-            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder), channels, gen)
+            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder), channels, gen, notes=model.cfg.notes)
             frames = None
             if a.piano:
                 # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
-                frames = piano_frames_for([vp for vp, _ in mine], int(batch8[3].max()), model.piano_frame_preprocessor(), decode)
+                frames = piano_frames_for([vp for vp, _ in mine], int(batch8[3].max()), model.piano_frame_preprocessor(), decode,
+                                          model.piano.video_multi)
             decoded.clear()
             if a.roll2midi and frames is not None and not a.validate:
                 written += write_midi_rolls(model, frames, [vp for vp, _ in mine], a.out_dir)
@@ -362,6 +373,10 @@ def main(argv=None):
                 print(json.dumps(dict(batch=b0 // a.batch, **validate_batch(model, [vp for vp, _ in mine], extras, frames, a.wav))), flush=True)
                 continue
             cond, lens = batch8[1], batch8[3]
+            if frames is not None:
+                # the collator's all-zero roll would win over `frames` in sample() (a given frames_embed is taken as the roll):
+                # with --piano the roll comes from the frames, through the Video2Roll encoder
+                extras.pop("frames_embed")
             if a.audio_prompt_seconds > 0:                           # raw waves (b, nw): sample() encodes them (x3:2157-2160)
                 cond = torch.stack([wave_prompt(model, vp, a.audio_prompt_seconds) if a.wav else read_audio_prompt(vp, a.audio_prompt_seconds)
                                     for vp, _ in mine])

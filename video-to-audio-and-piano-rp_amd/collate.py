@@ -14,7 +14,7 @@ from dataclasses import dataclass, field
 
 import torch
 
-NOTES = 51
+NOTES = 51                            # the default piano configuration (features.PIANO_51); `collate_clips(notes=)` takes the model's
 
 
 @dataclass
@@ -27,9 +27,10 @@ class ClipRequest:
     roll: torch.Tensor | None = None  # (n_frames, NOTES) piano roll (V2P) or None (V2A -> zeros, x3:2164-2165)
 
 
-def collate_clips(clips: list[ClipRequest], num_channels: int = 128, generator: torch.Generator | None = None):
+def collate_clips(clips: list[ClipRequest], num_channels: int = 128, generator: torch.Generator | None = None, notes: int = NOTES):
     """Returns (batch8, extras): `batch8` is the reference's 8-tuple; `extras` holds the padded
-    conditioning tensors to pass as sample(text_embed=, context=, context_mask=, frames_embed=)."""
+    conditioning tensors to pass as sample(text_embed=, context=, context_mask=, frames_embed=).
+    `notes`: keys of the piano roll, the model's `cfg.notes` (51, or 88 under E2TTS(piano_keys=88))."""
     assert clips, "empty batch"
     B = len(clips)
     n = max(c.n_frames for c in clips)
@@ -43,7 +44,7 @@ def collate_clips(clips: list[ClipRequest], num_channels: int = 128, generator: 
     clip_embed = torch.zeros(B, n, dt)
     context = torch.zeros(B, nc, dc)
     context_mask = torch.zeros(B, nc, dtype=torch.bool)
-    roll = torch.zeros(B, n, NOTES)
+    roll = torch.zeros(B, n, notes)
     any_roll = False
     for i, c in enumerate(clips):
         assert c.clip_embed.shape[0] == c.n_frames, "clip_embed must be resampled to n_frames (x3:1803-1805)"
@@ -51,6 +52,7 @@ def collate_clips(clips: list[ClipRequest], num_channels: int = 128, generator: 
         context[i, :c.context.shape[0]] = c.context
         context_mask[i, :c.context.shape[0]] = True
         if c.roll is not None:
+            assert c.roll.shape[-1] == notes, f"roll of {c.roll.shape[-1]} keys in a batch of {notes}-key rolls"
             roll[i, :c.n_frames] = c.roll[:c.n_frames]
             any_roll = True
     batch8 = [text, mel, video_paths, mel_len, video_drop_prompt, None, None, roll if any_roll else None]

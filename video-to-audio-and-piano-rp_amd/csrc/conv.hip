@@ -264,6 +264,31 @@ __global__ __launch_bounds__(256) void roll_expand_kernel(const float* __restric
   out[gid] = src < t ? roll[(b * t + src) * notes + j] : 0.f;
 }
 
+// The 88-key configuration's expansion (x3_2:1546-1554): rows repeated `rep` times, cut to d * GROUP rows, GROUP consecutive ones
+// averaged.  Row r of the result reads source rows (r * GROUP + g) / rep, all < t for r < d = t * rep / GROUP.  GROUP = 2 is
+// (a + b) * 0.5f: torch's mean over two elements adds them and multiplies by 1 / 2, both exact in the same places.
+template <int GROUP>
+__global__ __launch_bounds__(256) void roll_expand_ratio_kernel(const float* __restrict__ roll, float* __restrict__ out, int64_t total,
+                                                                int t, int notes, int rep, int d, int l) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= total) return;
+  const int j = (int)(gid % notes);
+  const int64_t r = gid / notes;
+  const int row = (int)(r % l);
+  const int64_t b = r / l;
+  float v = 0.f;
+  if (row < d) {
+    const int64_t k = (int64_t)row * GROUP;
+    const float* src = roll + b * t * (int64_t)notes + j;
+    if (GROUP == 1) {
+      v = src[(k / rep) * notes];
+    } else {
+      v = (src[(k / rep) * notes] + src[((k + 1) / rep) * notes]) * 0.5f;
+    }
+  }
+  out[gid] = v;
+}
+
 }  // namespace
 
 extern "C" int v2a_im2col(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t kh, int32_t kw, int32_t stride,
@@ -393,4 +418,21 @@ extern "C" int v2a_roll_expand(const float* roll, float* out, int32_t B, int32_t
   hipLaunchKernelGGL(roll_expand_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, roll, out, total, t,
                      notes, rep, l);
   return v2a_check_launch("v2a_roll_expand");
+}
+
+extern "C" int v2a_roll_expand_ratio(const float* roll, float* out, int32_t B, int32_t t, int32_t notes, int32_t rep, int32_t group,
+                                     int32_t l, v2a_stream_t stream) {
+  V2A_REQUIRE(roll && out, "v2a_roll_expand_ratio: null pointer");
+  V2A_REQUIRE(B > 0 && t > 0 && notes > 0 && rep > 0 && l > 0, "v2a_roll_expand_ratio: B=%d t=%d notes=%d rep=%d l=%d", B, t, notes, rep, l);
+  V2A_REQUIRE(group == 1 || group == 2, "v2a_roll_expand_ratio: group=%d (1 or 2)", group);
+  const int64_t d = (int64_t)t * rep / group;          // whole groups of repeated rows: every source row index stays below t
+  const int64_t total = (int64_t)B * l * notes;
+  V2A_REQUIRE(d <= INT32_MAX && (total + 255) / 256 <= INT32_MAX, "v2a_roll_expand_ratio: t * rep / group = %lld rows, %lld elements",
+              (long long)d, (long long)total);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (group == 1)
+    hipLaunchKernelGGL((roll_expand_ratio_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, roll, out, total, t, notes, rep, (int)d, l);
+  else
+    hipLaunchKernelGGL((roll_expand_ratio_kernel<2>), grid, dim3(256), 0, (hipStream_t)stream, roll, out, total, t, notes, rep, (int)d, l);
+  return v2a_check_launch("v2a_roll_expand_ratio");
 }

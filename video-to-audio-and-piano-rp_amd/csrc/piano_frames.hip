@@ -4,6 +4,8 @@
 //   v2a_piano_resize_h   rgb2l grey byte of every tap formed in registers + horizontal pass (22-bit fixed-point integer sums,
 //                        clipped to uint8) for the input rows the vertical pass reads -> uint8 tmp
 //   v2a_piano_resize_v   vertical pass over tmp, clipped to uint8, mapped through the host table u -> float32(u / 255.) -> fp32
+//   v2a_piano_resize_vt  the same with a transposed store, out[f][x][y]: the 88-key configuration resizes to 100 wide x 900 tall
+//                        and transposes (`Image.resize((100, 900))`, transpose [2, 1, 0]; x3_2 = e2_tts_crossatt3_2.py:65-68)
 // Bounds and coefficients come from the host (Pillow's precompute_coeffs / normalize_coeffs_8bpc); the host also guarantees that
 // every tap lies inside the image.  Memory-bound integer kernels: no MFMA.
 #include "v2a_common.h"
@@ -138,6 +140,66 @@ __global__ __launch_bounds__(PF_THREADS) void piano_resize_v_kernel(const uint8_
   }
 }
 
+// ---- vertical pass + table, transposed store (the 88-key configuration's portrait frames) ------------------------------------------
+// Block (band, j): output rows y = PF_BAND * band ... of frame j, all Wo columns.  Phase 1: an item is (row yy of the band, 4
+// consecutive columns): the sums of piano_resize_v_kernel, whose 4 table values go to the LDS tile [x][yy] (pitch PF_BAND + 1:
+// lanes on consecutive column quads land 4 * (PF_BAND + 1) words apart, 4 banks on, so at most 4 lanes of a 32-lane half share a bank;
+// at pitch PF_BAND every lane of a row would; the reads of phase 2 hit 32 distinct banks).  Phase 2: an item is
+// (column x, 4 consecutive yy): out[j][x][y ...] is contiguous along y, so a lane stores 16 bytes and 8 lanes cover a band's run
+// of 128 bytes; rows of Ho floats keep the alignment when Ho % 4 == 0 (PF_BAND % 4 == 0).
+constexpr int PF_BAND = 32;
+
+__global__ __launch_bounds__(PF_THREADS) void piano_vpass_transposed_kernel(const uint8_t* __restrict__ tmp, int rows, int ldt, int Ho, int Wo,
+                                                                     const int32_t* __restrict__ bounds, const int32_t* __restrict__ coef,
+                                                                     int ksize, const float* __restrict__ lut, float* __restrict__ out) {
+  extern __shared__ float pf_tile[];          // Wo rows of PF_BAND + 1 floats
+  __shared__ float tab[256];
+  tab[threadIdx.x] = lut[threadIdx.x];          // PF_THREADS == 256
+  __syncthreads();
+  constexpr int P = PF_BAND + 1;
+  const int yb = blockIdx.x * PF_BAND;
+  const int nb = min(PF_BAND, Ho - yb);
+  const int64_t j = blockIdx.y;
+  const int Q = (Wo + 3) >> 2;
+  const int ld4 = ldt >> 2;
+  for (int it = threadIdx.x; it < nb * Q; it += PF_THREADS) {
+    const int yy = it / Q, q = it - yy * Q;
+    const int y = yb + yy;
+    const int ys = min(bounds[2 * y + 1], min(ksize, rows));          // the host checks the tables; the clamps keep a wrong one inside tmp
+    const int ymin = max(0, min(bounds[2 * y], rows - ys));
+    const int32_t* k = coef + (int64_t)y * ksize;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(tmp + (j * rows + ymin) * (int64_t)ldt) + q;          // 4 q < ldt
+    int32_t a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21, a3 = 1 << 21;
+#pragma unroll 4
+    for (int i = 0; i < ys; ++i) {
+      const uint32_t w = src[(int64_t)i * ld4];
+      const int32_t kv = k[i];
+      a0 += kv * (int32_t)(w & 255);
+      a1 += kv * (int32_t)((w >> 8) & 255);
+      a2 += kv * (int32_t)((w >> 16) & 255);
+      a3 += kv * (int32_t)(w >> 24);
+    }
+    const float v[4] = {tab[pf_clip8(a0)], tab[pf_clip8(a1)], tab[pf_clip8(a2)], tab[pf_clip8(a3)]};
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (4 * q + c < Wo) pf_tile[(4 * q + c) * P + yy] = v[c];
+  }
+  __syncthreads();
+  float* o = out + j * (int64_t)Wo * Ho + yb;
+  const int G = PF_BAND / 4;
+  for (int it = threadIdx.x; it < Wo * G; it += PF_THREADS) {
+    const int x = it / G, y4 = 4 * (it - x * G);
+    if (y4 >= nb) continue;
+    const float* t = pf_tile + x * P + y4;
+    float* dst = o + (int64_t)x * Ho + y4;
+    if ((Ho & 3) == 0 && y4 + 4 <= nb) {
+      *reinterpret_cast<f32x4*>(dst) = f32x4{t[0], t[1], t[2], t[3]};
+    } else {
+      for (int c = 0; c < 4 && y4 + c < nb; ++c) dst[c] = t[c];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int v2a_piano_resize_h(const uint8_t* frames, int32_t F, int32_t H, int32_t W, const int32_t* sel, int32_t n, uint8_t* tmp,
@@ -168,4 +230,20 @@ extern "C" int v2a_piano_resize_v(const uint8_t* tmp, int32_t n, int32_t rows, i
   hipLaunchKernelGGL(piano_resize_v_kernel, dim3((unsigned)Ho, (unsigned)n), dim3(PF_THREADS), 0, (hipStream_t)stream, tmp, rows, ldt, Ho, Wo,
                      bounds, coef, ksize, lut, out);
   return v2a_check_launch("v2a_piano_resize_v");
+}
+
+extern "C" int v2a_piano_resize_vt(const uint8_t* tmp, int32_t n, int32_t rows, int32_t ldt, int32_t Ho, int32_t Wo, const int32_t* bounds,
+                                   const int32_t* coef, int32_t ksize, const float* lut, float* out, v2a_stream_t stream) {
+  V2A_REQUIRE(tmp && bounds && coef && lut && out, "v2a_piano_resize_vt: null pointer");
+  V2A_REQUIRE(n > 0 && n <= 65535 && rows > 0 && Ho > 0 && Wo > 0 && ksize > 0, "v2a_piano_resize_vt: n=%d rows=%d Ho=%d Wo=%d ksize=%d", n, rows,
+              Ho, Wo, ksize);
+  V2A_REQUIRE(ldt >= Wo && ldt % 4 == 0, "v2a_piano_resize_vt: ldt=%d must be a multiple of 4 and >= Wo=%d", ldt, Wo);
+  V2A_REQUIRE(((uintptr_t)tmp & 3) == 0 && ((uintptr_t)out & (Ho % 4 == 0 ? 15 : 3)) == 0,
+              "v2a_piano_resize_vt: tmp must be 4-byte aligned and out 16-byte aligned (4-byte when Ho %% 4 != 0)");
+  const size_t lds = (size_t)Wo * (PF_BAND + 1) * sizeof(float);
+  V2A_REQUIRE(lds + 256 * sizeof(float) <= 64 * 1024, "v2a_piano_resize_vt: Wo=%d needs %zu bytes of LDS (limit 65536 with the table)", Wo, lds);
+  const dim3 grid((unsigned)((Ho + PF_BAND - 1) / PF_BAND), (unsigned)n);
+  hipLaunchKernelGGL(piano_vpass_transposed_kernel, grid, dim3(PF_THREADS), lds, (hipStream_t)stream, tmp, rows, ldt, Ho, Wo, bounds, coef, ksize,
+                     lut, out);
+  return v2a_check_launch("v2a_piano_resize_vt");
 }

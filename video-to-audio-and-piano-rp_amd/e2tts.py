@@ -182,6 +182,7 @@ class E2TTS:
         text_encoder_fn: Callable | None = None,    # (prompts) -> ((b, nc, ctx) float, (b, nc) bool)
         frames_encoder_fn: Callable | None = None,  # (frames, n) -> (b, n, NOTES)
         frames_compute_dtype: str | None = None,    # Video2Roll encoder mode: None = "bf16" under compute_dtype "bf16", else "fp32"; or "fp32" | "bf16" | "bf16x3"
+        piano_keys: int = 51,                       # 51: e2_tts_crossatt3.py | 88: e2_tts_crossatt3_2.py, the reference's 88-key piano configuration (features.PianoConfig)
     ):
         if not isinstance(transformer, dict):
             raise TypeError("transformer must be the keyword dict of the reference (predict.py:120-134)")
@@ -194,6 +195,10 @@ class E2TTS:
             if not tk.pop(flag, flag != "if_text_conv"):
                 raise NotImplementedError(f"{flag}=False: only the shipped configuration (all True, predict.py:126-129) is built")
         tk.pop("cond_on_time", None)
+        from .features import piano_config
+        self.piano = piano_config(piano_keys)          # notes, note range, video_multi, roll expansion, frame layout
+        if tk.setdefault("notes", self.piano.notes) != self.piano.notes:
+            raise ValueError(f"transformer['notes']={tk['notes']} contradicts piano_keys={self.piano.notes}")
         if num_channels is None:
             raise ValueError("num_channels is required (predict.py:152)")
         self.cfg = DiTConfig(num_channels=num_channels, cond_proj_in=bool(if_cond_proj_in), **tk)
@@ -288,6 +293,9 @@ class E2TTS:
             lacking = [k for k in v2r_shapes() if k not in v2r and not k.endswith("num_batches_tracked")]
             if lacking:
                 raise RuntimeError(f"load_state_dict: {_V2R_PREFIX}* is incomplete, e.g. {lacking[:3]}")
+            if v2r["fc.weight"].shape[0] != self.cfg.notes:
+                raise RuntimeError(f"size mismatch for {_V2R_PREFIX}fc.weight: checkpoint {tuple(v2r['fc.weight'].shape)} vs model "
+                                   f"({self.cfg.notes}, 128): a checkpoint of the other piano configuration (E2TTS(piano_keys=...))")
             self._v2r_sd, self._v2r = v2r, None
         unexpected = [k for k in state_dict if k not in self._shapes and not k.startswith(_V2R_PREFIX)]
         if strict and (missing or unexpected):
@@ -313,25 +321,25 @@ class E2TTS:
 
     # ---- conditioning helpers ---------------------------------------------------------------
     def encode_frames(self, x, l: int):
-        """x3:1525-1553: (b, 1, t, 100, 900) grey frames -> piano-roll probabilities (b, l, 51) on the HIP Video2Roll
-        encoder (video2roll.py); needs the `video2roll_net.*` weights of the checkpoint (load_state_dict)."""
+        """x3:1525-1553: (b, 1, t, 100, 900) grey frames -> piano-roll probabilities (b, l, notes) on the HIP Video2Roll
+        encoder (video2roll.py): every frame's row x3 in time, or x2.5 under piano_keys=88 (x3_2:1546-1547).  Needs the
+        `video2roll_net.*` weights of the checkpoint (load_state_dict)."""
         if self._v2r_sd is None:
             raise RuntimeError("encode_frames: no `video2roll_net.*` weights were loaded (load_state_dict), pass "
                                "frames_embed= or frames_encoder_fn= instead")
-        if self._v2r is None:
-            from .video2roll import Video2RollEngine
-            self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute)
-        return self._v2r.encode_frames(x, l)
+        return self._video2roll().encode_frames(x, l)
 
     def encode_video_frames(self, video_paths, l: int, piano, *, video_frames=None):
         """x3:1829-1991, the `piano` branch: the grey frame stacks of a batch of clips and the (unused) MIDI ground truth,
         `(frames (b, 1, t, 100, 900), midis (b, l, NOTES) zeros)`, or `(None, None)` when `piano` is false or no clip has frames.
+        One video frame per `piano.video_multi` latent frames (3.0, or 2.5 under piano_keys=88, x3_2:1929-1930).
         `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) or None per clip, the convention of `sample` -- not to be
         confused with `_encode_video_frames`, the CLIP batcher over the same list.  A clip with a frame cache
         `<video>.generated_frames_raw.2.npz` is read from it; one without goes through the HIP piano-frame preprocessor
         (piano_frames.py), all its frames, and its cache is written (x3:1877-1891).  `video_paths=None`: the clips have no
         place for a cache, only the frames each one uses are resized and nothing is written.  The stack is on this model's
-        device whenever a clip was preprocessed."""
+        device whenever a clip was preprocessed.  The cache has the same name and shapes under both piano configurations, as in
+        the reference: one written under piano_keys=51 (landscape frames) is silently wrong under 88 (portrait), and the reverse."""
         if not piano:
             return None, None
         from .features import load_piano_frames
@@ -341,7 +349,7 @@ class E2TTS:
                 return None, None
             # names under which no cache can exist; nothing is written (write_cache=False)
             video_paths = [None if fr is None else f"<clip {i}>.mp4" for i, fr in enumerate(video_frames)]
-        stack = load_piano_frames(video_paths, l, video_frames=video_frames, write_cache=write,
+        stack = load_piano_frames(video_paths, l, video_frames=video_frames, write_cache=write, video_multi=self.piano.video_multi,
                                   preprocess=None if video_frames is None else self.piano_frame_preprocessor())
         if stack is None:
             return None, None
@@ -350,7 +358,7 @@ class E2TTS:
     def _video2roll(self):
         if self._v2r is None:
             from .video2roll import Video2RollEngine
-            self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute)
+            self._v2r = Video2RollEngine(self._v2r_sd, self._device, compute=self._frames_compute, expand=self.piano.expand)
         return self._v2r
 
     def load_roll2midi(self, src, **kw):
@@ -373,18 +381,24 @@ class E2TTS:
     def frames_to_midi(self, frames, window: int = 100, threshold: float = 0.5, tail: str = "own"):
         """(b, 1, t, 100, 900) grey piano frames -> (probs (b, t, 51) fp32, midi (b, t, 51) uint8) at the video frame rate: the
         Video2Roll encoder's per-frame key probabilities refined by the Roll2Midi generator, `midi = probs >= threshold`
-        (`Roll2MidiEngine.refine`).  Both networks run on the device with no host visit between them."""
+        (`Roll2MidiEngine.refine`).  Both networks run on the device with no host visit between them.  Under piano_keys=88
+        the generator gets keys 15..65 of the encoder's 88, and the result stays (b, t, 51)."""
         if self._v2r_sd is None:
             raise NotImplementedError("frames_to_midi needs the Video2Roll encoder: load a checkpoint holding `video2roll_net.*` (load_state_dict)")
         if self._r2m is None:
             raise NotImplementedError("frames_to_midi needs the Roll2Midi generator: load_roll2midi(state_dict_G, a checkpoint holding it, or its path)")
-        return self._r2m.refine(self._video2roll().frame_probs(frames), window=window, threshold=threshold, tail=tail)
+        from .features import PIANO_51
+        probs = self._video2roll().frame_probs(frames)
+        if self.piano.notes != PIANO_51.notes:
+            # an 88-key roll: the generator reads keys 15..65 of it (Roll2Midi_inference.py:25-38, Roll2Midi_dataset.py:13-14, 89-131)
+            probs = probs[..., PIANO_51.note_min - self.piano.note_min:PIANO_51.note_max - self.piano.note_min + 1].contiguous()
+        return self._r2m.refine(probs, window=window, threshold=threshold, tail=tail)
 
     def piano_frame_preprocessor(self):
         """The `PianoFramePreprocessor` of this model's device (made on first use)."""
         if self._piano_pre is None:
             from .piano_frames import PianoFramePreprocessor
-            self._piano_pre = PianoFramePreprocessor(self._device)
+            self._piano_pre = PianoFramePreprocessor(self._device, layout=self.piano.layout)
         return self._piano_pre
 
     def load_text_encoder(self, src, tokenizer=None):

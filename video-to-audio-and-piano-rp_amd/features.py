@@ -15,9 +15,40 @@ and, for a video without one, `load_piano_frames(video_frames=, preprocess=)` ov
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
+
+
+# ---- the two piano configurations the reference ships ----------------------------------------------------------------------
+class PianoConfig(NamedTuple):
+    """What differs between e2_tts_crossatt3.py (x3) and e2_tts_crossatt3_2.py (x3_2), the same file with three switches flipped:
+    `notes`, `note_min`, `note_max` (`NOTES`, `NOTTE_MIN`, `NOTE_MAX`, :70-76), `video_multi` latent frames per video frame
+    (:1929-1930), `expand` = (rep, group) of encode_frames -- every roll row `rep` times, every `group` of them averaged
+    (:1544-1547) -- and the frame `layout` of the module-level `transform` (:60-68): "landscape" resizes to 900 x 100,
+    "portrait" to 100 wide x 900 tall and transposes, out[i, j] = img[j, i].  Both give (100, 900) frames."""
+    notes: int
+    note_min: int
+    note_max: int
+    video_multi: float
+    expand: tuple
+    layout: str
+
+
+PIANO_51 = PianoConfig(51, 15, 65, 3.0, (3, 1), "landscape")          # x3, trainer_multigpus_alldatas3.py (piano_2h, 25 fps)
+PIANO_88 = PianoConfig(88, 0, 87, 2.5, (5, 2), "portrait")            # x3_2, trainer_multigpus_alldatas3_2.py (piano_20h, 30 fps)
+PIANO_CONFIGS = {51: PIANO_51, 88: PIANO_88}
+
+
+def piano_config(piano_keys) -> PianoConfig:
+    """51 | 88 (or a PianoConfig) -> the configuration; anything else is a ValueError."""
+    if isinstance(piano_keys, PianoConfig):
+        return piano_keys
+    if isinstance(piano_keys, bool) or piano_keys not in PIANO_CONFIGS:
+        raise ValueError(f"piano_keys must be 51 or 88, got {piano_keys!r}")
+    return PIANO_CONFIGS[piano_keys]
+
 
 _SUFFIX = {"clip_vit": ".generated.npz", "clip_vit2": ".generated.clip_vit2.npz",
            "clip_convnext": ".generated.clip_convnext.npz", "dinov2": ".generated.dinov2.npz", "mixed": ".generated.mixed.npz"}
@@ -125,11 +156,12 @@ def piano_frame_indices(n_video_frames: int, duration: float, l: int, start_samp
     return out
 
 
-def piano_frames_from_video(frames, duration: float, l: int, preprocess, start_sample: int = 0, max_sample: int | None = None) -> torch.Tensor:
+def piano_frames_from_video(frames, duration: float, l: int, preprocess, start_sample: int = 0, max_sample: int | None = None,
+                            video_multi: float = 3.0) -> torch.Tensor:
     """One clip's (t_i, Ho, Wo) float32 stack from its decoded frames (F, H, W, 3) uint8: the frames `piano_frame_indices` picks,
     each distinct one resized once by `preprocess(frames, select=[...]) -> (n, Ho, Wo)` (a `PianoFramePreprocessor`) and then
     gathered -- a 30 fps clip repeats no frame, a 12 fps one uses each about twice.  The result stays on preprocess's device."""
-    idx = piano_frame_indices(frames.shape[0], duration, l, start_sample, max_sample)
+    idx = piano_frame_indices(frames.shape[0], duration, l, start_sample, max_sample, video_multi)
     distinct = sorted(set(idx))
     out = preprocess(frames, select=distinct)
     if len(distinct) == len(idx):
@@ -138,15 +170,19 @@ def piano_frames_from_video(frames, duration: float, l: int, preprocess, start_s
     return out[torch.tensor([pos[j] for j in idx], device=out.device)]
 
 
-def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None, write_cache: bool = True) -> torch.Tensor | None:
+def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None, write_cache: bool = True,
+                      video_multi: float = 3.0) -> torch.Tensor | None:
     """Batch form of the `piano` branch of encode_video_frames: (b, 1, t, 100, 900) float32 with
-    t = max(floor(l / 3) + 1, longest clip) and zero frames as padding (x3:1935-1948); `None` paths give all-zero clips
+    t = max(floor(l / video_multi) + 1, longest clip) and zero frames as padding (x3:1935-1948); `None` paths give all-zero clips
     (x3:1939-1941).  Returns None when no path has frames (x3:1927-1928).  Tuples are (path, start_sample, max_sample).
     `video_frames`: one (frames uint8 (F, H, W, 3), duration_s) or None per path, the decoded video of a clip whose cache may be
     missing; such a clip goes through `preprocess` (x3:1877-1891) instead of raising.  With `write_cache` all its F frames are
     resized and saved in the reference's format, so that the reference and the next call read them; without, only the frames the
     clip uses are resized and nothing is written.  An existing cache wins.  The result is on preprocess's device when any clip
-    was preprocessed, else on the CPU."""
+    was preprocessed, else on the CPU.
+    `video_multi` (`PianoConfig.video_multi`): 3.0, or 2.5 for the 88-key configuration, whose `preprocess` is the portrait one.
+    The cache name is the same in both reference files and so are the shapes: a cache written under one configuration is
+    silently wrong under the other, here as there."""
     if video_frames is not None and len(video_frames) != len(video_paths):
         raise ValueError(f"video_frames: {len(video_frames)} entries for {len(video_paths)} video_paths")
     clips, lens = [], []
@@ -162,7 +198,7 @@ def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None
         if os.path.exists(fp):
             data = np.load(fp)
             raw = torch.from_numpy(data["arr_0"])
-            idx = piano_frame_indices(raw.shape[0], data["arr_1"].item(), l, start_sample, max_sample)
+            idx = piano_frame_indices(raw.shape[0], data["arr_1"].item(), l, start_sample, max_sample, video_multi)
             clip = raw[torch.tensor(idx)]
         elif video_frames is not None and video_frames[n] is not None:
             if preprocess is None:
@@ -171,10 +207,10 @@ def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None
             if write_cache:
                 raw = preprocess(fr).unsqueeze(-1)                                # (F, 100, 900, 1), x3:1890
                 save_piano_frames_cache(fp, raw, float(duration))
-                idx = piano_frame_indices(raw.shape[0], float(duration), l, start_sample, max_sample)
+                idx = piano_frame_indices(raw.shape[0], float(duration), l, start_sample, max_sample, video_multi)
                 clip = raw[torch.tensor(idx, device=raw.device)]
             else:
-                clip = piano_frames_from_video(fr, float(duration), l, preprocess, start_sample, max_sample).unsqueeze(-1)
+                clip = piano_frames_from_video(fr, float(duration), l, preprocess, start_sample, max_sample, video_multi).unsqueeze(-1)
         else:
             raise FileNotFoundError(f"{fp}: no cached piano frames for {vp} (the reference decodes the video with moviepy here)")
         clips.append(clip)
@@ -183,7 +219,7 @@ def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None
         return None
     H, W = next(c for c in clips if c is not None).shape[1:3]
     dev = next((c.device for c in clips if c is not None and c.device.type != "cpu"), torch.device("cpu"))
-    t = max(int(l // 3.0) + 1, max(lens))
+    t = max(int(l // video_multi) + 1, max(lens))
     out = torch.zeros(len(clips), t, H, W, 1, device=dev)
     for i, c in enumerate(clips):
         if c is not None:
@@ -192,7 +228,7 @@ def load_piano_frames(video_paths, l: int, *, video_frames=None, preprocess=None
 
 
 # ---- MIDI ground truth of the V2P validation pass (x3:1852-1866) -------------------------------------------------------
-NOTE_MIN, NOTE_MAX = 15, 65          # x3:71-72 (`NOTTE_MIN`, `NOTE_MAX`): the 51 piano keys the roll covers
+NOTE_MIN, NOTE_MAX = PIANO_51.note_min, PIANO_51.note_max          # x3:71-72 (`NOTTE_MIN`, `NOTE_MAX`): the 51 piano keys the roll covers
 
 
 def midi_ground_truth_path(video_path: str) -> str:
@@ -200,17 +236,18 @@ def midi_ground_truth_path(video_path: str) -> str:
     return video_path.replace(".mp4", ".3.npy")
 
 
-def load_midi_ground_truth(video_paths, l: int) -> torch.Tensor | None:
-    """x3:1852-1866: `<video>.3.npy` (frames, 88 keys) -> columns NOTE_MIN..NOTE_MAX as float32, zero padded or cut to `l` frames:
-    (b', l, 51) over the paths that are not None (tuples are (path, start_sample, max_sample)), or None when there is none.  This is
+def load_midi_ground_truth(video_paths, l: int, piano_keys=51) -> torch.Tensor | None:
+    """x3:1852-1866: `<video>.3.npy` (frames, 88 keys) -> columns note_min..note_max of the configuration (15..65, or all 88 with
+    piano_keys=88) as float32, zero padded or cut to `l` frames: (b', l, notes) over the paths that are not None (tuples are (path, start_sample, max_sample)), or None when there is none.  This is
     `midis` of `E2TTS.forward(val=True)`; `E2TTS.encode_video_frames` keeps returning zeros, as the reference's live branch does."""
+    pc = piano_config(piano_keys)
     rows = []
     for vp in video_paths:
         if vp is None:
             continue
         if isinstance(vp, tuple):
             vp = vp[0]
-        gt = torch.from_numpy(np.load(midi_ground_truth_path(vp)).astype(np.float32))[:, NOTE_MIN:NOTE_MAX + 1]
+        gt = torch.from_numpy(np.load(midi_ground_truth_path(vp)).astype(np.float32))[:, pc.note_min:pc.note_max + 1]
         out = torch.zeros(int(l), gt.shape[1])
         k = min(int(l), gt.shape[0])
         out[:k] = gt[:k]

@@ -10,6 +10,10 @@ reference divides a uint8 array by a Python float and casts afterwards).  Roundi
 part of the result: the three channels are never filtered separately.  The coefficient tables are `resample.resample_coeffs`
 (Pillow's `precompute_coeffs` + `normalize_coeffs_8bpc`); a pass Pillow skips (equal sizes) has identity tables here, which give
 the same bytes.
+
+The 88-key configuration (x3_2 = e2_tts_crossatt3_2.py:65-68) resizes to 100 wide x 900 tall and transposes: layout="portrait",
+out[f, i, j] = img[j, i], again (F, 100, 900).  Same arithmetic, other tables (W -> 100, H -> 900); the vertical pass stores
+transposed (`v2a_piano_resize_vt`).  The cache file has the same name and shapes under both layouts (features.load_piano_frames).
 """
 from __future__ import annotations
 
@@ -19,7 +23,8 @@ import torch
 from . import _lib as L
 from .resample import PRECISION_BITS, resample_coeffs, vertical_window
 
-PIANO_HW = (100, 900)          # x3:60: `x.resize((900, 100))`
+PIANO_HW = (100, 900)          # x3:60: `x.resize((900, 100))`; x3_2:65-67: `x.resize((100, 900))`, transposed
+LAYOUTS = ("landscape", "portrait")
 _HALF = 1 << (PRECISION_BITS - 1)
 
 
@@ -36,9 +41,15 @@ def scale_table() -> np.ndarray:
 
 class PianoFramePlan:
     """Host tables of one input size: horizontal bounds / coefficients of all Wo columns, the input rows [y0, y0 + rows) the
-    vertical pass reads, and its bounds relative to y0."""
+    vertical pass reads, and its bounds relative to y0.  Ho, Wo: the shape of an output frame.  layout="portrait": the image is
+    resized to Ho wide x Wo tall and stored transposed, so the tables are those of W -> Ho and H -> Wo."""
 
-    def __init__(self, H: int, W: int, Ho: int = PIANO_HW[0], Wo: int = PIANO_HW[1]):
+    def __init__(self, H: int, W: int, Ho: int = PIANO_HW[0], Wo: int = PIANO_HW[1], layout: str = "landscape"):
+        if layout not in LAYOUTS:
+            raise ValueError(f"layout must be 'landscape' or 'portrait', got {layout!r}")
+        self.layout, self.out_hw = layout, (int(Ho), int(Wo))
+        if layout == "portrait":
+            Ho, Wo = Wo, Ho                                  # from here on: the resized image's rows and columns
         self.H, self.W, self.Ho, self.Wo = int(H), int(W), int(Ho), int(Wo)
         self.hb, self.hk = resample_coeffs(self.W, self.Wo)
         vb, self.vk = resample_coeffs(self.H, self.Ho)
@@ -52,7 +63,8 @@ class PianoFramePlan:
 
     def integer_passes(self, frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """(F, H, W, 3) uint8 -> the sums of both passes after the shift and before the clip, int64 (F, rows, Wo) and
-        (F, Ho, Wo): what `preprocess_numpy` clips, and what tells whether a test image overshoots [0, 255] at all."""
+        (F, Ho, Wo) of the resized image (untransposed): what `preprocess_numpy` clips, and what tells whether a test image
+        overshoots [0, 255] at all."""
         fr = np.asarray(frames)
         if fr.dtype != np.uint8 or fr.ndim != 4 or fr.shape[1:] != (self.H, self.W, 3):
             raise ValueError(f"PianoFramePlan({self.H}, {self.W}): frames must be uint8 (F, {self.H}, {self.W}, 3), got {fr.shape} {fr.dtype}")
@@ -70,16 +82,26 @@ class PianoFramePlan:
 
     def preprocess_numpy(self, frames: np.ndarray) -> np.ndarray:
         """(F, H, W, 3) uint8 RGB -> (F, Ho, Wo) float32, the reference's `frames_raw[:, :, :, 0]`: the pure-integer restatement
-        the kernels follow."""
-        return self.lut[np.clip(self.integer_passes(frames)[1], 0, 255)]
+        the kernels follow.  Portrait: the resized (Wo tall, Ho wide) image transposed (x3_2:66-67)."""
+        out = self.lut[np.clip(self.integer_passes(frames)[1], 0, 255)]
+        return np.ascontiguousarray(out.transpose(0, 2, 1)) if self.layout == "portrait" else out
+
+
+def lib_vpass(layout: str):
+    """The vertical pass of a layout: `v2a_piano_resize_v` stores (n, Ho, Wo), `v2a_piano_resize_vt` the transposed (n, Wo, Ho)."""
+    return L.lib().v2a_piano_resize_vt if layout == "portrait" else L.lib().v2a_piano_resize_v
 
 
 class PianoFramePreprocessor:
     """`__call__(frames, select=None)`: uint8 (F, H, W, 3) RGB frames (tensor or array) -> (n, Ho, Wo) float32 on the device, for
     the frame numbers `select` (any order, repeats allowed) or all F.  Frames are processed `chunk` at a time so that the uint8
-    intermediate of the two passes stays bounded; no arithmetic crosses frames, so the chunk size changes no byte."""
+    intermediate of the two passes stays bounded; no arithmetic crosses frames, so the chunk size changes no byte.
+    layout: "landscape" (x3) or "portrait" (x3_2, the 88-key configuration); (Ho, Wo) is the output frame's shape in both."""
 
-    def __init__(self, device, Ho: int = PIANO_HW[0], Wo: int = PIANO_HW[1], chunk: int = 64):
+    def __init__(self, device, Ho: int = PIANO_HW[0], Wo: int = PIANO_HW[1], chunk: int = 64, layout: str = "landscape"):
+        if layout not in LAYOUTS:
+            raise ValueError(f"layout must be 'landscape' or 'portrait', got {layout!r}")
+        self.layout = layout
         self.device = torch.device(device)
         self.Ho, self.Wo, self.chunk = int(Ho), int(Wo), int(chunk)
         self.frames_done = 0          # frames resized so far (callers and tests count the work)
@@ -90,7 +112,7 @@ class PianoFramePreprocessor:
     def _plan(self, H: int, W: int):
         pl = self._plans.get((H, W))
         if pl is None:
-            p = PianoFramePlan(H, W, self.Ho, self.Wo)
+            p = PianoFramePlan(H, W, self.Ho, self.Wo, self.layout)
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
             if self._lut is None:
                 self._lut = t(p.lut)
@@ -120,7 +142,9 @@ class PianoFramePreprocessor:
             fr, sel, F = fr[uniq], inv, uniq.numel()
         fr = fr.to(self.device).contiguous()
         step = max(1, int(chunk or self.chunk))
-        ldt = -(-self.Wo // 4) * 4
+        # p.Ho, p.Wo are the rows and columns of the resized image: the output's (Ho, Wo), or for portrait the output's (Wo, Ho)
+        ldt = -(-p.Wo // 4) * 4
+        vpass = lib_vpass(self.layout)
         tmp = torch.empty(min(step, n), p.rows, ldt, dtype=torch.uint8, device=self.device)
         whole = sel is None and step >= n
         seld = None if whole else (torch.arange(F, dtype=torch.int32) if sel is None else sel.to(torch.int32)).to(self.device)
@@ -128,9 +152,9 @@ class PianoFramePreprocessor:
         for i in range(0, n, step):
             m = min(step, n - i)
             sp = 0 if whole else seld.data_ptr() + 4 * i
-            L.check(lib.v2a_piano_resize_h(fr.data_ptr(), F, H, W, sp, m, tmp.data_ptr(), ldt, p.y0, p.rows, self.Wo, hb.data_ptr(),
+            L.check(lib.v2a_piano_resize_h(fr.data_ptr(), F, H, W, sp, m, tmp.data_ptr(), ldt, p.y0, p.rows, p.Wo, hb.data_ptr(),
                                            hk.data_ptr(), hk.shape[1], s))
-            L.check(lib.v2a_piano_resize_v(tmp.data_ptr(), m, p.rows, ldt, self.Ho, self.Wo, vb.data_ptr(), vk.data_ptr(), vk.shape[1],
-                                           self._lut.data_ptr(), out[i:i + m].data_ptr(), s))
+            L.check(vpass(tmp.data_ptr(), m, p.rows, ldt, p.Ho, p.Wo, vb.data_ptr(), vk.data_ptr(), vk.shape[1],
+                          self._lut.data_ptr(), out[i:i + m].data_ptr(), s))
         self.frames_done += n
         return out

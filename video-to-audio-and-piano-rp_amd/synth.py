@@ -61,8 +61,9 @@ def synthetic_conditioning(cfg: DiTConfig, b: int, n: int = 750, nc: int = 16, s
     return y0, text, roll, context, context_mask
 
 
-def random_video2roll_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
-    """Seeded weights in the key layout of `Video2RollNet.resnet18(num_classes=51)` (no piano checkpoint is reachable
+def random_video2roll_state_dict(seed: int = 0, num_classes: int = 51) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `Video2RollNet.resnet18(num_classes=51)`, or of the 88-key configuration's
+    `num_classes=88`: `fc.*` are the last keys, so every tensor in front of them is the same for both (no piano checkpoint is reachable
     offline: `./ckpts/piano5_4_2_8000.pt`, predict.py:68).  numpy's legacy RandomState stream, so the same seed gives the
     same tensors on any machine / torch build (the golden vectors of tests/golden/video2roll_*.npz depend on that).
     Conv weights follow the reference init N(0, sqrt(2 / (k*k*out))) (Video2RollNet.py:160-163); BatchNorm scale, shift
@@ -73,7 +74,7 @@ def random_video2roll_state_dict(seed: int = 0) -> dict[str, torch.Tensor]:
 
     rs = np.random.RandomState(seed)
     sd = {}
-    for k, shp in expected_state_dict_shapes().items():
+    for k, shp in expected_state_dict_shapes(num_classes).items():
         if k.endswith("num_batches_tracked"):
             v = np.array(1000, dtype=np.int64)
         elif k.endswith("running_var"):

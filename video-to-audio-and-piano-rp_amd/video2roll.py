@@ -112,9 +112,11 @@ class Video2RollEngine:
     "fp32" (exact-fp32 MFMA over explicit patch matrices).
     chunk: windows per pass.  Default 256 in the bf16 and bf16x3 modes (implicit GEMM: no patch matrix; ~22 MB of activation maps
     per window in bf16, ~29 MB in bf16x3, and one pass per clip measured fastest: 8.8 ms per 251-frame clip vs 13.3 ms at 25 in
-    bf16) and 16 in fp32 mode (the explicit fp32 patch matrix of the first layer is 53 MB per window)."""
+    bf16) and 16 in fp32 mode (the explicit fp32 patch matrix of the first layer is 53 MB per window).
+    expand: (rep, group) of `encode_frames`' expansion in time (`features.PianoConfig.expand`): (3, 1) repeats every row x3
+    (x3:1545), (5, 2) is the 88-key configuration's x2.5 (x3_2:1546-1547).  The number of keys is the checkpoint's (`fc.weight`)."""
 
-    def __init__(self, sd, device="cuda:0", compute="bf16", prefix="", chunk=None):
+    def __init__(self, sd, device="cuda:0", compute="bf16", prefix="", chunk=None, expand=(3, 1)):
         L.lib()                                                   # fail loudly without the HIP library
         self.dev = torch.device(device)
         if compute not in ("bf16", "bf16x3", "fp32"):
@@ -124,6 +126,9 @@ class Video2RollEngine:
         self.cd = torch.float32 if compute == "fp32" else torch.bfloat16
         self.code = L.F32 if compute == "fp32" else L.BF16
         self.chunk = int(chunk) if chunk else (16 if compute == "fp32" else 256)
+        self.expand = (int(expand[0]), int(expand[1]))
+        if self.expand[0] < 1 or self.expand[1] not in (1, 2):
+            raise ValueError(f"expand must be (rep >= 1, group 1 | 2), got {expand!r}")
         sd = {k[len(prefix):]: v.detach().cpu() for k, v in sd.items() if k.startswith(prefix)}
         check_state_dict(sd, expected_state_dict_shapes(sd["fc.weight"].shape[0] if "fc.weight" in sd else NOTES), "Video2RollEngine")
         self.notes = sd["fc.weight"].shape[0]
@@ -366,11 +371,16 @@ class Video2RollEngine:
 
     @torch.no_grad()
     def encode_frames(self, x, l: int):
-        """`E2TTS.encode_frames(x, l)` (x3:1525-1553): x (b, 1, t, H, W) -> roll probabilities (b, l, notes)."""
+        """`E2TTS.encode_frames(x, l)` (x3:1525-1553): x (b, 1, t, H, W) -> roll probabilities (b, l, notes), rows expanded in
+        time by `expand`."""
         b, c, t, H, W = x.shape
         assert c == 1
         frames = x[:, 0].to(self.dev, torch.float32).contiguous()
         roll = self._run(frames, t, True)
         out = torch.empty(b, int(l), self.notes, device=self.dev, dtype=torch.float32)
-        L.roll_expand(roll, out, B=b, t=t, notes=self.notes, rep=3, l=int(l))
+        rep, group = self.expand
+        if group == 1:
+            L.roll_expand(roll, out, B=b, t=t, notes=self.notes, rep=rep, l=int(l))
+        else:
+            L.roll_expand_ratio(roll, out, B=b, t=t, notes=self.notes, rep=rep, group=group, l=int(l))      # x3_2:1546-1554
         return out
