@@ -855,6 +855,33 @@ int v2a_roll2midi_gate(float* x0, int64_t pitch0, int32_t C0, void* shadow0, int
                        void* shadow1, int64_t lo_offset1, const float* w, float bias, int32_t shadow_mode, int32_t n, int32_t H, int32_t W,
                        int32_t border, float* logits, float* alpha, v2a_stream_t stream);
 
+/* =====================================================================================
+ * Note extraction: the link behind Roll2Midi in the reference's Audeo chain, `process_midi` / `process_roll` and `GetNote` of
+ * src/audeo/Midi_synth.py:33-118 -- a binarised key roll -> onsets and offsets -> (key, start, end) rows.
+ * Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+#define V2A_ROLL_NOTES_MAX_KEYS 128
+#define V2A_ROLL_NOTES_TILE 256                 /* frames a workgroup holds in LDS at a time; T itself is not bounded by LDS */
+#define V2A_ROLL_NOTES_MAX_FRAMES (1 << 24)     /* keys * ceil(T / 2) rows of a clip stay inside int32 */
+
+/* roll: element (b, j, i) = clip b, frame j < T, key i < keys at roll[b * batch_stride + j * frame_stride + i * key_stride] (strides in
+ * ELEMENTS: a (B, T, keys) tensor and a transposed (B, keys, T) view are both read in place).  elem_bytes 1: bytes, on iff != 0;
+ * elem_bytes 4: fp32, on iff > threshold (a NaN is off; threshold is ignored for bytes).  lens (B) int32 or NULL: the valid frames of
+ * every clip, clamped to [0, T] (NULL: T); frames at or beyond lens[b] count as off and are not read.
+ *   onset at (j, i):  on at j and (j == 0 or off at j - 1)          Midi_synth.py:54-61, 85-92
+ *   offset at (j, i): j > 0, on at j - 1 and off at j; a key on at frame lens[b] - 1 has its last offset at lens[b]   (:104-105, 115-116)
+ *   notes of key i = (k-th onset, k-th offset), k = 0 .. counts[b][i] - 1                                              (:106, 117)
+ * counts (B, keys) int32; totals (B) int32 = the sum of a clip's counts; notes (B, cap, 3) int32 rows (key, start, end) of clip b from
+ * notes + b * cap * 3 on, ordered by key, then by start.  Rows at or beyond min(totals[b], cap) are NOT written; totals[b] > cap is no
+ * error of this call (it returns 0, totals holds the true count: the caller compares).  cap = 0 with notes NULL: counts only.
+ * onset (B, keys, T) int8 or NULL: +1 at an onset, -1 at an offset at a frame < T, 0 elsewhere -- every element is written (the
+ * reference's `onset.T`).  One launch of B workgroups, no atomics, no host synchronisation; a clip's results do not depend on B or on
+ * the other clips.  keys <= V2A_ROLL_NOTES_MAX_KEYS, T <= V2A_ROLL_NOTES_MAX_FRAMES. */
+int v2a_roll_notes(const void* roll, int32_t elem_bytes, int64_t batch_stride, int64_t frame_stride, int64_t key_stride, float threshold,
+                   int32_t B, int32_t T, int32_t keys, const int32_t* lens, int32_t* counts, int32_t* totals, int32_t* notes, int32_t cap,
+                   int8_t* onset, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,7 @@ EXPORTS = [
     "v2a_roll2midi_stem", "v2a_leaky_shadow", "v2a_roll2midi_head", "v2a_roll2midi_gate",
     "v2a_xattn_absorb_prepare", "v2a_xattn_absorbed",
     "v2a_roll_expand_ratio", "v2a_piano_resize_vt",
+    "v2a_roll_notes",
 ]
 
 
@@ -230,6 +231,7 @@ def _declare(lib):
     lib.v2a_leaky_shadow.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, i64, i32, vp]
     lib.v2a_roll2midi_head.argtypes = [vp, i64, i32, vp, i64, i32, vp, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.v2a_roll2midi_gate.argtypes = [vp, i64, i32, vp, i64, vp, i64, i32, vp, i64, vp, f32, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.v2a_roll_notes.argtypes = [vp, i32, i64, i64, i64, f32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int
@@ -718,6 +720,18 @@ def roll2midi_gate(seg0, seg1, w, *, bias, shadow_mode, n, H, W, border, logits=
     _launch("roll2midi_gate", 2.0 * n * H * W * (c0 + c1), n * H * W * (c0 + c1) * (8.0 + 2 * shadow_mode) + 4.0 * (c0 + c1),
             lambda: lib().v2a_roll2midi_gate(x0.data_ptr(), p0, c0, _p(s0), l0, _p(x1), p1, c1, _p(s1), l1, w.data_ptr(), float(bias),
                                              shadow_mode, n, H, W, border, _p(logits), _p(alpha), stream_ptr()))
+
+
+# ---- note extraction behind Roll2Midi (midi.py) --------------------------------------------------
+ROLL_NOTES_MAX_KEYS, ROLL_NOTES_TILE, ROLL_NOTES_MAX_FRAMES = 128, 256, 1 << 24      # V2A_ROLL_NOTES_* of include/v2a_cfm.h
+
+
+def roll_notes(roll, counts, totals, notes, *, strides, B, T, keys, cap, threshold=0.0, lens=None, onset=None):
+    """One v2a_roll_notes launch.  roll: uint8 or fp32 tensor read at b * strides[0] + frame * strides[1] + key * strides[2] elements;
+    counts (B, keys), totals (B), notes (B, cap, 3) int32 (None with cap = 0), lens (B) int32 or None, onset (B, keys, T) int8 or None."""
+    _launch("roll_notes<%s>" % ("f32" if roll.dtype == torch.float32 else "u8"), 0.0, 2.0 * B * T * keys * roll.element_size(),
+            lambda: lib().v2a_roll_notes(roll.data_ptr(), roll.element_size(), strides[0], strides[1], strides[2], float(threshold), B, T, keys,
+                                         _p(lens), counts.data_ptr(), totals.data_ptr(), _p(notes), cap, _p(onset), stream_ptr()))
 
 
 # ---- N1: Encodec decoder (vocoder) ---------------------------------------------------------------

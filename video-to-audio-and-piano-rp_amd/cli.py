@@ -45,6 +45,10 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
                      the attention-gated one its trainer writes (Roll2MidiNet_enhance.py); the keys tell which.  The per-frame key
                      probabilities of the Video2Roll encoder go through it on the GPU and `<name>.midi.npz` is written next to each output:
                      `midi` (t, 51) uint8, the reference's key name (Roll2Midi_inference.py:79), and `prob` (t, 51) float32.
+  --midi-file {midi,roll}   (with --piano) the next link, src/audeo/Midi_synth.py up to its FluidSynth rendering: the notes of the roll
+                     (one v2a_roll_notes launch per batch) written as `<name>.mid`, a format-1 Standard MIDI File at tempo 80, program 0,
+                     velocity 100 (Midi_synth.py:136-148).  midi: the notes of the Roll2Midi roll (needs --roll2midi); roll: the notes
+                     of the Video2Roll encoder's own roll, probability >= 0.4 -- Midi_synth.py's shipped default -- without a generator.
 The moviepy mux of audio and video stays outside (out of scope).
 """
 from __future__ import annotations
@@ -256,18 +260,37 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--roll2midi", default=None, metavar="CKPT", help="with --piano: checkpoint (or state dict) of the Roll2Midi generator "
                     "(`state_dict_G` of Roll2MidiNet.py or of Roll2MidiNet_enhance.py, told apart by its keys): also write <name>.midi.npz with `midi` (t, 51) uint8 and `prob` (t, 51) float32 per video frame")
     ap.add_argument("--roll2midi-dtype", default="bf16x3", choices=["fp32", "bf16", "bf16x3"], help="compute mode of the Roll2Midi generator")
+    ap.add_argument("--midi-file", default=None, choices=["midi", "roll"],
+                    help="with --piano: also write <name>.mid, a Standard MIDI File of the clip's notes (Midi_synth.py up to the FluidSynth "
+                         "rendering): midi = from the Roll2Midi generator's roll (needs --roll2midi), roll = from the Video2Roll encoder's "
+                         "own roll, probability >= 0.4 (the reference's shipped default)")
     return ap
 
 
-def write_midi_rolls(model, frames, video_paths, out_dir) -> list:
-    """--roll2midi: `E2TTS.frames_to_midi` over the --piano stack of a batch -> `<out_dir>/<name>.midi.npz` per clip."""
+def write_midi_rolls(model, frames, video_paths, out_dir, midi_file: bool = False) -> list:
+    """--roll2midi: `E2TTS.frames_to_midi` over the --piano stack of a batch -> `<out_dir>/<name>.midi.npz` per clip.
+    midi_file (--midi-file midi): the notes of the same roll, taken on the device, also go to `<out_dir>/<name>.mid`."""
     probs, midi = model.frames_to_midi(frames)
+    notes = model.midi_to_notes(midi) if midi_file else None
     probs, midi = probs.cpu().numpy(), midi.cpu().numpy()
     paths = []
     for i, vp in enumerate(video_paths):
         name = vp.rsplit("/", 1)[-1].rsplit(".", 1)[0]
         paths.append(os.path.join(out_dir, name + ".midi.npz"))
         np.savez(paths[-1], midi=midi[i], prob=probs[i])
+    if midi_file:
+        paths += write_note_files(notes, video_paths, out_dir, model.piano_spf)
+    return paths
+
+
+def write_note_files(notes, video_paths, out_dir, spf) -> list:
+    """--midi-file: one clip's rows (pitch, start_frame, end_frame) per video -> `<out_dir>/<name>.mid` (midi.write_midi)."""
+    from .midi import write_midi
+    paths = []
+    for one, vp in zip(notes, video_paths):
+        name = vp.rsplit("/", 1)[-1].rsplit(".", 1)[0]
+        paths.append(os.path.join(out_dir, name + ".mid"))
+        write_midi(paths[-1], one, spf)
     return paths
 
 
@@ -285,6 +308,12 @@ def main(argv=None):
 
     if a.roll2midi and not a.piano:
         ap.error("--roll2midi needs --piano (the frames the Video2Roll encoder reads)")
+
+    if a.midi_file and not a.piano:
+        ap.error("--midi-file needs --piano (the frames the Video2Roll encoder reads)")
+
+    if a.midi_file == "midi" and not a.roll2midi:
+        ap.error("--midi-file midi needs --roll2midi (the generator whose roll the notes are taken from); --midi-file roll does without")
 
     if a.validate and int(os.environ.get("WORLD_SIZE", 1)) > 1:
         ap.error("--validate runs on one rank")
@@ -367,7 +396,9 @@ def main(argv=None):
                                           model.piano.video_multi)
             decoded.clear()
             if a.roll2midi and frames is not None and not a.validate:
-                written += write_midi_rolls(model, frames, [vp for vp, _ in mine], a.out_dir)
+                written += write_midi_rolls(model, frames, [vp for vp, _ in mine], a.out_dir, midi_file=a.midi_file == "midi")
+            if a.midi_file == "roll" and frames is not None and not a.validate:
+                written += write_note_files(model.frames_to_notes(frames, source="roll"), [vp for vp, _ in mine], a.out_dir, model.piano_spf)
             if a.validate:
                 import json
                 print(json.dumps(dict(batch=b0 // a.batch, **validate_batch(model, [vp for vp, _ in mine], extras, frames, a.wav))), flush=True)

@@ -394,6 +394,40 @@ class E2TTS:
             probs = probs[..., PIANO_51.note_min - self.piano.note_min:PIANO_51.note_max - self.piano.note_min + 1].contiguous()
         return self._r2m.refine(probs, window=window, threshold=threshold, tail=tail)
 
+    @property
+    def piano_spf(self) -> float:
+        """Seconds per video frame of the piano configuration: video_multi latent frames of 320 samples at 24 kHz -- 0.04 (25 fps,
+        the `spf` of Midi_synth.py:29) under piano_keys=51, 1 / 30 under 88."""
+        return self.piano.video_multi * 320 / 24000
+
+    def midi_to_notes(self, midi, lens=None):
+        """The (b, t, 51) `midi` of `frames_to_midi` -> one (n_i, 3) int32 array of (pitch, start_frame, end_frame) per clip, keys
+        15..65 = pitches 36..86: `process_midi` and `GetNote` of Midi_synth.py:66-118 in one launch (midi.roll_to_notes).  lens (b):
+        the valid video frames of every clip."""
+        from .features import PIANO_51
+        from .midi import roll_to_notes
+        if midi.ndim != 3 or midi.shape[2] != PIANO_51.notes:
+            raise ValueError(f"midi_to_notes: the (b, t, {PIANO_51.notes}) output of frames_to_midi, got {tuple(midi.shape)}")
+        return roll_to_notes(midi, lens, note_min=PIANO_51.note_min, device=self._device)
+
+    def frames_to_notes(self, frames, source: str = "midi", lens=None, **kw):
+        """(b, 1, t, 100, 900) grey piano frames -> the notes of every clip, rows (pitch, start_frame, end_frame); a frame lasts
+        `piano_spf` seconds.  source="midi": `frames_to_midi(frames, **kw)` and `midi_to_notes`, the roll staying on the device in
+        between (Midi_synth.py with `self.midi = True`).  source="roll": the file's shipped default (`self.midi = False`, :14), the
+        Video2Roll encoder's own roll -- probability >= 0.4 (Video2Roll_inference.py:71-78) over the model's keys, 51 from key 15 or
+        88 from key 0 -- and no Roll2Midi generator."""
+        from .midi import ROLL_THRESHOLD_BELOW, roll_to_notes
+        if source == "midi":
+            return self.midi_to_notes(self.frames_to_midi(frames, **kw)[1], lens)
+        if source != "roll":
+            raise ValueError(f"frames_to_notes: source is 'midi' or 'roll', got {source!r}")
+        if kw:
+            raise TypeError(f"frames_to_notes(source='roll') takes no {sorted(kw)}: they are frames_to_midi's")
+        if self._v2r_sd is None:
+            raise NotImplementedError("frames_to_notes needs the Video2Roll encoder: load a checkpoint holding `video2roll_net.*` (load_state_dict)")
+        probs = self._video2roll().frame_probs(frames)
+        return roll_to_notes(probs, lens, threshold=ROLL_THRESHOLD_BELOW, note_min=self.piano.note_min)
+
     def piano_frame_preprocessor(self):
         """The `PianoFramePreprocessor` of this model's device (made on first use)."""
         if self._piano_pre is None:
