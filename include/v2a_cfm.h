@@ -446,6 +446,25 @@ int v2a_cfg_euler(float* y, const float* pred, int32_t B, int32_t T, int32_t C,
                   int64_t pred_batch_stride, int32_t row_off, float cfg_strength,
                   const float* dt, const int32_t* step, const double* apg,
                   float keep_parallel_frac, v2a_stream_t stream);
+/* Additive to ABI 9: v2a_cfg_euler that also stores the operand planes of the y it has just updated (V2A_BF16_SPLIT, the rounding of
+ * v2a_split_bf16, 8-byte vector stores): element (b, i, c) goes to row (k * B + b) * rows_per_seq + row_off + i of `planes` for every
+ * copy k < copies, hi plane at column c, lo plane at column lo_offset + c; rows outside [row_off, row_off + T) of a sequence are not
+ * touched.  The DiT engine's folded layer-0 GEMMs read these rows as their K = C operand: row_off = registers, rows_per_seq = registers +
+ * frames, copies = 2 (the conditional and the null half of the CFG batch both hold y).  y is updated exactly as by v2a_cfg_euler; with
+ * planes == NULL (or a NULL struct) the call IS v2a_cfg_euler. */
+typedef struct v2a_y_planes {
+  void* planes;          /* bf16 rows, 8-byte aligned */
+  int64_t ld;            /* row pitch in elements, >= lo_offset + C, % 4 == 0 */
+  int64_t lo_offset;     /* elements from the hi plane of a row to its lo plane, >= C, % 4 == 0 */
+  int32_t row_off;       /* first row of y inside every sequence */
+  int32_t rows_per_seq;  /* >= row_off + T */
+  int32_t copies;        /* 1 or 2 stacked batches of B sequences */
+  int32_t reserved;
+} v2a_y_planes;
+int v2a_cfg_euler_planes(float* y, const float* pred, int32_t B, int32_t T, int32_t C,
+                         int64_t pred_batch_stride, int32_t row_off, float cfg_strength,
+                         const float* dt, const int32_t* step, const double* apg,
+                         float keep_parallel_frac, const v2a_y_planes* planes, v2a_stream_t stream);
 /* y[r][0:d] = hi, y[r][d:2d] = lo of x[r][0:d] (V2A_BF16_SPLIT layout above), rows x d fp32 in, row strides in elements,
  * d % 4 == 0: the split operand copy of an fp32 buffer (residual streams, attention outputs, GEGLU hidden) for the
  * three-segment bf16 GEMMs of the bf16x3 mode */

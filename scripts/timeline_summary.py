@@ -13,6 +13,20 @@ def short(n):
     m = re.search(r"(gemm_bf16_dma_kernel<[^>]*>|gemm_bf16_dma_kernelI\w+?E{2}|gemm_bf16_8ph_kernel<[^>]*>|gemm_bf16_8ph_kernelI\w+?E{2}|attn_mfma\w*<[^>]*>|dwconv|rmsnorm|rope|cfg_euler|linear_small|step_adv|cast)", n)
     return (m.group(1) if m else n)[:44]
 print("eval wall us %.1f  kernels %d" % ((t1 - t0) / 1e3, len(ev)))
+# the seam between two evaluations: from the end of the audio stream's last feed-forward-out GEMM (the last GEMM but one of an evaluation: to_pred
+# follows it) to the start of the next evaluation's first depthwise conv -- to_pred, CFG + Euler, the step counter and the head of layer 0, short
+# dependent launches on an otherwise empty chip
+def seam(lo, mid, hi):
+    gemms = [r for r in rows[lo + 1:mid + 1] if "gemm_" in r["Kernel_Name"]]
+    conv = [r for r in rows[mid + 1:hi + 1] if "dwconv" in r["Kernel_Name"]]
+    if len(gemms) < 2 or not conv:
+        return None
+    head = rows[mid + 1:rows.index(conv[0])]
+    return (int(conv[0]["Start_Timestamp"]) - int(gemms[-2]["End_Timestamp"])) / 1e3, [short(r["Kernel_Name"]) for r in head]
+seams = [s for s in (seam(adv[i], adv[i + 1], adv[i + 2]) for i in range(max(0, len(adv) - 8), len(adv) - 2)) if s]
+if seams:
+    print("seam (last feed-forward-out GEMM end -> first dwconv start of the next evaluation) us: %s; kernels between the step counter and that dwconv: %s"
+          % (" ".join("%.1f" % s[0] for s in seams), ", ".join(seams[-1][1])))
 q = collections.defaultdict(list)
 for r in ev:
     q[r["Queue_Id"]].append(r)

@@ -112,6 +112,12 @@ class XattnAbsorbedArgs(C.Structure):
                 ("row_ssq", C.c_void_p), ("ld_row_ssq", C.c_int64), ("row_ssq_parts", C.c_int32), ("row_norm_dim", C.c_int32)]
 
 
+class YPlanes(C.Structure):
+    """Mirror of `v2a_y_planes`: where v2a_cfg_euler_planes stores the operand planes of the updated y."""
+    _fields_ = [("planes", C.c_void_p), ("ld", C.c_int64), ("lo_offset", C.c_int64), ("row_off", C.c_int32), ("rows_per_seq", C.c_int32),
+                ("copies", C.c_int32), ("reserved", C.c_int32)]
+
+
 class T5AttnArgs(C.Structure):
     """Mirror of `v2a_t5_attn_args`."""
     _fields_ = [
@@ -151,6 +157,7 @@ EXPORTS = [
     "v2a_xattn_absorb_prepare", "v2a_xattn_absorbed",
     "v2a_roll_expand_ratio", "v2a_piano_resize_vt",
     "v2a_roll_notes",
+    "v2a_cfg_euler_planes",
 ]
 
 
@@ -192,6 +199,7 @@ def _declare(lib):
     lib.v2a_time_cond.argtypes = [vp, i32, vp, vp, vp, vp, i32, vp]
     lib.v2a_apg_reduce.argtypes = [vp, vp, i32, i32, i32, i64, i32, vp, vp]
     lib.v2a_cfg_euler.argtypes = [vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, f32, vp]
+    lib.v2a_cfg_euler_planes.argtypes = [vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, f32, C.POINTER(YPlanes), vp]
     lib.v2a_step_advance.argtypes = [vp, vp]
     lib.v2a_cast_bf16.argtypes = [vp, vp, i64, vp]
     lib.v2a_split_bf16.argtypes = [vp, i64, vp, i64, i64, i32, vp]
@@ -625,10 +633,18 @@ def apg_reduce(pred, apg, *, B, T, C_, pred_batch_stride, row_off, valid_rows=No
     check(lib().v2a_apg_reduce(pred.data_ptr(), apg.data_ptr(), B, T, C_, pred_batch_stride, row_off, _p(valid_rows), stream_ptr()))
 
 
-def cfg_euler(y, pred, *, B, T, C_, pred_batch_stride, row_off, cfg_strength, dt, step=None, apg=None, keep=0.0):
-    _launch("cfg_euler", 0.0, 16.0 * B * T * C_,
-            lambda: lib().v2a_cfg_euler(y.data_ptr(), pred.data_ptr(), B, T, C_, pred_batch_stride, row_off,
-                                        float(cfg_strength), dt.data_ptr(), _p(step), _p(apg), float(keep), stream_ptr()))
+def cfg_euler(y, pred, *, B, T, C_, pred_batch_stride, row_off, cfg_strength, dt, step=None, apg=None, keep=0.0, planes=None):
+    """planes = dict(out, ld, lo_offset, row_off, rows_per_seq, copies) or None: the hi | lo bf16 planes of the updated y as well, into
+    rows [row_off, row_off + T) of every one of copies * B sequences of rows_per_seq rows of `out` (v2a_cfg_euler_planes)."""
+    if planes is None:
+        _launch("cfg_euler", 0.0, 16.0 * B * T * C_,
+                lambda: lib().v2a_cfg_euler(y.data_ptr(), pred.data_ptr(), B, T, C_, pred_batch_stride, row_off,
+                                            float(cfg_strength), dt.data_ptr(), _p(step), _p(apg), float(keep), stream_ptr()))
+        return
+    pl = YPlanes(planes["out"].data_ptr(), planes["ld"], planes["lo_offset"], planes["row_off"], planes["rows_per_seq"], planes["copies"], 0)
+    _launch("cfg_euler", 0.0, (16.0 + 4.0 * planes["copies"]) * B * T * C_,
+            lambda: lib().v2a_cfg_euler_planes(y.data_ptr(), pred.data_ptr(), B, T, C_, pred_batch_stride, row_off, float(cfg_strength),
+                                               dt.data_ptr(), _p(step), _p(apg), float(keep), C.byref(pl), stream_ptr()))
 
 
 def step_advance(step):

@@ -595,16 +595,11 @@ __global__ __launch_bounds__(256) void time_cond_kernel(const float* __restrict_
 // (Round 5 measured the step counter advanced by this launch itself -- every block counts in through a device atomic once it has used
 // step[0], the last one increments -- instead of by the one-thread launch behind it: 750 same-address atomics cost the launch ~3 us
 // (8.3 against 5.2 us at 8 clips, profiles/r05_kernel_stats_bf16x3_8clips_singlestream.csv), as much as the launch they replace.  Not kept.)
-__global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ y, const float* __restrict__ pred, int B,
-                                                        int T, int C, int64_t pbs, int row_off, float s,
-                                                        const float* __restrict__ dt, const int32_t* step,
-                                                        const double* apg, float keep) {
-  const int64_t idx4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t per_b = (int64_t)T * C;
-  const int64_t total4 = (int64_t)B * per_b / 4;
-  if (idx4 >= total4) return;
-  const int64_t e = idx4 * 4;
-  const int64_t b = e / per_b, r = e % per_b;
+// One thread's four latent elements of clip b starting at element r of the clip: the updated y, stored and returned.  Shared by the plain
+// kernel and the one that also writes y's operand planes, so that both update y with the same instructions.
+__device__ __forceinline__ f32x4 cfg_euler_update(float* __restrict__ y, const float* __restrict__ pred, int B, int C, int64_t pbs,
+                                                  int row_off, float s, const float* __restrict__ dt, const int32_t* step,
+                                                  const double* apg, float keep, int64_t e, int64_t b, int64_t r) {
   const float h = dt[step ? step[0] : 0];
   const f32x4 pc = *reinterpret_cast<const f32x4*>(pred + b * pbs + (int64_t)row_off * C + r);
   const f32x4 pn = *reinterpret_cast<const f32x4*>(pred + (b + B) * pbs + (int64_t)row_off * C + r);
@@ -626,6 +621,51 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ y, c
     yv[j] += h * (pc[j] + upd * s);
   }
   *reinterpret_cast<f32x4*>(y + e) = yv;
+  return yv;
+}
+
+__global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ y, const float* __restrict__ pred, int B,
+                                                        int T, int C, int64_t pbs, int row_off, float s,
+                                                        const float* __restrict__ dt, const int32_t* step,
+                                                        const double* apg, float keep) {
+  const int64_t idx4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t per_b = (int64_t)T * C;
+  const int64_t total4 = (int64_t)B * per_b / 4;
+  if (idx4 >= total4) return;
+  const int64_t e = idx4 * 4;
+  cfg_euler_update(y, pred, B, C, pbs, row_off, s, dt, step, apg, keep, e, e / per_b, e % per_b);
+}
+
+// ... and the hi | lo bf16 planes of the updated y (split_bf16_kernel's rounding) into the rows of `copies` stacked batches of B sequences of
+// rows_per_seq rows each, plane_row_off rows into every sequence: the A operand of the next evaluation's folded layer-0 GEMMs (DiTEngine),
+// whose conditional and null halves both read y.  8-byte vector stores; the rows in front of plane_row_off are not touched.
+__global__ __launch_bounds__(256) void cfg_euler_planes_kernel(float* __restrict__ y, const float* __restrict__ pred, int B,
+                                                               int T, int C, int64_t pbs, int row_off, float s,
+                                                               const float* __restrict__ dt, const int32_t* step,
+                                                               const double* apg, float keep, bf16_t* __restrict__ planes,
+                                                               int64_t ldp, int64_t lo_off, int plane_row_off, int rows_per_seq, int copies) {
+  const int64_t idx4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t per_b = (int64_t)T * C;
+  const int64_t total4 = (int64_t)B * per_b / 4;
+  if (idx4 >= total4) return;
+  const int64_t e = idx4 * 4;
+  const int64_t b = e / per_b, r = e % per_b;
+  float sv = s;
+  asm volatile("" : "+v"(sv));      // a register of its own: as the high half of a loaded argument pair, s made the packed FMAs of the update
+                                    // take the high-half broadcast form tests/test_isa_guard.py forbids
+  const f32x4 yv = cfg_euler_update(y, pred, B, C, pbs, row_off, sv, dt, step, apg, keep, e, b, r);
+  bf16x4 hi, lo;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    hi[j] = (bf16_t)yv[j];
+    lo[j] = (bf16_t)(yv[j] - (float)hi[j]);
+  }
+  const int64_t t = r / C, c = r % C;       // C % 4 == 0: the four elements lie in one row
+  for (int k = 0; k < copies; ++k) {
+    bf16_t* row = planes + (((int64_t)k * B + b) * rows_per_seq + plane_row_off + t) * ldp + c;
+    *reinterpret_cast<bf16x4*>(row) = hi;
+    *reinterpret_cast<bf16x4*>(row + lo_off) = lo;
+  }
 }
 
 __global__ __launch_bounds__(256) void apg_reduce_kernel(const float* __restrict__ pred, double* __restrict__ apg, int B,
@@ -917,6 +957,27 @@ extern "C" int v2a_cfg_euler(float* y, const float* pred, int32_t B, int32_t T, 
   hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, pred,
                      B, T, C, pbs, row_off, cfg_strength, dt, step, apg, keep);
   return v2a_check_launch("v2a_cfg_euler");
+}
+
+extern "C" int v2a_cfg_euler_planes(float* y, const float* pred, int32_t B, int32_t T, int32_t C, int64_t pbs, int32_t row_off,
+                                    float cfg_strength, const float* dt, const int32_t* step, const double* apg, float keep,
+                                    const v2a_y_planes* pl, v2a_stream_t stream) {
+  if (!pl || !pl->planes)       // no plane outputs: the plain launch, bit for bit
+    return v2a_cfg_euler(y, pred, B, T, C, pbs, row_off, cfg_strength, dt, step, apg, keep, stream);
+  V2A_REQUIRE(y && pred && dt, "v2a_cfg_euler_planes: null pointer");
+  V2A_REQUIRE(B > 0 && T > 0 && C > 0 && C % 4 == 0 && pbs % 4 == 0, "v2a_cfg_euler_planes: B=%d T=%d C=%d", B, T, C);
+  V2A_REQUIRE(((uintptr_t)pl->planes & 7) == 0 && pl->ld % 4 == 0 && pl->lo_offset % 4 == 0 && pl->lo_offset >= C &&
+                  pl->ld >= pl->lo_offset + (int64_t)C,
+              "v2a_cfg_euler_planes: planes need 8-byte alignment, lo_offset (%lld) >= C, ld (%lld) >= lo_offset + C, both multiples of 4",
+              (long long)pl->lo_offset, (long long)pl->ld);
+  V2A_REQUIRE(pl->row_off >= 0 && pl->rows_per_seq >= pl->row_off + (int64_t)T && pl->copies >= 1 && pl->copies <= 2,
+              "v2a_cfg_euler_planes: row_off=%d rows_per_seq=%d copies=%d (rows_per_seq >= row_off + T, 1 or 2 copies)", pl->row_off,
+              pl->rows_per_seq, pl->copies);
+  const int64_t total4 = (int64_t)B * T * C / 4;
+  hipLaunchKernelGGL(cfg_euler_planes_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, pred,
+                     B, T, C, pbs, row_off, cfg_strength, dt, step, apg, keep, (bf16_t*)pl->planes, pl->ld, pl->lo_offset, pl->row_off,
+                     pl->rows_per_seq, pl->copies);
+  return v2a_check_launch("v2a_cfg_euler_planes");
 }
 
 extern "C" int v2a_step_advance(int32_t* step, v2a_stream_t stream) {

@@ -94,6 +94,35 @@ def pack_weight(w, dev, cd, split=False):
     return L.split_planes(w).contiguous().to(dev)
 
 
+def fold_embed_weights(sd, dim):
+    """float64 (G_a, G_t, G_f): layer 0's three cross-condition Linears applied to proj_in, [N][C] each.  x0 = W_in y + (bias + position) is
+    read by nothing but those three GEMMs, so their outputs are  table(y = 0) + y G^T  with
+        G_a = (I + W_tfa[:, :D]) W_in   (the residual x0 rides along),   G_t = W_at[:, :D] W_in,   G_f = W_af[:, :D] W_in
+    (DiTEngine.begin_steps: K = num_channels instead of D + dim_text + dim_frames on the head of every evaluation)."""
+    P = "transformer.layers.0.1.5"
+    w_in = sd["proj_in.weight"].double()
+    tfa, at, af = (sd[f"{P}.{n}.weight"].double()[:, :dim] for n in ("text_frames_to_audio", "audio_to_text", "audio_to_frames"))
+    return w_in + tfa @ w_in, at @ w_in, af @ w_in
+
+
+def y_plane_rows(B, T, N, R, copies=2):
+    """Rows of the (copies * B * N)-row operand buffer that hold the planes of y[b, t]: (copies, B, T).  Every sequence has N = R + T
+    rows, its R register rows stay zero; the conditional and the null half of a CFG batch (copies = 2) both hold y."""
+    seq = torch.arange(copies * B).reshape(copies, B, 1)
+    return seq * N + R + torch.arange(T).reshape(1, 1, T)
+
+
+def same_grid(cached, t_points, dt):
+    """Whether prepare() was last run on this plan with the same host-side grid (t_points, dt): the time conditioning and the two modulation
+    tables depend on nothing else.  Device-resident grids are never compared (that would synchronise): they recompute."""
+    if cached is None or t_points.device.type != "cpu" or (dt is not None and dt.device.type != "cpu"):
+        return False
+    ct, cdt = cached
+    if (cdt is None) != (dt is None) or ct.shape != t_points.shape:
+        return False
+    return bool(torch.equal(ct, t_points.to(torch.float32))) and (dt is None or bool(torch.equal(cdt, dt.to(torch.float32))))
+
+
 class _Attn:
     """Packed weights of one x-transformers Attention (A1, A5 of SURVEY 8c)."""
 
@@ -228,6 +257,11 @@ class PackedWeights:
             self.xattn_wo = torch.stack([ly["a_attn2"].wo32 for ly in self.layers]).to(dev).contiguous()
         for ly in self.layers:
             ly["a_attn2"].wk = ly["a_attn2"].wv = ly["a_attn2"].wq32 = ly["a_attn2"].wo32 = None
+        # bf16x3 mode, num_channels a whole number of 64-wide K stages: proj_in folded into layer 0's cross-condition weights, formed in
+        # float64 from the fp32 masters like x_skip above (G_a, G_t, G_f as hi | lo planes; DiTEngine.fold_embed)
+        self.fold_g = None
+        if split and c.num_channels % 64 == 0 and c.depth >= 2:
+            self.fold_g = tuple(pk(g.float()) for g in fold_embed_weights(sd, c.dim))
 
 
 # ---- measured tile choices, in ONE place -----------------------------------------------------------------------------------------
@@ -345,6 +379,11 @@ class DiTEngine:
         # (v2a_xattn_absorbed) and one K = H*KP out-projection per clip: see _absorb().  Independent of fuse_xattn, which chooses the form
         # of the unabsorbed path.  V2A_ABSORB_XATTN=0 in the environment turns the default off (A/B runs of an unchanged bench.py).
         self.absorb_xattn = os.environ.get("V2A_ABSORB_XATTN", "1") != "0"
+        # bf16x3 mode, CFG batch, num_channels % 64 == 0: embed() folded into layer 0's cross-condition on a plan armed by begin_steps() --
+        # the three GEMMs at the head of an evaluation read the K = num_channels planes of y (written by cfg_euler) against G_a / G_t / G_f
+        # and add the tables prepare(fold_embed=True) computed at y = 0; no linear_small / split_bf16 per evaluation.  A caller that runs
+        # prepare() -> euler_step() without begin_steps() keeps the unfolded sequence.  V2A_FOLD_EMBED=0 turns the default off (A/B runs).
+        self.fold_embed = os.environ.get("V2A_FOLD_EMBED", "1") != "0"
         # x_at / x_af cross-condition GEMMs on the side streams (True: all three on the main stream, -2.2 %)
         self.cross_on_main = False
         # capture order: audio {cross .. self-attention}, sides {conv, norm, attention}, audio {cross-attention, feed-forward},
@@ -382,6 +421,7 @@ class DiTEngine:
             self.plans.move_to_end(key)
             self.plan = p
             self._alloc_absorbed(p)     # absorb_xattn may have been switched on since the plan was made
+            self._alloc_folded(p)       # ... and fold_embed
             return p
         c, dev, cd = self.cfg, self.dev, self.cd
         R = c.num_registers
@@ -427,6 +467,10 @@ class DiTEngine:
         p["ctx_kv"] = e(B * nc, 2 * c.depth * inner, dt=self.ad)
         p["xattn_kp"] = 0
         self._alloc_absorbed(p)
+        # folded embed: armed by begin_steps(), disarmed by prepare(); c0_ok = the tables hold this prepare()'s offsets; grid_host = the
+        # host grid the time / modulation tables were last computed for (same_grid)
+        p["armed"], p["c0_ok"], p["grid_host"] = False, False, None
+        self._alloc_folded(p)
         p["ctx"] = e(B * nc, w2 * c.ctx_dim, dt=cd)
         p["ctx_len"] = torch.full((B,), nc, dtype=torch.int32, device=dev)
         p["pred"] = e(Bt, N, c.num_channels)
@@ -468,7 +512,7 @@ class DiTEngine:
         p = self.plan
         return (p["ragged"], p["has_cond"], p["per_sample_t"], self.multi_stream, self.side_tile, tuple(sorted(self.side_tiles.items())),
                 tuple(sorted(self.big_tiles.items())), tuple(sorted(self.split_tiles.items())), tuple(sorted(self.split_big_tiles.items())), self.main_tile, self.fold_norm, self.fold_gemm_all, self.fuse_skip, self.fuse_xattn, self.cross_on_main,
-                self.interleave_capture, self.rope_cross, self.zero_masked_queries, self.absorb_xattn, p["xattn_kp"])
+                self.interleave_capture, self.rope_cross, self.zero_masked_queries, self.absorb_xattn, p["xattn_kp"], self.fold_embed, p["armed"])
 
     # --------------------------------------------------------------------------- primitives
     def _rows(self, t):
@@ -662,6 +706,25 @@ class DiTEngine:
         p["wvo"] = e(p["B"], c.depth, c.dim, 2 * c.heads * kp)
         p["xp"] = e(p["B"] * p["N"], 2 * c.heads * kp)
 
+    def _fold_ok(self, p):
+        """Whether the plan takes the folded embed: the switch, split operands with G packed (bf16x3, num_channels % 64 == 0, depth >= 2),
+        the CFG batch (both halves hold y) and one grid point for all sequences."""
+        return self.fold_embed and self.split and self.W.fold_g is not None and p["cfg_mode"] and not p.get("per_sample_t", False)
+
+    def _alloc_folded(self, p):
+        """Buffers of the folded embed, only for a plan that can take it: `ybuf`, the hi | lo planes of y as (Bt * N, 2 C) operand rows with
+        zero register rows (written once here; begin_steps() and cfg_euler write the frame rows), the three fp32 offset tables of layer 0's
+        cross-condition outputs at y = 0 (filled by prepare(fold_embed=True)) and the zero latent they are computed from."""
+        c = self.cfg
+        if "ybuf" in p or not self._fold_ok(p):
+            return
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=self.dev)
+        C_ = c.num_channels
+        p["ybuf"] = L.Operand(z(p["rows"], 2 * C_, dt=self.cd), 2 * C_, C_)
+        p["y_zero"] = z(p["B"], p["T"], C_)
+        for s, d in (("a", c.dim), ("t", c.dim_text), ("f", c.dim_frames)):
+            p[f"c0_{s}"] = torch.empty(p["Bt"], p["N"], d, dtype=torch.float32, device=self.dev)
+
     def _audio_cross_attention_absorbed(self, i, ly, x, nctx, cons2, fold2, lens):
         """The absorbed form of _audio_cross_attention: P sigmoid(gate) over the key slots (one launch), then per clip the K = H*KP
         out-projection against Wvo of (clip, layer) with the gate / residual / folded-norm epilogue of the unabsorbed out-projection."""
@@ -741,7 +804,7 @@ class DiTEngine:
 
     # ------------------------------------------------------------------------------ prepare
     def prepare(self, text, frames_roll, context, context_mask, t_points, *, lens=None,
-                drop_text=None, drop_ctx=None, dt=None, step_cond=None, rope_len=None, rope_ctx_len=None):
+                drop_text=None, drop_ctx=None, dt=None, step_cond=None, rope_len=None, rope_ctx_len=None, fold_embed=False):
         """Everything that is constant over the Euler loop.
         text (B,T,Dt) f32 CLIP features, frames_roll (B,T,51) f32, context (B,nc,ctx) f32,
         context_mask (B,nc) bool (prefix form), t_points (S,) f32 (host or device),
@@ -752,22 +815,32 @@ class DiTEngine:
         (x3:2015-2035: a dropped cond is zero, the bias stays).
         rope_len / rope_ctx_len: sequence length (registers + frames) and context length the REFERENCE call would have had when
         the plan is padded to a bucket (defaults: the plan's N and nc): the cross-attention keys are rotated with the last
-        rope_ctx_len positions of a rope_len-long table (A7), which padding must not move."""
+        rope_ctx_len positions of a rope_len-long table (A7), which padding must not move.
+        fold_embed: the caller will run begin_steps() (E2TTS.sample): on a plan that can take the folded embed (_fold_ok) the offset tables
+        of layer 0's cross-condition outputs are computed here, and the time conditioning with its two modulation tables is kept when
+        the host-side grid (t_points, dt) is the one this plan was last prepared for -- in use the grid is fixed per model
+        configuration.  Without it (the default) the call issues the launches it always did; either way it disarms the plan."""
         p, c, W, dev = self.plan, self.cfg, self.W, self.dev
         B, Bt, T, N, nc, S = p["B"], p["Bt"], p["T"], p["N"], p["nc"], p["S"]
         R, D, Dt, Df = c.num_registers, c.dim, c.dim_text, c.dim_frames
         assert text.shape == (B, T, Dt) and frames_roll.shape == (B, T, c.notes) and context.shape == (B, nc, c.ctx_dim)
         p["valid_T"].fill_(T if rope_len is None else min(T, int(rope_len) - R))
+        p["armed"] = p["c0_ok"] = False
+        folding = fold_embed and "ybuf" in p and self._fold_ok(p)
         # -- time conditioning + modulation tables for every grid point
-        p["t_pts"].copy_(t_points.to(dev, torch.float32))
-        if dt is not None:
-            p["dt"].copy_(dt.to(dev, torch.float32))
         p["step"].zero_()
-        L.time_cond(p["t_pts"], W.fourier_w, W.time_wt, W.time_b, p["tc"], S=S, d=D)
-        nt = c.depth * 3 * D
-        L.gemm([(p["tc"], D, D)], W.norm_gamma_w, p["norm_tab"], M=S, N=nt, compute=L.F32, bias=W.norm_gamma_b, ldo=nt)
-        L.gemm([(p["tc"], D, D)], W.gate_w, p["gate_tab"], M=S, N=nt, compute=L.F32, epilogue=L.EPI_SIGMOID,
-               bias=W.gate_b, ldo=nt)
+        if not (folding and same_grid(p["grid_host"], t_points, dt)):
+            p["t_pts"].copy_(t_points.to(dev, torch.float32))
+            if dt is not None:
+                p["dt"].copy_(dt.to(dev, torch.float32))
+            L.time_cond(p["t_pts"], W.fourier_w, W.time_wt, W.time_b, p["tc"], S=S, d=D)
+            nt = c.depth * 3 * D
+            L.gemm([(p["tc"], D, D)], W.norm_gamma_w, p["norm_tab"], M=S, N=nt, compute=L.F32, bias=W.norm_gamma_b, ldo=nt)
+            L.gemm([(p["tc"], D, D)], W.gate_w, p["gate_tab"], M=S, N=nt, compute=L.F32, epilogue=L.EPI_SIGMOID,
+                   bias=W.gate_b, ldo=nt)
+        p["grid_host"] = None
+        if folding and t_points.device.type == "cpu" and (dt is None or dt.device.type == "cpu"):
+            p["grid_host"] = (t_points.detach().to(torch.float32).clone(), None if dt is None else dt.detach().to(torch.float32).clone())
         # -- sequence lengths (mask = lens_to_mask(duration) padded by R registers, x3:978-979, 2216)
         if lens is not None and not bool((torch.as_tensor(lens) == T).all()):
             sl = (torch.as_tensor(lens).to(torch.int32) + R).to(dev)
@@ -833,6 +906,42 @@ class DiTEngine:
         ly = W.layers[0]
         self._side_block(ly, "t", p["t0"], p["tL0"], Bt, Dt)
         self._side_block(ly, "f", p["f0"], p["fL0"], Bt, Df)
+        # -- folded embed: layer 0's three cross-condition outputs at y = 0, by the launches an unfolded evaluation runs (the audio-prompt
+        #    GEMM of embed() included: it does not depend on the step either).  An armed evaluation adds y G^T to them (forward()).
+        if folding:
+            self.embed(p["y_zero"])
+            xa, tl, fl = p["xA"], p["tL0"], p["fL0"]
+            rows = p["rows"]
+            ht, hf = self._cross_hints()
+            self._mm([xa.op, tl.op, fl.op], ly["x_tfa"], p["c0_a"], M=rows, N=D, epilogue=L.EPI_RESID, resid=xa.x, ldo=D, ldr=D,
+                     tile_hint=self._tile_hint("a", "x_tfa"))
+            self._mm([xa.op, tl.op], ly["x_at"], p["c0_t"], M=rows, N=Dt, epilogue=L.EPI_RESID, resid=tl.x, ldo=Dt, ldr=Dt, tile_hint=ht)
+            self._mm([xa.op, fl.op], ly["x_af"], p["c0_f"], M=rows, N=Df, epilogue=L.EPI_RESID, resid=fl.x, ldo=Df, ldr=Df, tile_hint=hf)
+            p["c0_ok"] = True
+
+    def begin_steps(self, y0):
+        """Start an Euler loop on the prepared plan from the latent y0 (B, T, C): y0 into plan["y"] (allocated on first use), and -- when
+        prepare(fold_embed=True) left the offset tables -- its hi | lo planes into the frame rows of both halves of `ybuf`, which arms the
+        plan: euler_step(plan["y"], ...) then skips embed() and runs layer 0's cross-condition as three K = num_channels GEMMs, and
+        cfg_euler keeps the planes in step with y.  The next prepare() disarms.  Returns plan["y"].
+        The planes follow y only through euler_step: a caller that writes plan["y"] itself and wants the next evaluation to start from
+        what it wrote calls begin_steps again.  (bench.py's roofline leg restores y behind its timed evaluations without doing so: the first
+        evaluation after a restore starts from the planes of the y reached before, the same launches on finite values; it times them and
+        keeps none of their results.)"""
+        p, c = self.plan, self.cfg
+        B, T, N, C_ = p["B"], p["T"], p["N"], c.num_channels
+        if "y" not in p:
+            p["y"] = torch.empty(B, T, C_, dtype=torch.float32, device=self.dev)
+        y = p["y"]
+        y.copy_(y0.to(self.dev, torch.float32))
+        p["armed"] = False
+        if p["c0_ok"] and "ybuf" in p and self._fold_ok(p):
+            yb = p["ybuf"]
+            for seq in range(p["Bt"]):          # the rows of y[b] in the conditional and in the null half; register rows stay zero
+                r0 = seq * N + c.num_registers
+                L.split_bf16(y[seq % B], yb.t[r0:r0 + T], rows=T, d=C_, ldy=yb.ld)
+            p["armed"] = True
+        return y
 
     # ------------------------------------------------------------------------------ forward
     def embed(self, y):
@@ -849,8 +958,15 @@ class DiTEngine:
             self._mm([self._rows(p["condbuf"])], W.cond_w, x.x, M=B * N, N=D, epilogue=L.EPI_RESID, resid=x.x,
                      ldo=D, ldr=D, shadow=x.sh)
 
-    def forward(self, n_ctx_seqs: int | None = None):
+    def _cross_hints(self):
+        """Tile hints of the x_at / x_af cross-condition GEMMs: the side streams' table entries when they run there, else the library's choice."""
+        on_side = self.dev.type == "cuda" and self.plan.get("st") is not None and not self.cross_on_main
+        return (self._tile_hint("t", "cross"), self._tile_hint("f", "cross")) if on_side else (0, 0)
+
+    def forward(self, n_ctx_seqs: int | None = None, folded: bool = False):
         """Transformer.forward over the plan's Bt sequences starting from xA; result in plan['pred'].
+        folded (an armed plan, see begin_steps): xA is not read -- layer 0's three cross-condition GEMMs take the planes of y in `ybuf`
+        against G_a / G_t / G_f (K = num_channels) and add the offset tables of prepare(); same outputs, streams and events.
 
         Dependency structure of one layer i (x3:1081-1137): the text block T_i and frames block F_i need only
         their own stream; the cross-condition reads the PRE-update x, text, frames; the audio block A_i needs
@@ -913,12 +1029,16 @@ class DiTEngine:
             xn = p["skips"][i] if i < half else xo
             ax, at_, af_ = xc.op, tc_.op, fc_.op
             fused = fz and i >= half
+            fold0 = folded and i == 0 and not fused
             if fused:
                 # second half, bf16 mode: cross-condition + skip projection in one GEMM over [x | skip | text | frames]; x's
                 # bf16 copy was written into the left half of the skip's wide buffer by the previous layer's FF2 epilogue
                 wd = p["wide"][c.depth - 1 - i]
                 ax = wd.x
                 self._mm([wd.whole, at_, af_], ly["x_skip"], p["xS"], M=rows, N=D, ldo=D, tile_hint=self._tile_hint("a", "x_tfa"))
+            elif fold0:
+                self._mm([p["ybuf"]], W.fold_g[0], xn.x, M=rows, N=D, epilogue=L.EPI_RESID, resid=p["c0_a"], ldo=D, ldr=D,
+                         shadow=xn.sh, tile_hint=self._tile_hint("a", "x_tfa"))
             else:
                 self._mm([ax, at_, af_], ly["x_tfa"], xn.x, M=rows, N=D, epilogue=L.EPI_RESID, resid=xc.x, ldo=D, ldr=D,
                          shadow=xn.sh, tile_hint=self._tile_hint("a", "x_tfa"))
@@ -928,9 +1048,15 @@ class DiTEngine:
                 hint_t = self._tile_hint("t", "cross") if on_side else 0
                 hint = self._tile_hint("f", "cross") if on_side else 0
                 def cross_t():
+                    if fold0:
+                        return self._mm([p["ybuf"]], W.fold_g[1], tbuf[0].x, M=rows, N=Dt,
+                                        epilogue=L.EPI_RESID, resid=p["c0_t"], ldo=Dt, ldr=Dt, tile_hint=hint_t)
                     self._mm([ax, at_], ly["x_at"], tbuf[0].x, M=rows, N=Dt,
                              epilogue=L.EPI_RESID, resid=tc_.x, ldo=Dt, ldr=Dt, tile_hint=hint_t)
                 def cross_f():
+                    if fold0:
+                        return self._mm([p["ybuf"]], W.fold_g[2], fbuf[0].x, M=rows, N=Df,
+                                        epilogue=L.EPI_RESID, resid=p["c0_f"], ldo=Df, ldr=Df, tile_hint=hint)
                     self._mm([ax, af_], ly["x_af"], fbuf[0].x, M=rows, N=Df,
                              epilogue=L.EPI_RESID, resid=fc_.x, ldo=Df, ldr=Df, tile_hint=hint)
                 if self.cross_on_main or not multi:
@@ -1028,12 +1154,19 @@ class DiTEngine:
     def euler_step(self, y, cfg_strength: float, remove_parallel_component: bool = False, keep_parallel_frac: float = 0.0):
         """One CFG + Euler evaluation, in place on y (B,T,C): the unit that is hipGraph-captured."""
         p, c = self.plan, self.cfg
-        self.embed(y)
-        self.forward()
+        # an armed plan (begin_steps) holds the planes of ITS y: any other tensor takes the unfolded sequence
+        folded = p["armed"] and self._fold_ok(p) and "y" in p and y.data_ptr() == p["y"].data_ptr()
+        if not folded:
+            self.embed(y)
+        self.forward(folded=folded)
         kw = dict(B=p["B"], T=p["T"], C_=c.num_channels, pred_batch_stride=p["N"] * c.num_channels, row_off=c.num_registers)
+        planes = None
+        if folded:          # the planes of the updated y for the next evaluation's layer-0 GEMMs, both halves
+            yb = p["ybuf"]
+            planes = dict(out=yb.t, ld=yb.ld, lo_offset=yb.k, row_off=c.num_registers, rows_per_seq=p["N"], copies=p["Bt"] // p["B"])
         apg = None
         if remove_parallel_component:
             L.apg_reduce(p["pred"], p["apg"], valid_rows=p["valid_T"], **kw)
             apg = p["apg"]
-        L.cfg_euler(y, p["pred"], cfg_strength=cfg_strength, dt=p["dt"], step=p["step"], apg=apg, keep=keep_parallel_frac, **kw)
+        L.cfg_euler(y, p["pred"], cfg_strength=cfg_strength, dt=p["dt"], step=p["step"], apg=apg, keep=keep_parallel_frac, planes=planes, **kw)
         L.step_advance(p["step"])

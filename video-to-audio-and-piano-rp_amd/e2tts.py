@@ -896,7 +896,7 @@ class E2TTS:
         ev[0].record()
         eng.prepare(pad_t(text_embed), pad_t(frames_embed), context, context_mask, t[:-1], lens=duration,
                     drop_ctx=drop_ctx, dt=t[1:] - t[:-1], step_cond=pad_t(step_cond),
-                    rope_len=cfgm.num_registers + n, rope_ctx_len=nc)
+                    rope_len=cfgm.num_registers + n, rope_ctx_len=nc, fold_embed=True)
         ev[1].record()
         self._run_steps(eng, pad_t(y0), S, float(cfg_strength), bool(remove_parallel_component), trajectory_out, n)
         ev[2].record()
@@ -934,8 +934,7 @@ class E2TTS:
         """steps-1 Euler evaluations (A12 of SURVEY 8c).  cfg_strength < 1e-5 (x3:2101) still
         runs the batched pass; the null half then has weight 0."""
         p = eng.plan
-        y = p["y"]
-        y.copy_(y0.to(self._device, torch.float32))
+        y = eng.begin_steps(y0)        # y0 into plan["y"]; arms the folded embed where prepare() left its tables (DiTEngine.fold_embed)
         p["step"].zero_()
         if traj is not None:
             traj.append(y[:, :n_valid].clone())
@@ -955,7 +954,7 @@ class E2TTS:
             keep = y.clone()
             eng.euler_step(y, cfg_strength, apg)
             torch.cuda.synchronize()
-            y.copy_(keep)
+            eng.begin_steps(keep)       # restores y and, on an armed plan, its operand planes
             p["step"].zero_()
             g = torch.cuda.CUDAGraph()
             # thread-local capture mode: only this thread's calls are policed, so a communication library's watchdog thread
