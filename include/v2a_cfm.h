@@ -901,6 +901,38 @@ int v2a_roll_notes(const void* roll, int32_t elem_bytes, int64_t batch_stride, i
                    int32_t B, int32_t T, int32_t keys, const int32_t* lens, int32_t* counts, int32_t* totals, int32_t* notes, int32_t cap,
                    int8_t* onset, v2a_stream_t stream);
 
+/* =====================================================================================
+ * Log-mel front end: the reference's `MelSpec` (x3:375-417) -- torchaudio's MelSpectrogram and log(clamp(mel, 1e-5)) (x3:293-294).
+ * v2a_mel_pad, the exact-fp32 v2a_gemm over overlapping rows (lda = hop, K = n_fft, W = the windowed real DFT basis with the rows of
+ * bin k at 2k (re) and 2k + 1 (im): mel.py, stft_basis), v2a_mel_from_dft.  The GEMM adds its K products in one fp32 chain, so K is cut
+ * into chunks (256 samples in mel.py): one launch per chunk on the same rows, A and W moved by the chunk, each into a partial DFT of its
+ * own.  Window, normalisation and mel norm live in the two host tables; the kernels know n_fft, hop, the bins, n_mels and power.
+ * Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+#define V2A_MEL_MAX_FFT 2048                    /* a workgroup of v2a_mel_from_dft holds n_fft / 2 + 1 bins of 16 frames in LDS */
+#define V2A_MEL_MAX_CHUNKS 16                   /* partial DFTs of one frame: mel.py cuts K into chunks of 256 samples */
+
+/* B waves x (row b at x + b * ldx, nw samples) -> out + b * pitch: `pad` reflected samples, the wave, `pad` reflected samples
+ * (torch.stft's center = True with pad_mode = "reflect": the edge sample is not repeated; pad < nw), pad = 0: a copy.  Only the
+ * nw + 2 pad samples of every clip are written; pitch >= nw + 2 pad.  With pitch a multiple of hop, frame t of clip b is row
+ * b * pitch / hop + t of the GEMM behind it. */
+int v2a_mel_pad(const float* x, int64_t ldx, int32_t B, int64_t nw, int32_t pad, float* out, int64_t pitch, v2a_stream_t stream);
+/* dft: n_chunks partial DFTs, chunk_stride floats apart, each fp32 rows of ld_dft floats with (re, im) of bin k at 2k and 2k + 1,
+ * k < n_fft / 2 + 1; frame t < T of clip b < B is row b * rows_per_clip + t (rows_per_clip >= T: the rows between two clips are never
+ * read).  re and im of a bin are its partials added in chunk order, ((c0 + c1) + c2) + ...  Per frame and bin
+ *   p[k] = fma(im, im, re * re)  (power 2)   or   sqrt of it, correctly rounded  (power 1)
+ * and per mel channel m, with (first, count) = bands[2m], bands[2m + 1] and w = weights + m * wpitch,
+ *   mel = fma(w[count - 1], p[first + count - 1], ... fma(w[1], p[first + 1], fma(w[0], p[first], 0)))
+ * one fp32 chain in ascending bin order, so a value does not depend on the tiling, on B or on T.  Stored at
+ * out[b * out_batch_stride + m * out_row_stride + t]: float(log((double)max(mel, eps))), the log taken in double and rounded once,
+ * or mel itself when eps < 0.  Nothing else of out is written.  `bands` (device) and `bands_host` (host) hold the same n_mels pairs:
+ * the entry point checks the host copy (0 <= first, 0 <= count <= wpitch, first + count <= bins), the kernel clamps what it reads.
+ * n_fft even, 4 .. V2A_MEL_MAX_FFT; hop a positive multiple of 4 (the GEMM's lda); power 1 or 2; no atomics. */
+int v2a_mel_from_dft(const float* dft, int64_t ld_dft, int64_t rows_per_clip, int32_t n_chunks, int64_t chunk_stride, int32_t B, int32_t T,
+                     int32_t n_fft, int32_t hop, int32_t n_mels, const int32_t* bands_host, const int32_t* bands, const float* weights, int32_t wpitch,
+                     int32_t power, float eps, float* out, int64_t out_batch_stride, int64_t out_row_stride, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

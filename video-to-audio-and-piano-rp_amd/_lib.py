@@ -158,6 +158,7 @@ EXPORTS = [
     "v2a_roll_expand_ratio", "v2a_piano_resize_vt",
     "v2a_roll_notes",
     "v2a_cfg_euler_planes",
+    "v2a_mel_pad", "v2a_mel_from_dft",
 ]
 
 
@@ -240,6 +241,8 @@ def _declare(lib):
     lib.v2a_roll2midi_head.argtypes = [vp, i64, i32, vp, i64, i32, vp, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.v2a_roll2midi_gate.argtypes = [vp, i64, i32, vp, i64, vp, i64, i32, vp, i64, vp, f32, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.v2a_roll_notes.argtypes = [vp, i32, i64, i64, i64, f32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+    lib.v2a_mel_pad.argtypes = [vp, i64, i32, i64, i32, vp, i64, vp]
+    lib.v2a_mel_from_dft.argtypes = [vp, i64, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, i64, i64, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int

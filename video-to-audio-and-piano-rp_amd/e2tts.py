@@ -470,6 +470,19 @@ class E2TTS:
         self.mel_spec = lambda wave: enc.encoder(wave.unsqueeze(1))
         return enc
 
+    def load_mel_spec(self, src=None, **mel_spec_kwargs):
+        """The log-mel front end behind a raw-wave `cond` / `inp` (b, nw) of a model whose latents are mel frames (x3:2157-2160,
+        2328-2331): a `MelSpec`, or the reference's `MelSpec` keywords to build one on the model's device.  Sets `mel_spec`."""
+        from .mel import MelSpec
+        if src is None:
+            src = MelSpec(device=self._device, **mel_spec_kwargs)
+        elif not isinstance(src, MelSpec) or mel_spec_kwargs:
+            raise TypeError(f"load_mel_spec: a MelSpec, or keywords alone to build one, got {type(src).__name__}")
+        if src.n_mel_channels != self.num_channels:
+            raise ValueError(f"load_mel_spec: n_mel_channels={src.n_mel_channels} but the model has num_channels={self.num_channels}")
+        self.mel_spec = src
+        return src
+
     def wave_front_end(self):
         """The `WaveFrontEnd` in front of the audio encoder: any rate -> the model's rate, `normalize_wav`; made on first use."""
         from .wave import WaveFrontEnd
