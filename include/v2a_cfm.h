@@ -933,6 +933,59 @@ int v2a_mel_from_dft(const float* dft, int64_t ld_dft, int64_t rows_per_clip, in
                      int32_t n_fft, int32_t hop, int32_t n_mels, const int32_t* bands_host, const int32_t* bands, const float* weights, int32_t wpitch,
                      int32_t power, float eps, float* out, int64_t out_batch_stride, int64_t out_row_stride, v2a_stream_t stream);
 
+/* =====================================================================================
+ * Vocos vocoder, mel variant with padding = "center": mel frames -> wave, the `vocos` of a model whose latents are log-mel frames
+ * (Vocos.from_pretrained('charactr/vocos-mel-24khz'), e2_tts_crossatt.py:1324, e2_tts_crossatt6.py:1469; `self.vocos.decode`,
+ * x3:2275-2287).  vocos.py runs it as: v2a_vocos_stage_in, v2a_gemm (embed conv over overlapping rows), v2a_clip_layernorm, per
+ * block v2a_vocos_dwconv_ln + v2a_gemm (pwconv1) + v2a_vocos_gelu + v2a_gemm (pwconv2) + v2a_vocos_scale_residual, v2a_clip_layernorm,
+ * v2a_gemm (head), v2a_vocos_spectrum, v2a_gemm against the inverse-DFT basis of vocos.py (window, 1 / n_fft and the factor 2 of the
+ * inner bins folded in), v2a_vocos_overlap_add.  Every GEMM runs in K chunks of 256, chunk c added to the sum of the chunks before it by
+ * the RESID epilogue: the exact-fp32 GEMM adds its K products in one chain whose error grows with K.  Activations are fp32 rows, frame t of clip b at row
+ * b * rows_per_clip + t; vocos.py keeps rows_per_clip = T + 6, the rows between two clips are computed and never read.
+ * `lens` (device int32[B] or NULL = T everywhere): clip b has lens[b] frames and is decoded as if it were alone -- every convolution
+ * zero padded at its own end, its own envelope.  The kernels clamp lens[b] to 0 .. T.  No atomics.
+ * Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+#define V2A_VOCOS_MAX_DIM 2048                  /* d of v2a_vocos_dwconv_ln: a tile of 2 frames + 6 halo rows fits 64 KB of LDS */
+#define V2A_VOCOS_MAX_FFT 4096
+#define V2A_VOCOS_MAX_FRAMES (1 << 24)
+
+/* x (B, C, T) fp32 channel-major (clip b at x + b * x_batch_stride, channel c at + c * x_chan_stride, unit stride along time) ->
+ * out: B * (T + 6) rows of c_pad floats, row b * (T + 6) + 3 + t = frame t of clip b; the 3 rows on either side of a clip, the columns
+ * C .. c_pad - 1 and the frames t >= lens[b] are zero.  Every element of out is written.  c_pad >= C, a multiple of 16.
+ * Replaces: the zero padding of `backbone.embed` (Conv1d(C, dim, 7, padding=3)) -- the convolution itself is v2a_gemm on rows
+ * b * (T + 6) + t with lda = c_pad and K = 7 c_pad. */
+int v2a_vocos_stage_in(const float* x, int64_t x_batch_stride, int64_t x_chan_stride, int32_t B, int32_t C, int32_t T, const int32_t* lens,
+                       float* out, int32_t c_pad, v2a_stream_t stream);
+/* Per frame t < lens[b] of clip b (row r = b * rows_per_clip + t) and channel c < d:
+ *   a[c] = fma(wt[6 d + c], x[t + 3][c], ... fma(wt[d + c], x[t - 2][c], fma(wt[c], x[t - 3][c], bias[c])))     x[u] = 0 outside [0, lens[b])
+ *   y[r][c] = (a[c] - mean) / sqrt(var + eps) * gamma[c] + beta[c]     mean, var over the d channels (biased, centred two-pass, fp32)
+ * wt is tap-major, (7, d): wt[j * d + c] = dwconv.weight[c][0][j].  Rows lens[b] <= t < T of y are zeroed, nothing else is written.
+ * d a multiple of 16, 16 .. V2A_VOCOS_MAX_DIM; ldx, ldy >= d and multiples of 4; x != y.
+ * Replaces: ConvNeXtBlock.dwconv and ConvNeXtBlock.norm of the Vocos backbone. */
+int v2a_vocos_dwconv_ln(const float* x, int64_t ldx, const float* wt, const float* bias, const float* gamma, const float* beta, float eps,
+                        int32_t B, int32_t T, int64_t rows_per_clip, int32_t d, const int32_t* lens, float* y, int64_t ldy, v2a_stream_t stream);
+/* x[r][c] = 0.5 x (1 + erf(x / sqrt 2)) in place, r < rows, c < n; n a multiple of 4, ldx >= n a multiple of 4.
+ * Replaces: ConvNeXtBlock.act (nn.GELU) behind pwconv1. */
+int v2a_vocos_gelu(float* x, int64_t ldx, int64_t rows, int32_t n, v2a_stream_t stream);
+/* out[r][c] = fma(gamma[c], p[r][c], resid[r][c]), r < rows, c < n; n and the row strides multiples of 4; out may be resid, not p.
+ * Replaces: ConvNeXtBlock's `residual + self.gamma * x`. */
+int v2a_vocos_scale_residual(const float* p, int64_t ldp, const float* gamma, const float* resid, int64_t ldr, float* out, int64_t ldo,
+                             int64_t rows, int32_t n, v2a_stream_t stream);
+/* logits: `rows` rows of n_fft + 2 floats, log-magnitudes m[k] at k and phases p[k] at n_fft / 2 + 1 + k, k <= n_fft / 2 ->
+ * spec[r][2k] = float(min(exp(m), 100) cos p), spec[r][2k + 1] = float(min(exp(m), 100) sin p): exp, cos, sin and the products in double
+ * from the fp32 logits, rounded once.  Columns n_fft + 2 .. ld_spec - 1 are zeroed (the K pad of the GEMM behind it); ld_spec even.
+ * Replaces: ISTFTHead.forward up to the complex spectrogram. */
+int v2a_vocos_spectrum(const float* logits, int64_t ld_logits, int64_t rows, int32_t n_fft, float* spec, int64_t ld_spec, v2a_stream_t stream);
+/* torch.istft's overlap-add (center = True) in gather form.  frames: rows of n_fft floats, irfft(S[:, t]) * w of frame t of clip b at
+ * row b * rows_per_clip + t; wsq[j] = w[j]^2.  For n < (lens[b] - 1) hop, with p = n + n_fft / 2,
+ *   out[b * out_batch_stride + n] = (sum_t frames[t][p - t hop]) / (sum_t wsq[p - t hop])      over t < lens[b] with 0 <= p - t hop < n_fft,
+ * both sums fp32 in ascending t, one IEEE division.  Nothing else of out is written.  1 <= hop <= n_fft, T >= 2.
+ * Replaces: ISTFT.forward (torch.istft) of the Vocos head. */
+int v2a_vocos_overlap_add(const float* frames, int64_t ld_frames, int64_t rows_per_clip, const float* wsq, int32_t B, int32_t T, int32_t n_fft,
+                          int32_t hop, const int32_t* lens, float* out, int64_t out_batch_stride, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,7 @@ EXPORTS = [
     "v2a_roll_notes",
     "v2a_cfg_euler_planes",
     "v2a_mel_pad", "v2a_mel_from_dft",
+    "v2a_vocos_stage_in", "v2a_vocos_dwconv_ln", "v2a_vocos_gelu", "v2a_vocos_scale_residual", "v2a_vocos_spectrum", "v2a_vocos_overlap_add",
 ]
 
 
@@ -243,6 +244,12 @@ def _declare(lib):
     lib.v2a_roll_notes.argtypes = [vp, i32, i64, i64, i64, f32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
     lib.v2a_mel_pad.argtypes = [vp, i64, i32, i64, i32, vp, i64, vp]
     lib.v2a_mel_from_dft.argtypes = [vp, i64, i64, i32, i64, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, i64, i64, vp]
+    lib.v2a_vocos_stage_in.argtypes = [vp, i64, i64, i32, i32, i32, vp, vp, i32, vp]
+    lib.v2a_vocos_dwconv_ln.argtypes = [vp, i64, vp, vp, vp, vp, f32, i32, i32, i64, i32, vp, vp, i64, vp]
+    lib.v2a_vocos_gelu.argtypes = [vp, i64, i64, i32, vp]
+    lib.v2a_vocos_scale_residual.argtypes = [vp, i64, vp, vp, i64, vp, i64, i64, i32, vp]
+    lib.v2a_vocos_spectrum.argtypes = [vp, i64, i64, i32, vp, i64, vp]
+    lib.v2a_vocos_overlap_add.argtypes = [vp, i64, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int

@@ -24,6 +24,11 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
   --encodec STATE    torch-saved state dict of `EncodecModel.from_pretrained("facebook/encodec_24khz")` (or of its decoder):
                      each clip's valid frames are decoded by the HIP vocoder and written as `<name>.wav` (24 kHz float32),
                      what the reference does with `save_to_filename` / torchaudio.save (x3:2291-2303, predict.py:279-281).
+  --vocos DIR        the vocoder of a checkpoint whose latents are log-mel frames: a local directory with `config.yaml` and
+                     `pytorch_model.bin` as the hub stores `charactr/vocos-mel-24khz` (the reference's `Vocos.from_pretrained`,
+                     e2_tts_crossatt.py:1324; nothing is fetched).  Each clip's valid frames are decoded by the HIP Vocos (vocos.py) and
+                     written as `<name>.wav`; a clip has 24000 / hop frames per second, hop from the vocoder's config (256), not 320.
+                     As the vocoder it is exclusive with --encodec.
   --audio-prompt-seconds S   (with --encodec, checkpoint built with if_cond_proj_in) the first S seconds of `<video>.wav` (24 kHz) are
                      encoded by the HIP Encodec encoder and given to the sampler as the audio prompt: `cond` = the raw waves,
                      `lens` = ceil(24000 S / 320) frames, which come back unchanged in front of the generated ones (x3:2196-2231).
@@ -141,9 +146,10 @@ def validation_sources(video_paths, wav: bool = False):
     return out
 
 
-def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None, video_encoder: str = "clip_vit"):
+def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None, video_encoder: str = "clip_vit", hop: int = 320):
     """clip_encode: optional `video_path -> (image_embeds, duration)` that makes a missing `<video>.generated.npz` (--clip);
-    video_encoder: which cache name is read and written (--video-encoder)."""
+    video_encoder: which cache name is read and written (--video-encoder); hop: samples per latent frame (320: Encodec; --vocos: the
+    vocoder's hop)."""
     from .collate import ClipRequest
     from .features import feature_cache_path, load_clip_cache, resample_clip_features, save_clip_cache
     reqs = []
@@ -154,7 +160,7 @@ def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip
                 raise FileNotFoundError(f"{fp}: no cached CLIP features for {vp}; pass --clip DIR (with moviepy installed) to encode it")
             save_clip_cache(fp, *clip_encode(vp))                                # x3:1706-1793
         emb, duration = load_clip_cache(fp)
-        n = min(n_frames, int(duration * 24000) // 320) if n_frames > 0 else int(duration * 24000) // 320
+        n = min(n_frames, int(duration * 24000) // hop) if n_frames > 0 else int(duration * 24000) // hop
         clip = resample_clip_features(emb.float(), duration, n)
         prompt = "" if drop_prompt else cap
         t5p = vp.replace(".mp4", ".t5.npz")
@@ -248,6 +254,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="compute mode of the Video2Roll encoder behind --piano (default: bf16 under --dtype bf16, else fp32); bf16x3: "
                          "split-bf16 implicit GEMM inside 1e-4 of the reference probabilities")
     ap.add_argument("--encodec", default=None, help="state dict (.pt) of the Encodec model / decoder: also write <name>.wav")
+    ap.add_argument("--vocos", default=None, metavar="DIR", help="local Vocos directory (config.yaml, pytorch_model.bin) of a checkpoint whose latents "
+                    "are mel frames: also write <name>.wav through the HIP Vocos; exclusive with --encodec")
     ap.add_argument("--audio-prompt-seconds", type=float, default=0.0, help="with --encodec and a checkpoint built with if_cond_proj_in: "
                     "prompt every clip with the first S seconds of <video>.wav, encoded by the HIP Encodec encoder")
     ap.add_argument("--codes", type=float, default=None, choices=[1.5, 3.0, 6.0, 12.0, 24.0], metavar="KBPS",
@@ -299,6 +307,9 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.audio_prompt_seconds < 0 or (a.audio_prompt_seconds > 0 and not a.encodec):
         ap.error("--audio-prompt-seconds needs a positive S and --encodec (the state dict that holds the encoder)")
+
+    if a.vocos and a.encodec:
+        ap.error("--vocos and --encodec are exclusive: each is the vocoder of its own latents (mel frames / Encodec latents)")
 
     if a.codes is not None and not a.encodec:
         ap.error("--codes needs --encodec (the state dict that holds the quantizer's codebooks)")
@@ -379,6 +390,11 @@ def main(argv=None):
         vocoder = EncodecDecoder(esd, torch.device("cuda", local))
         if a.codes is not None:
             model.load_audio_quantizer(esd)
+    hop = 320                                                        # samples per latent frame (torch_tools.py:32-40)
+    if a.vocos:
+        voc = model.load_vocoder(a.vocos)                            # refuses a vocoder whose channels are not the model's
+        hop = voc.hop
+        vocoder = voc if rank == 0 else None
     items = read_scp(a.test_scp, a.start, a.end)
     os.makedirs(a.out_dir, exist_ok=True)
     gen = torch.Generator().manual_seed(a.seed)
@@ -388,7 +404,7 @@ def main(argv=None):
         s, e, per = shard_range(len(chunk), rank, world)
         mine = chunk[s:e]
         if mine:
-            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder), channels, gen, notes=model.cfg.notes)
+            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder, hop), channels, gen, notes=model.cfg.notes)
             frames = None
             if a.piano:
                 # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
@@ -429,7 +445,7 @@ def main(argv=None):
                 if vocoder is not None:
                     from scipy.io import wavfile
                     from .features import load_clip_cache, feature_cache_path
-                    n = min(a.frames, int(load_clip_cache(feature_cache_path(vp, a.video_encoder))[1] * 24000) // 320) if a.frames > 0 else one.shape[0]
+                    n = min(a.frames, int(load_clip_cache(feature_cache_path(vp, a.video_encoder))[1] * 24000) // hop) if a.frames > 0 else one.shape[0]
                     wav = vocoder.decode(one[:n].t()[None].float())[0]                     # predict.py:277-278
                     wavfile.write(os.path.join(a.out_dir, name + ".wav"), 24000, wav.cpu().numpy())
                     if a.codes is not None:

@@ -483,6 +483,30 @@ class E2TTS:
         self.mel_spec = src
         return src
 
+    def load_vocoder(self, src, **kw):
+        """The Vocos vocoder behind `sample(return_raw_output=False)` of a model whose latents are mel frames (x3:2275-2287; the
+        reference's `Vocos.from_pretrained(pretrained_vocos_path)`, e2_tts_crossatt.py:1324): a `Vocos`, its state dict, or a local
+        directory with config.yaml and pytorch_model.bin.  Sets `self.vocos` and returns it.  `kw` go to the Vocos constructor."""
+        from .vocos import Vocos
+        if isinstance(src, Vocos):
+            if kw:
+                raise TypeError("load_vocoder: keywords go with a state dict or a directory, not with a Vocos")
+            voc = src
+        elif isinstance(src, dict):
+            voc = Vocos(src, self._device, **kw)
+        elif isinstance(src, (str, os.PathLike)):
+            voc = Vocos.from_pretrained(src, device=self._device, **kw)
+        else:
+            raise TypeError(f"load_vocoder: a Vocos, a state dict or a local directory, got {type(src).__name__}")
+        if voc.C != self.num_channels:
+            raise ValueError(f"load_vocoder: the vocoder reads {voc.C} channels but the model has num_channels={self.num_channels}")
+        hop = getattr(self.mel_spec, "hop", None)
+        if self.sampling_rate is not None and hop is not None and int(hop) != voc.hop:
+            raise ValueError(f"load_vocoder: the vocoder's hop is {voc.hop} but the loaded mel_spec has hop_length={int(hop)}: "
+                             f"the wave would not run at sampling_rate={self.sampling_rate}")
+        self.vocos = voc
+        return voc
+
     def wave_front_end(self):
         """The `WaveFrontEnd` in front of the audio encoder: any rate -> the model's rate, `normalize_wav`; made on first use."""
         from .wave import WaveFrontEnd
