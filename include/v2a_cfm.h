@@ -79,12 +79,15 @@ enum {
                              fp32 output) or split operands (the bf16x3 mode; output fp32 with exact erff, or out_dtype V2A_BF16_SPLIT: row m =
                              [hi of the N outputs | lo of them], ldo >= 2N, erf by Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7, the fc2 operand
                              written directly).  Plain bf16 compute refuses it. */
-  V2A_EPI_SWIGLU = 7      /* ABI 8, additive: the GEGLU row packing [16 value | 16 gate] per 16 outputs with silu on the gate,
+  V2A_EPI_SWIGLU = 7,     /* ABI 8, additive: the GEGLU row packing [16 value | 16 gate] per 16 outputs with silu on the gate,
                              out[m][j] = (acc_v + b_v) * silu(acc_g + b_g), silu(x) = x / (1 + exp(-x)); out has N/2 cols -- Dinov2SwiGLUFFN of the
                              DINOv2 image encoder (`video_encoder="dinov2"`, x3:1432-1433, 1714, 1742-1744): gate = rows [0, Hf) of weights_in (x1),
                              value = rows [Hf, 2Hf) (x2).  fp32 compute (exact expf and division, fp32 output) or split operands (the bf16x3 mode;
                              output fp32 with exact expf, or out_dtype V2A_BF16_SPLIT: row m = [hi of the N/2 outputs | lo of them], ldo >= N, silu
                              on v_exp_f32, the weights_out operand written directly).  Plain bf16 compute refuses it. */
+  V2A_EPI_CFG_EULER = 8   /* Additive to ABI 9; v2a_gemm_cfg_euler only (v2a_gemm rejects it): the STORE epilogue on a tile that holds 32 rows of the
+                             conditional half and the same 32 rows of the null half of the M rows, followed by the CFG + Euler update of y and the
+                             operand planes of the new y -- see v2a_gemm_cfg_euler below */
 };
 
 typedef struct v2a_gemm_args {
@@ -474,6 +477,34 @@ int v2a_split_bf16(const float* x, int64_t ldx, void* y, int64_t ldy, int64_t ro
 int v2a_cast_bf16(const float* x, void* y, int64_t n, v2a_stream_t stream);
 /* step[0] += 1 (own launch: every block of the step has read step[0] before it runs) */
 int v2a_step_advance(int32_t* step, v2a_stream_t stream);
+/* Additive to ABI 9: the step seam of the sampler in ONE launch -- the to_pred GEMM, v2a_cfg_euler_planes (without APG) and v2a_step_advance.
+ * `g` describes the to_pred GEMM exactly as for v2a_gemm: split operands (a_dtype V2A_BF16_SPLIT, bf16 compute), V2A_EPI_STORE, fp32 out with
+ * ldo >= N, optional bias and row_ssq (folded final norm); no shadow, rope, relu or offset tables.  M = 2 * B * rows_per_seq rows: the
+ * conditional half, then the null half; N = C, a multiple of 64.  The kernel is the 64x64 split ring of v2a_gemm with another row map -- tile
+ * row j of row band i is row 32 i + (j mod 32) of the conditional (j < 32) or the null (j >= 32) half -- and the epilogue V2A_EPI_CFG_EULER:
+ *   out[m] = acc * (1 / rms of row m) + bias      for every row m < M (the bits of the v2a_gemm launch: the split ring adds every 32-wide k
+ *                                                 step in one order whatever the tile), register rows included;
+ *   y[b][t] += dt[step[0]] * (pc + cfg_strength * (pc - pn))    with pc / pn = out of rows b * rows_per_seq + row_off + t of the two halves, the
+ *                                                 expression of v2a_cfg_euler; hi | lo planes of the new y[b][t] into those two rows of `planes`
+ *                                                 as by v2a_cfg_euler_planes with copies = 2; rows outside [row_off, row_off + T) of a sequence
+ *                                                 update nothing and their plane rows are not touched.
+ * Step counter: every workgroup reads dt[step[0]] and then adds 1 to arrive[0]; the workgroup that finds all others there stores step[0] + 1 and
+ * puts arrive[0] back to 0.  No workgroup waits for another.  arrive[0] must be 0 when the launch starts, and is 0 again when it has ended. */
+typedef struct v2a_step_seam {
+  float* y;              /* (B, T, C) fp32, 16-byte aligned, updated in place */
+  const float* dt;       /* step sizes */
+  int32_t* step;         /* device step counter (required) */
+  uint32_t* arrive;      /* arrival counter of the launch */
+  void* planes;          /* bf16 rows of both halves (M rows), 8-byte aligned */
+  int64_t ld;            /* row pitch of planes in elements, >= lo_offset + C, % 4 == 0 */
+  int64_t lo_offset;     /* elements from the hi plane of a row to its lo plane, >= C, % 4 == 0 */
+  int32_t B, T;          /* clips, latent frames */
+  int32_t row_off;       /* first row of y inside every sequence (registers) */
+  int32_t rows_per_seq;  /* >= row_off + T */
+  float cfg_strength;
+  int32_t reserved;
+} v2a_step_seam;
+int v2a_gemm_cfg_euler(const v2a_gemm_args* g, const v2a_step_seam* s, v2a_stream_t stream);
 
 /* =======================================================================================
  * N2: Video2Roll frame encoder -- `E2TTS.encode_frames` x3:1525-1553 running

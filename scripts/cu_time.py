@@ -15,7 +15,8 @@ def rows_of(d):
 
 
 def one_eval(rows):
-    end = [i for i, r in enumerate(rows) if "cfg_euler" in r["Kernel_Name"]]
+    # the CFG + Euler launch, or the one-launch step seam (the ring GEMM's epilogue 8, v2a_gemm_cfg_euler)
+    end = [i for i, r in enumerate(rows) if "cfg_euler" in r["Kernel_Name"] or re.search(r"gemm_bf16_dma_kernel(<8,|ILi8E)", r["Kernel_Name"])]
     a, b = end[-4], end[-3]
     return rows[a + 1:b + 1]
 

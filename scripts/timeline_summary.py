@@ -4,7 +4,9 @@ import csv, glob, re, sys, collections
 f = glob.glob(sys.argv[1] + "/**/*_kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-adv = [i for i, r in enumerate(rows) if "step_advance" in r["Kernel_Name"]]
+# an evaluation ends with the step counter's launch, or with the one-launch step seam (the ring GEMM's epilogue 8, v2a_gemm_cfg_euler)
+SEAM = re.compile(r"gemm_bf16_dma_kernel(<8,|ILi8E)")
+adv = [i for i, r in enumerate(rows) if "step_advance" in r["Kernel_Name"] or SEAM.search(r["Kernel_Name"])]
 a, b = adv[-4], adv[-3]
 ev = rows[a + 1:b + 1]
 t0, t1 = int(ev[0]["Start_Timestamp"]), int(ev[-1]["End_Timestamp"])
@@ -41,6 +43,8 @@ for k, rs in q.items():
     print("   idle between its kernels: %.1f us; largest gaps:" % (tot / 1e3))
     for g, x, y in sorted(gaps, reverse=True)[:6]:
         print("      %.1f us  after %-44s before %s" % (g / 1e3, x, y))
+    # layer by layer: how long the queue stood idle between its cross-condition GEMM (audio: the skip GEMM where there is one) and its depthwise conv
+    print("   idle in front of each dwconv, us: " + " ".join("%.1f" % (g / 1e3) for g, _, y in gaps if y == "dwconv"))
 
 # ---- how many kernels run at once, and what one layer looks like (audio = the queue with the most kernels)
 evs = []

@@ -118,6 +118,13 @@ class YPlanes(C.Structure):
                 ("copies", C.c_int32), ("reserved", C.c_int32)]
 
 
+class StepSeam(C.Structure):
+    """Mirror of `v2a_step_seam`: what v2a_gemm_cfg_euler needs besides the to_pred GEMM's own arguments."""
+    _fields_ = [("y", C.c_void_p), ("dt", C.c_void_p), ("step", C.c_void_p), ("arrive", C.c_void_p), ("planes", C.c_void_p), ("ld", C.c_int64),
+                ("lo_offset", C.c_int64), ("B", C.c_int32), ("T", C.c_int32), ("row_off", C.c_int32), ("rows_per_seq", C.c_int32),
+                ("cfg_strength", C.c_float), ("reserved", C.c_int32)]
+
+
 class T5AttnArgs(C.Structure):
     """Mirror of `v2a_t5_attn_args`."""
     _fields_ = [
@@ -157,7 +164,7 @@ EXPORTS = [
     "v2a_xattn_absorb_prepare", "v2a_xattn_absorbed",
     "v2a_roll_expand_ratio", "v2a_piano_resize_vt",
     "v2a_roll_notes",
-    "v2a_cfg_euler_planes",
+    "v2a_cfg_euler_planes", "v2a_gemm_cfg_euler",
     "v2a_mel_pad", "v2a_mel_from_dft",
     "v2a_vocos_stage_in", "v2a_vocos_dwconv_ln", "v2a_vocos_gelu", "v2a_vocos_scale_residual", "v2a_vocos_spectrum", "v2a_vocos_overlap_add",
 ]
@@ -203,6 +210,7 @@ def _declare(lib):
     lib.v2a_cfg_euler.argtypes = [vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, f32, vp]
     lib.v2a_cfg_euler_planes.argtypes = [vp, vp, i32, i32, i32, i64, i32, f32, vp, vp, vp, f32, C.POINTER(YPlanes), vp]
     lib.v2a_step_advance.argtypes = [vp, vp]
+    lib.v2a_gemm_cfg_euler.argtypes = [C.POINTER(GemmArgs), C.POINTER(StepSeam), vp]
     lib.v2a_cast_bf16.argtypes = [vp, vp, i64, vp]
     lib.v2a_split_bf16.argtypes = [vp, i64, vp, i64, i64, i32, vp]
     lib.v2a_im2col.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, i32, i32, vp]
@@ -659,6 +667,17 @@ def cfg_euler(y, pred, *, B, T, C_, pred_batch_stride, row_off, cfg_strength, dt
 
 def step_advance(step):
     check(lib().v2a_step_advance(step.data_ptr(), stream_ptr()))
+
+
+def gemm_cfg_euler(a_segs, w, out, *, y, dt, step, arrive, planes, B, T, row_off, rows_per_seq, cfg_strength, **kw):
+    """The step seam in one launch (v2a_gemm_cfg_euler): the to_pred GEMM (a_segs, w, out and kw as for gemm(); split operands, STORE), the
+    CFG + Euler update of y (B, T, C) from the two halves of its rows, the hi | lo planes of the new y into both halves of planes =
+    dict(out, ld, lo_offset), and the step counter advanced by the workgroup that arrives last at `arrive` (uint32 [1], zero between launches)."""
+    g, key, flops, nbytes = gemm_args(a_segs, w, out, **kw)
+    s = StepSeam(y.data_ptr(), dt.data_ptr(), step.data_ptr(), arrive.data_ptr(), planes["out"].data_ptr(), planes["ld"], planes["lo_offset"],
+                 B, T, row_off, rows_per_seq, float(cfg_strength), 0)
+    _launch(key.replace("store", "cfg_euler"), flops, nbytes + (8.0 + 8.0) * B * T * kw["N"],
+            lambda: lib().v2a_gemm_cfg_euler(C.byref(g), C.byref(s), stream_ptr()))
 
 
 def split_bf16(x, y, *, rows, d, ldx=None, ldy=None):

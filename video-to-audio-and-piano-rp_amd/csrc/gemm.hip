@@ -171,6 +171,84 @@ int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
 }
 
 
+// Step seam (v2a_gemm_cfg_euler): the epilogue of the to_pred GEMM that also does the CFG combine, the Euler update, the operand planes of the new
+// y and the step counter.  The workgroup's BM x BN accumulators are staged in LDS (the ring is dead), so that the thread that holds four columns of
+// a conditional row finds the same columns of its null row (BM/2 tile rows further, another wave's).  Both predictions are formed by the expressions
+// of the STORE epilogue (1 / rms per row, then the bias) and stored for every row the plain launch writes, register rows included; frame rows then
+// update y by cfg_euler_axpy, the expression of v2a_cfg_euler, and store its hi | lo planes (split_bf16's rounding) for both halves.
+// Step counter: every wave reads dt[step[0]] first; behind the barrier that follows, one thread counts the workgroup in.  The workgroup that finds
+// all others counted in advances the counter and puts the arrival counter back to zero; nobody waits for anybody.
+template <int TM, int TN, int WM, int WN, int BM, int BN>
+__device__ __forceinline__ void gemm_epilogue_cfg_euler(const GemmParams& p, f32x4 (&acc)[TM][TN], float* tile, const float* rs, int tm, int n0,
+                                                        int wm, int wn, int tid) {
+  constexpr int LD = BN + 4, HB = BM / 2;
+  static_assert(BN / 4 == 16 && HB == 2 * 16, "256 threads: 16 lanes of four columns per row, two rows each");
+  const int lane = tid & 63, lr = lane & 15, lq = lane >> 4;
+  const int32_t stepv = p.seam.step[0];
+  float h = p.seam.dt[stepv];
+  float sv = p.seam.s;
+  asm volatile("" : "+v"(h), "+v"(sv));     // h has arrived before the workgroup counts in; s in a register of its own (as cfg_euler_planes_kernel)
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) tile[(wm * WM + i * 16 + lq * 4 + jj) * LD + wn * WN + j * 16 + lr] = acc[i][j][jj];
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t nwg = gridDim.x;
+    if (atomicAdd(p.seam.arrive, 1u) == nwg - 1) {      // every workgroup has read the step
+      atomicExch(p.seam.arrive, 0u);
+      p.seam.step[0] = stepv + 1;
+    }
+  }
+  const int c4 = (tid & 15) * 4, r0 = tid >> 4;
+  const int n = n0 + c4;                    // N % BN == 0 (host): every column exists
+  const int mh = p.M >> 1, N = p.N;
+  f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+  if (p.bias) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
+  float* out = reinterpret_cast<float*>(p.out);
+  const int rps = p.seam.rows_per_seq, row_off = p.seam.row_off, T = p.seam.T;
+#pragma unroll
+  for (int q = 0; q < HB / 16; ++q) {
+    const int r = r0 + q * 16;
+    const int m = tm * HB + r;              // row of the conditional half; the null half's lies mh further
+    if (m >= mh) continue;
+    f32x4 pc = *reinterpret_cast<const f32x4*>(tile + r * LD + c4);
+    f32x4 pn = *reinterpret_cast<const f32x4*>(tile + (r + HB) * LD + c4);
+    if (rs) {
+      pc *= rs[r];
+      pn *= rs[r + HB];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      pc[e] += bv[e];
+      pn[e] += bv[e];
+    }
+    *reinterpret_cast<f32x4*>(out + (int64_t)m * p.ldo + n) = pc;
+    *reinterpret_cast<f32x4*>(out + (int64_t)(mh + m) * p.ldo + n) = pn;
+    const int b = m / rps, t = m - b * rps - row_off;
+    if (t < 0 || t >= T) continue;          // register rows (and rows a padded sequence keeps behind its frames): the predictions only
+    float* yp = p.seam.y + ((int64_t)b * T + t) * N + n;
+    f32x4 yv = *reinterpret_cast<const f32x4*>(yp);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) yv[e] = cfg_euler_axpy(yv[e], pc[e], pc[e] - pn[e], h, sv);
+    *reinterpret_cast<f32x4*>(yp) = yv;
+    bf16x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      hi[e] = (bf16_t)yv[e];
+      lo[e] = (bf16_t)(yv[e] - (float)hi[e]);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      bf16_t* row = p.seam.planes + (int64_t)(k * mh + m) * p.seam.ldp + n;
+      *reinterpret_cast<bf16x4*>(row) = hi;
+      *reinterpret_cast<bf16x4*>(row + p.seam.lo_off) = lo;
+    }
+  }
+}
+
 // ---- v2: bf16 x bf16, LDS-DMA staging, 3-deep ring -------------------------------------------
 // Both tiles arrive by global_load_lds_dwordx4 (1 KiB = 8 rows x 128 B per wave-instruction, LDS
 // image linear per wave, XOR swizzle applied to the per-lane SOURCE chunk: rule 21 of the CDNA guide),
@@ -219,6 +297,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_dma_kernel(const Gem
   int tm, tn;
   tile_of_block(p, blockIdx.x, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
+  // step seam (v2a_gemm_cfg_euler): tile row j of band tm is row tm * BM/2 + (j mod BM/2) of the conditional (j < BM/2) or the null half of the
+  // M rows, so that a tile holds both predictions of its BM/2 rows of y; same K loop, rows are only fetched from elsewhere
+  constexpr bool SEAM = EPI == V2A_EPI_CFG_EULER;
+  static_assert(!SEAM || (S3 && BK == 64), "the step seam runs on the 64-wide K stage split ring");
+  auto seam_row = [&](int j) {
+    const int mh = p.M >> 1, r = tm * (BM / 2) + (j & (BM / 2 - 1));
+    return (j >= BM / 2 ? mh : 0) + (r < mh ? r : mh - 1);
+  };
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -246,7 +332,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_dma_kernel(const Gem
   for (int i = 0; i < LPW; ++i) {
     const int g = wave + i * NW;
     if (g < GA) {
-      const int r = m0 + g * RPG + srow;
+      const int r = SEAM ? seam_row(g * RPG + srow) : m0 + g * RPG + srow;
       grow[i] = r < p.M ? r : p.M - 1;
     } else {
       const int r = n0 + (g - GA) * RPG + srow;
@@ -321,13 +407,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_dma_kernel(const Gem
   // tests/test_isa_guard.py: off there too)
   constexpr bool PF = BM * BN <= 128 * 256 && !((EPI == V2A_EPI_GATE_RESID || EPI == V2A_EPI_STORE) && BM * BN == 128 * 256);
   EpiPrefetch<EPI, TM, WN, PF> pf;
-  if (p.vec_epi) pf.load(p, m0 + wm * WM, n0 + wn * WN, lane);
+  if constexpr (!SEAM) {
+    if (p.vec_epi) pf.load(p, m0 + wm * WM, n0 + wn * WN, lane);
+  }
   // folded RMSNorm (consumer): the row's partial sums are requested ahead of the first operand DMA ...
   static_assert(BM <= 64 * NW, "one thread per tile row");
   float* rs_lds = reinterpret_cast<float*>(smem_raw + NST * STAGE_BYTES);
   const bool scaled = p.rssq != nullptr && p.vec_epi;
   RowScaleLoad rsl;
-  if (scaled && tid < BM) rowscale_load(p, m0 + tid, rsl);
+  if (scaled && tid < BM) rowscale_load(p, SEAM ? seam_row(tid) : m0 + tid, rsl);
   const int nk = p.K / BK;
   // ring of NST stages, NST - 1 K tiles in flight while one is computed (3 by default; 2: the 256x256 tile, whose 64 KB
   // stages leave room for only two; 6: the small tiles of a one-clip launch, which has at most one workgroup per CU and is
@@ -447,7 +535,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_bf16_dma_kernel(const Gem
     if constexpr (NST > 4) { if (kt + 4 < nk) tile(std::integral_constant<int, 4>{}, kt + 4); }
     if constexpr (NST > 5) { if (kt + 5 < nk) tile(std::integral_constant<int, 5>{}, kt + 5); }
   }
-  if (p.vec_epi) {
+  if constexpr (SEAM) {
+    __builtin_amdgcn_s_barrier();   // every wave is done reading the K-loop stages; all DMAs were retired above
+    static_assert(BM * (BN + 4) * 4 <= NST * STAGE_BYTES, "the staged tile must fit in the ring memory");
+    gemm_epilogue_cfg_euler<TM, TN, WM, WN, BM, BN>(p, acc, reinterpret_cast<float*>(smem_raw), scaled ? rs_lds : nullptr, tm, n0, wm, wn, tid);
+  } else if (p.vec_epi) {
     __builtin_amdgcn_s_barrier();   // every wave is done reading the K-loop stages; all DMAs were retired above
     static_assert(NW * 16 * (WN + 4) * 4 <= NST * STAGE_BYTES, "epilogue slabs must fit in the ring memory");
     float* tile = reinterpret_cast<float*>(smem_raw) + wave * (16 * (WN + 4));
@@ -889,6 +981,38 @@ static int gemm_dispatch(const v2a_gemm_args* a, GemmTarget to) {
 }
 
 extern "C" int v2a_gemm(const v2a_gemm_args* a, v2a_stream_t stream) { return gemm_dispatch(a, {(hipStream_t)stream, nullptr}); }
+
+// The step seam in one launch (include/v2a_cfm.h): gemm_prepare's checks for the to_pred GEMM, then the 64x64 split ring with the seam's row map and
+// epilogue.  One workgroup per 32 rows of a half x 64 columns.
+extern "C" int v2a_gemm_cfg_euler(const v2a_gemm_args* a, const v2a_step_seam* s, v2a_stream_t stream) {
+  GemmParams p;
+  if (int rc = gemm_prepare(a, p)) return rc;
+  V2A_REQUIRE(s && s->y && s->dt && s->step && s->arrive && s->planes, "v2a_gemm_cfg_euler: null pointer");
+  V2A_REQUIRE(a->a_dtype == V2A_BF16_SPLIT && a->compute_dtype == V2A_BF16 && a->epilogue == V2A_EPI_STORE && a->out_dtype == V2A_F32 && p.vec_epi &&
+                  !a->out_bf16 && !a->rope_table && !a->relu && !a->a_row_offset && !a->a_ktile_offset && !a->out_row_offset && a->ldo >= a->N,
+              "v2a_gemm_cfg_euler: the GEMM must be a split-operand STORE launch with dense fp32 rows and no shadow, rope, relu or offset tables");
+  V2A_REQUIRE(a->N % 64 == 0 && s->B > 0 && s->T > 0 && s->row_off >= 0 && s->rows_per_seq >= s->row_off + s->T &&
+                  (int64_t)a->M == 2 * (int64_t)s->B * s->rows_per_seq,
+              "v2a_gemm_cfg_euler: N=%d (%% 64), M=%d = 2 * B (%d) * rows_per_seq (%d), rows_per_seq >= row_off (%d) + T (%d)", a->N, a->M, s->B,
+              s->rows_per_seq, s->row_off, s->T);
+  V2A_REQUIRE(((uintptr_t)s->y & 15) == 0 && ((uintptr_t)s->planes & 7) == 0 && s->lo_offset >= a->N && s->lo_offset % 4 == 0 && s->ld % 4 == 0 &&
+                  s->ld >= s->lo_offset + a->N,
+              "v2a_gemm_cfg_euler: y needs 16-byte, planes 8-byte alignment, lo_offset (%lld) >= N, ld (%lld) >= lo_offset + N, both multiples of 4",
+              (long long)s->lo_offset, (long long)s->ld);
+  constexpr int BM = 64, BN = 64, NST = 3, BK = 64;
+  const int bands = (a->M / 2 + BM / 2 - 1) / (BM / 2);
+  const int m_real = p.M;
+  p.M = bands * BM;               // the tile map counts row bands of BM/2 rows per half
+  v2a_detail::fill_tile_map(p, BM, BN);
+  p.M = m_real;
+  p.seam = {s->y, s->dt, s->step, s->arrive, reinterpret_cast<bf16_t*>(s->planes), s->ld, s->lo_offset, s->rows_per_seq, s->row_off, s->T, s->cfg_strength};
+  constexpr size_t smem = NST * (size_t)(BM + BN) * (BK * 2) * 2 + BM * 4 + 16;      // as launch_dma: the ring + one row scale per tile row
+  auto kern = gemm_bf16_dma_kernel<V2A_EPI_CFG_EULER, float, BM, BN, 2, 2, NST, true, BK>;
+  static std::atomic<uint64_t> lds_set{0};
+  if (int rc = v2a_enable_lds(reinterpret_cast<const void*>(kern), smem, lds_set, "v2a_gemm_cfg_euler")) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(256), smem, (hipStream_t)stream, p);
+  return v2a_check_launch("v2a_gemm_cfg_euler");
+}
 
 extern "C" int v2a_gemm_choose(const v2a_gemm_args* a, v2a_gemm_choice* choice) {
   V2A_REQUIRE(choice != nullptr, "v2a_gemm_choose: null choice");

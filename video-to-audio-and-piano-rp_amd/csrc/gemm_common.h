@@ -65,6 +65,18 @@ struct GemmParams {
   // to three) logical segments, whose rows are [hi k | lo k] (lda >= 2k), against weight rows [W_hi (s3_kl) | W_lo (s3_kl)].  0 = plain operands
   int32_t s3_kl;
   int32_t dbg;              // probe builds only (-DV2A_GEMM_PROBE, scripts/probes/kloop_probe.py): K-loop parts switched off by bit
+  // step seam (v2a_gemm_cfg_euler, gemm.hip): what the CFG + Euler epilogue of the to_pred GEMM needs besides the GEMM's own operands.  Read by
+  // that one instantiation only
+  struct Seam {
+    float* y;               // latent (B, T, N), updated in place
+    const float* dt;        // step sizes, indexed by step[0]
+    int32_t* step;          // device step counter: read by every workgroup, advanced by the one that arrives last
+    uint32_t* arrive;       // arrival counter of the launch: zero before and after
+    bf16_t* planes;         // operand planes of y: rows as the GEMM's A rows (both halves), hi plane at column c, lo plane lo_off further
+    int64_t ldp, lo_off;
+    int32_t rows_per_seq, row_off, T;
+    float s;                // CFG strength
+  } seam;
 };
 
 // tile-shape selectors of the LDS-DMA bf16 kernels (v2a_set_tuning)

@@ -618,7 +618,7 @@ __device__ __forceinline__ f32x4 cfg_euler_update(float* __restrict__ y, const f
       const float par = coef * pc[j];
       upd = (upd - par) + par * keep;
     }
-    yv[j] += h * (pc[j] + upd * s);
+    yv[j] = cfg_euler_axpy(yv[j], pc[j], upd, h, s);
   }
   *reinterpret_cast<f32x4*>(y + e) = yv;
   return yv;

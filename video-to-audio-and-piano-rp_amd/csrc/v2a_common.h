@@ -64,6 +64,9 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+// The CFG + Euler update of one latent element (rowops.hip cfg_euler_update; the step-seam epilogue of gemm.hip): y + h (pc + s upd) with
+// upd = pc - pn, or its projected form under APG.  One expression for every kernel that updates y, so that they round alike.
+__device__ __forceinline__ float cfg_euler_axpy(float y, float pc, float upd, float h, float s) { return y + h * (pc + upd * s); }
 __device__ __forceinline__ float silu_exact_f(float x) { return x / (1.0f + expf(-x)); }   // libm expf, IEEE division: the fp32 parity form
 __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7): one v_exp + one v_rcp instead of libm erff's

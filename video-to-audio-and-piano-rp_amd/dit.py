@@ -334,6 +334,28 @@ def process_streams(dev):
     return s
 
 
+class StreamHandoffs:
+    """The stream primitives DiTEngine.forward() expresses its hand-offs with (DiTEngine.handoffs): the stream launches currently go to,
+    a block of launches on another stream, an event recorded on a stream, a stream waiting for an event.  This one is torch.cuda's; a
+    test substitutes labelled fake streams and drives forward() on the CPU (tests/test_schedule_hazards.py)."""
+
+    def current(self, dev):
+        """The stream of the caller, None on a device without streams: everything is then issued in order."""
+        return torch.cuda.current_stream() if dev.type == "cuda" else None
+
+    def on(self, stream):
+        """Context manager: launches inside go to `stream`."""
+        return torch.cuda.stream(stream)
+
+    def rec(self, stream):
+        e = torch.cuda.Event()
+        e.record(stream)
+        return e
+
+    def wait(self, stream, event):
+        stream.wait_event(event)
+
+
 class DiTEngine:
     """One plan = fixed (Bt sequences, T frames, nc context tokens); all buffers preallocated."""
 
@@ -384,8 +406,20 @@ class DiTEngine:
         # and add the tables prepare(fold_embed=True) computed at y = 0; no linear_small / split_bf16 per evaluation.  A caller that runs
         # prepare() -> euler_step() without begin_steps() keeps the unfolded sequence.  V2A_FOLD_EMBED=0 turns the default off (A/B runs).
         self.fold_embed = os.environ.get("V2A_FOLD_EMBED", "1") != "0"
+        # an armed plan (begin_steps) without APG: the step seam -- to_pred, the CFG + Euler update with the planes of the new y, and the step
+        # counter -- as ONE launch (v2a_gemm_cfg_euler) instead of three dependent ones on an idle chip; y, the planes, plan["pred"] and the
+        # counter equal bit for bit.  Every other caller keeps the three launches.  OFF by default: the seam it shortens (55 -> 44 us) does not
+        # resolve in sampler throughput (profiles/r10_late_ex_ab.txt), and the pinned tail of an armed evaluation (tests/test_fold_embed_trace.py)
+        # stays the three launches.  V2A_FUSE_STEP_SEAM=1 in the environment turns it on (A/B runs of an unchanged bench.py).
+        self.fuse_step_seam = os.environ.get("V2A_FUSE_STEP_SEAM", "0") == "1"
         # x_at / x_af cross-condition GEMMs on the side streams (True: all three on the main stream, -2.2 %)
         self.cross_on_main = False
+        # plans with operand copies (bf16 / bf16x3) whose side streams run their own cross-condition GEMMs: a side block waits for the audio
+        # stream's cross-condition GEMM (eX) in front of its LAST launch, the only one that writes what that GEMM reads, instead of at its
+        # head (forward()).  Same launches per stream.  V2A_LATE_EX=0 turns the default off (A/B runs of an unchanged bench.py).
+        self.late_ex = os.environ.get("V2A_LATE_EX", "1") != "0"
+        # streams and events of forward(): torch.cuda's (a test injects recording fakes)
+        self.handoffs = StreamHandoffs()
         # capture order: audio {cross .. self-attention}, sides {conv, norm, attention}, audio {cross-attention, feed-forward},
         # sides {norm, feed-forward} instead of audio block, text block, frames block
         self.interleave_capture = False
@@ -480,6 +514,7 @@ class DiTEngine:
         p["t_pts"] = e(S)
         p["dt"] = e(S)
         p["step"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        p["arrive"] = torch.zeros(1, dtype=torch.int32, device=dev)     # arrival counter of the one-launch step seam: zero between launches
         p["apg"] = torch.zeros(2 * B, dtype=torch.float64, device=dev)
         # latent frames of the CALL (<= T when the plan is padded to a shape bucket): the APG sums of x3:162-173 run over the call's own
         # (b, n, C) tensor, not over padding rows.  A device int -- a captured graph bakes scalar arguments, and one graph serves a bucket
@@ -512,7 +547,7 @@ class DiTEngine:
         p = self.plan
         return (p["ragged"], p["has_cond"], p["per_sample_t"], self.multi_stream, self.side_tile, tuple(sorted(self.side_tiles.items())),
                 tuple(sorted(self.big_tiles.items())), tuple(sorted(self.split_tiles.items())), tuple(sorted(self.split_big_tiles.items())), self.main_tile, self.fold_norm, self.fold_gemm_all, self.fuse_skip, self.fuse_xattn, self.cross_on_main,
-                self.interleave_capture, self.rope_cross, self.zero_masked_queries, self.absorb_xattn, p["xattn_kp"], self.fold_embed, p["armed"])
+                self.interleave_capture, self.rope_cross, self.zero_masked_queries, self.absorb_xattn, p["xattn_kp"], self.fold_embed, p["armed"], self.late_ex, self.fuse_step_seam)
 
     # --------------------------------------------------------------------------- primitives
     def _rows(self, t):
@@ -621,8 +656,9 @@ class DiTEngine:
                     scale=self.cfg.dim_head ** -0.5, softclamp=self.softclamp, dtype=self.adc, out_split=self.split)
         self._mm([self._rows(ao)], A.w_out, x, M=rows, N=d, resid=x, ldo=d, ldr=d, **out_kw)
 
-    def _ff(self, Fw: _FF, x, s, nseq, d, out_kw, in_kw={}):
-        """x += epilogue(W2 geglu(W1 hn_s)); out_kw may name the `shadow` that receives the bf16 copy of x."""
+    def _ff(self, Fw: _FF, x, s, nseq, d, out_kw, in_kw={}, before_out=None):
+        """x += epilogue(W2 geglu(W1 hn_s)); out_kw may name the `shadow` that receives the bf16 copy of x.  before_out: called between the
+        two GEMMs (a side block's late wait, forward())."""
         p = self.plan
         rows = nseq * p["N"]
         hn, ffh = p[f"hn_{s}"], p[f"ffh_{s}"]
@@ -630,6 +666,8 @@ class DiTEngine:
         # the text stream's GEMM from 66.9 to 51 us alone and LOSES 2 % in the sampler, profiles/r03_rowsplit_probe.txt: not done.)
         self._mm([self._rows(hn)], Fw.w1, ffh, M=rows, N=2 * Fw.inner, epilogue=L.EPI_GEGLU, bias=Fw.b1, ldo=ffh.stride(-2),
                  **(dict(out_split=True) if self.split else {}), **in_kw)
+        if before_out is not None:
+            before_out()
         self._mm([self._rows(ffh)], Fw.w2, x, M=rows, N=d, bias=Fw.b2, resid=x, ldo=d, ldr=d, **out_kw)
 
     def _tile_hint(self, stream, op):
@@ -652,11 +690,12 @@ class DiTEngine:
         narrow = self.main_tile if op in ("x_tfa", "skip", "out", "out2", "ff2") else -1
         return max(self.side_tiles.get((stream, op), self.side_tile if side else narrow), -1) + 1
 
-    def _side_block(self, ly, s, src, dst, nseq, d, parts=(0, 1, 2)):
+    def _side_block(self, ly, s, src, dst, nseq, d, parts=(0, 1, 2), before_out=None):
         """text / frames stream block (x3:1081-1086, 1097-1101): conv, attention, feed-forward.  `parts` selects
         0 = conv + norm, 1 = attention, 2 = norm + feed-forward, so that the caller can interleave the CAPTURE order of the
         two side blocks and the audio block (a replayed graph hands kernels to the queues in capture order).  src: fp32 rows;
-        dst: a _Stream, whose operand copy the feed-forward writes."""
+        dst: a _Stream, whose operand copy the feed-forward writes -- by its out GEMM, the block's last launch and the only one that touches
+        dst.sh; before_out is called in front of that launch (part 2)."""
         p = self.plan
         N, rows = p["N"], nseq * p["N"]
         lens = p["seq_len"] if p["ragged"] else None
@@ -681,7 +720,7 @@ class DiTEngine:
         if 2 in parts:
             if not fold2:
                 self._norm_plain(x, hn, rows, d, ly[f"{s}_g2"])
-            self._ff(ly[f"{s}_ff"], x, s, nseq, d, dict(epilogue=L.EPI_RESID, tile_hint=h2, shadow=dst.sh), cons2)
+            self._ff(ly[f"{s}_ff"], x, s, nseq, d, dict(epilogue=L.EPI_RESID, tile_hint=h2, shadow=dst.sh), cons2, before_out=before_out)
 
     def _absorb(self, B, N, nc):
         """Whether a plan of B clips with N rows and nc context tokens takes the absorbed cross-attention: the identity needs no rotary
@@ -963,8 +1002,10 @@ class DiTEngine:
         on_side = self.dev.type == "cuda" and self.plan.get("st") is not None and not self.cross_on_main
         return (self._tile_hint("t", "cross"), self._tile_hint("f", "cross")) if on_side else (0, 0)
 
-    def forward(self, n_ctx_seqs: int | None = None, folded: bool = False):
+    def forward(self, n_ctx_seqs: int | None = None, folded: bool = False, seam: dict | None = None):
         """Transformer.forward over the plan's Bt sequences starting from xA; result in plan['pred'].
+        seam (euler_step on an armed plan): the arguments of L.gemm_cfg_euler besides the GEMM's -- to_pred then also updates y, writes its
+        planes and advances the step counter, the last launch of the evaluation.
         folded (an armed plan, see begin_steps): xA is not read -- layer 0's three cross-condition GEMMs take the planes of y in `ybuf`
         against G_a / G_t / G_f (K = num_channels) and add the offset tables of prepare(); same outputs, streams and events.
 
@@ -972,10 +1013,25 @@ class DiTEngine:
         their own stream; the cross-condition reads the PRE-update x, text, frames; the audio block A_i needs
         the cross-conditioned x.  Hence T_{i+1} and F_{i+1} run beside A_i.  With side streams this is
         expressed by events (captured as hipGraph edges); without them everything is issued in order on
-        the current stream.  Hand-offs per layer: side blocks done (eT, eF -> main's cross-condition GEMM of the next
-        layer), x of the layer ready (eA -> the side streams' own cross-condition GEMMs) and main's cross-condition GEMM
-        done (eX -> the side blocks may overwrite the text / frames buffers it read).  All are forward edges: the main
-        stream (the critical path) waits only for eT / eF, which the side streams reach with slack."""
+        the current stream.
+
+        Who touches the side buffers.  The text stream of layer i > 0 lives in tbuf[1] (layer 0: tL0, written by prepare() only), a _Stream
+        of fp32 rows `.x` and the operand copy `.sh` (bf16 rows or hi | lo planes; None in fp32 mode, where `.x` is the operand);
+        tbuf[0] takes the cross-conditioned rows.  Frames likewise with fbuf.  Per layer i, text side (st = its stream):
+          * main: x_tfa (or the fused x_skip) READS tbuf[1].sh -- and nothing else of the side buffers;
+          * st: x_at READS x's operand copy, tbuf[1].sh and tbuf[1].x (residual), WRITES tbuf[0].x;
+          * st: side block i+1 READS tbuf[0].x; its conv, attention and first feed-forward GEMM WRITE tbuf[1].x and the stream's scratch
+            (hn_t, ssq_t, qkv_t, ao_t, ffh_t); its LAST launch, the feed-forward-out GEMM, WRITES tbuf[1].x and tbuf[1].sh.
+        Hand-offs, all forward edges (the main stream, the critical path, waits only for eT / eF):
+          * eT, eF (side block i+1 done -> main's cross-condition GEMM of layer i+1): tbuf[1].sh is written before it is read.  The same
+            edge orders main's feed-forward-out GEMM of layer i+1, which rewrites x's operand copy, behind x_at / x_af of layer i.
+          * eA (x of layer i ready -> the side streams' x_at / x_af): x's operand copy is written before they read it.
+          * eX (main's cross-condition GEMM of layer i done -> side block i+1): write after read on what that GEMM read of tbuf[1] / fbuf[1].
+            With operand copies and the side streams running their own cross-condition GEMMs that is `.sh` alone, which only the block's
+            last launch writes: with `late_ex` the wait stands in front of that launch, and the conv .. first feed-forward GEMM of the
+            block no longer idle behind x_tfa.  In fp32 mode x_tfa reads `.x`, which the block's first launch (the conv) overwrites, and
+            with cross_on_main x_at / x_af read tbuf[1].x on the main stream: there the wait stays at the head of the block.
+        tests/test_schedule_hazards.py derives happens-before from these events and checks every cross-stream pair of launches."""
         p, c, W = self.plan, self.cfg, self.W
         B, Bt, N, rows = p["B"], p["Bt"], p["N"], p["rows"]
         D, Dt, Df = c.dim, c.dim_text, c.dim_frames
@@ -989,33 +1045,32 @@ class DiTEngine:
         tc_, fc_ = p["tL0"], p["fL0"]
         tbuf, fbuf = [p["tA"], p["tB"]], [p["fA"], p["fB"]]
 
-        main = torch.cuda.current_stream() if self.dev.type == "cuda" else None
+        H = self.handoffs
+        main = H.current(self.dev)
         st, sf = (p.get("st"), p.get("sf")) if main is not None else (None, None)
         multi = st is not None
+        # the eX wait in front of the side blocks' last launch instead of their first (docstring)
+        late = self.late_ex and multi and not self.cross_on_main and p["tA"].sh is not None and p["fA"].sh is not None
 
         class _On:                      # run a block of launches on a side stream (or inline)
             def __init__(self, s):
                 self.s = s
             def __enter__(self):
                 if multi:
-                    self.ctx = torch.cuda.stream(self.s)
+                    self.ctx = H.on(self.s)
                     self.ctx.__enter__()
             def __exit__(self, *a):
                 if multi:
                     self.ctx.__exit__(*a)
 
         def rec(stream):
-            if not multi:
-                return None
-            e = torch.cuda.Event()
-            e.record(stream)
-            return e
+            return H.rec(stream) if multi else None
 
         def wait(stream, *evs):
             if multi:
                 for e in evs:
                     if e is not None:
-                        stream.wait_event(e)
+                        H.wait(stream, e)
 
         eT = eF = None                  # layer 0's side blocks were hoisted into prepare()
         eA = rec(main) if not self.cross_on_main else None      # x of layer 0 (embed output) is ready; forks the side streams
@@ -1102,11 +1157,11 @@ class DiTEngine:
             if not last and self.interleave_capture:
                 for part in (0, 1):
                     with _On(st):
-                        if part == 0:
+                        if part == 0 and not late:
                             wait(st, eX)
                         self._side_block(nxt, "t", tbuf[0].x, tbuf[1], Bt, Dt, (part,))
                     with _On(sf):
-                        if part == 0:
+                        if part == 0 and not late:
                             wait(sf, eX)
                         self._side_block(nxt, "f", fbuf[0].x, fbuf[1], Bt, Df, (part,))
             if nctx > 0:
@@ -1131,24 +1186,27 @@ class DiTEngine:
                 # stream (the critical path) sat idle for ~75 us per layer until 18 side kernels had been handed over.
                 rest = (2,) if self.interleave_capture else (0, 1, 2)
                 with _On(st):
-                    if not self.interleave_capture:
+                    if not self.interleave_capture and not late:
                         wait(st, eX)
-                    self._side_block(nxt, "t", tbuf[0].x, tbuf[1], Bt, Dt, rest)
+                    self._side_block(nxt, "t", tbuf[0].x, tbuf[1], Bt, Dt, rest, before_out=(lambda: wait(st, eX)) if late else None)
                     eT = rec(st)
                 with _On(sf):
-                    if not self.interleave_capture:
+                    if not self.interleave_capture and not late:
                         wait(sf, eX)
-                    self._side_block(nxt, "f", fbuf[0].x, fbuf[1], Bt, Df, rest)
+                    self._side_block(nxt, "f", fbuf[0].x, fbuf[1], Bt, Df, rest, before_out=(lambda: wait(sf, eX)) if late else None)
                     eF = rec(sf)
                 tc_, fc_ = tbuf[1], fbuf[1]
             xc, xo = xo, xc
         # final norm over all rows (registers are dropped by the consumer) + to_pred (x3:1141-1143, 2083)
+        pk = dict(M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels)
         if self._fold_gemm():
-            self._mm([self._rows(p["hn_a"])], W.pred_w, p["pred"], M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels,
-                     **self._ncons("a", D))
+            pk.update(self._ncons("a", D))
         else:
             L.rmsnorm(xc.x, p["hn_a"], rows=rows, d=D, gamma=W.final_g, split=self.split)
-            self._mm([self._rows(p["hn_a"])], W.pred_w, p["pred"], M=rows, N=c.num_channels, bias=W.pred_b, ldo=c.num_channels)
+        if seam is not None:
+            L.gemm_cfg_euler([self._rows(p["hn_a"])], W.pred_w, p["pred"], compute=L.BF16, a_split=True, **pk, **seam)
+        else:
+            self._mm([self._rows(p["hn_a"])], W.pred_w, p["pred"], **pk)
         return p["pred"]
 
     def euler_step(self, y, cfg_strength: float, remove_parallel_component: bool = False, keep_parallel_frac: float = 0.0):
@@ -1158,6 +1216,11 @@ class DiTEngine:
         folded = p["armed"] and self._fold_ok(p) and "y" in p and y.data_ptr() == p["y"].data_ptr()
         if not folded:
             self.embed(y)
+        if folded and self.fuse_step_seam and not remove_parallel_component:
+            yb = p["ybuf"]
+            self.forward(folded=True, seam=dict(y=y, dt=p["dt"], step=p["step"], arrive=p["arrive"], planes=dict(out=yb.t, ld=yb.ld, lo_offset=yb.k),
+                                                B=p["B"], T=p["T"], row_off=c.num_registers, rows_per_seq=p["N"], cfg_strength=cfg_strength))
+            return
         self.forward(folded=folded)
         kw = dict(B=p["B"], T=p["T"], C_=c.num_channels, pred_batch_stride=p["N"] * c.num_channels, row_off=c.num_registers)
         planes = None
