@@ -85,9 +85,15 @@ enum {
                              value = rows [Hf, 2Hf) (x2).  fp32 compute (exact expf and division, fp32 output) or split operands (the bf16x3 mode;
                              output fp32 with exact expf, or out_dtype V2A_BF16_SPLIT: row m = [hi of the N/2 outputs | lo of them], ldo >= N, silu
                              on v_exp_f32, the weights_out operand written directly).  Plain bf16 compute refuses it. */
-  V2A_EPI_CFG_EULER = 8   /* Additive to ABI 9; v2a_gemm_cfg_euler only (v2a_gemm rejects it): the STORE epilogue on a tile that holds 32 rows of the
+  V2A_EPI_CFG_EULER = 8,  /* Additive to ABI 9; v2a_gemm_cfg_euler only (v2a_gemm rejects it): the STORE epilogue on a tile that holds 32 rows of the
                              conditional half and the same 32 rows of the null half of the M rows, followed by the CFG + Euler update of y and the
                              operand planes of the new y -- see v2a_gemm_cfg_euler below */
+  V2A_EPI_QUICK_GELU = 9  /* Additive to ABI 9: out = v sigmoid(1.702 v) = v / (1 + exp(-1.702 v)), v = acc + bias (transformers QuickGELUActivation)
+                             -- CLIPMLP.fc1 + activation_fn of the ViT-L/14-336 CLIP image encoder (`video_encoder="clip_vit2"`, x3:1426-1428,
+                             1714, 1736-1738).  Accepted and refused exactly where V2A_EPI_GELU is, with the same tiles: fp32 compute (v_exp_f32 of
+                             -|1.702 v| and a Newton-refined reciprocal of 1 + e, fp32 output) or split operands (output fp32 likewise, or out_dtype V2A_BF16_SPLIT: row m = [hi of the
+                             N outputs | lo of them], ldo >= 2N, on v_exp_f32 / v_rcp_f32, rounded to the planes once).  Evaluated in fp32 from the
+                             fp32 accumulator and finite for every finite v (v << 0 gives -0).  Plain bf16 compute refuses it. */
 };
 
 typedef struct v2a_gemm_args {
@@ -177,7 +183,7 @@ typedef struct v2a_gemm_args {
    * whether a stage holds 64 k (two steps) or 32: the sum order of an output element does not depend on the shape.  STORE (with or without
    * fused RoPE) / RESID / GATE_RESID results, their shadows and norm_ssq are equal bit for bit on the ring shapes 1..4, 6, 7, and the fp32
    * results of shape 5 (the 8-phase kernel forms the same products in the same order per 32 logical k) equal them too
-   * (tests/test_gemm_split_ring_gpu.py asserts both).  GEGLU / SWIGLU / GELU results agree to rounding only: their store forms may evaluate the activation differently. */
+   * (tests/test_gemm_split_ring_gpu.py asserts both).  GEGLU / SWIGLU / GELU / QUICK_GELU results agree to rounding only: their store forms may evaluate the activation differently. */
   int32_t tile_hint;
   /* RMSNorm folded into its neighbours (bf16 x bf16, 16-byte aligned epilogue operands, N % 32 == 0):
    * PRODUCER (RESID / GATE_RESID with out_bf16): with norm_gamma the shadow is out_bf16[m][n] = bf16(out[m][n] * gamma[n]),
@@ -198,8 +204,8 @@ typedef struct v2a_gemm_args {
   int32_t row_ssq_parts, row_norm_dim;
   /* non-zero: the out_bf16 shadow is written in the V2A_BF16_SPLIT layout, row m = [hi_0 .. hi_{N-1} | lo_0 .. lo_{N-1}] of the
    * (gamma-scaled, when norm_gamma is given) fp32 result, ld_out_bf16 >= 2 * N: the operand of a later split-bf16 GEMM without a
-   * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU, SWIGLU and GELU epilogues only): out row m = [hi | lo] planes of the N/2
-   * hidden values, ldo >= N (GELU: of the N values, ldo >= 2N).  A split shadow is written by the LDS-staged epilogue of the ring and 8-phase
+   * v2a_split_bf16 pass.  Likewise out_dtype = V2A_BF16_SPLIT (GEGLU, SWIGLU, GELU and QUICK_GELU epilogues only): out row m = [hi | lo] planes of the N/2
+   * hidden values, ldo >= N (GELU / QUICK_GELU: of the N values, ldo >= 2N).  A split shadow is written by the LDS-staged epilogue of the ring and 8-phase
    * kernels only: out_bf16_split is refused (V2A_ERR_ARG) with compute_dtype V2A_F32, with fp32 A on bf16 compute, with the SIGMOID epilogue and
    * with epilogue operands that are not 16-byte aligned -- those launches run a scalar epilogue that would write the hi plane alone. */
   int32_t out_bf16_split;

@@ -23,6 +23,7 @@ EPI_STORE, EPI_SIGMOID, EPI_GEGLU, EPI_RESID, EPI_GATE_RESID = 0, 1, 2, 3, 4
 EPI_GEGLU_TANH = 5           # v2a_gemm_skinny_f32 only
 EPI_GELU = 6                 # fp32 compute or split operands (CLIP's MLP)
 EPI_SWIGLU = 7               # fp32 compute or split operands (DINOv2's feed-forward): the GEGLU packing, silu on the gate
+EPI_QUICK_GELU = 9           # as EPI_GELU with v sigmoid(1.702 v) (the ViT-L/14-336 CLIP's MLP); 8 is v2a_gemm_cfg_euler's own
 
 _lib = None
 
@@ -409,7 +410,7 @@ def _launch(key, flops, nbytes, call):
         _prof.launch(key, flops, nbytes, lambda: check(call()))
 
 
-_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh", 6: "gelu", 7: "swiglu"}
+_EPI_NAMES = {0: "store", 1: "sigmoid", 2: "geglu", 3: "resid", 4: "gate_resid", 5: "geglu_tanh", 6: "gelu", 7: "swiglu", 9: "quick_gelu"}
 
 
 # ------------------------------------------------------------------------------------------

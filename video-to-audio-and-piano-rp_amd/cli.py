@@ -12,8 +12,9 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
 `vocos.decode` (src/inference_v2a.py / predict.py:277-278).
 
   --clip DIR         encode the videos that have no CLIP feature cache (moviepy decode, HIP CLIP encoder of this rank's GPU)
-  --video-encoder {clip_vit,dinov2}   which frame encoder the checkpoint was trained on: selects the class --clip DIR loads (the HIP
-                     CLIP ViT-bigG or DINOv2 encoder) and the cache name (`<video>.generated.npz` / `<video>.generated.dinov2.npz`)
+  --video-encoder {clip_vit,clip_vit2,dinov2}   which frame encoder the checkpoint was trained on: selects the class --clip DIR loads (the
+                     HIP CLIP ViT-bigG, CLIP ViT-L/14-336 or DINOv2 encoder) and the cache name (`<video>.generated.npz` /
+                     `<video>.generated.clip_vit2.npz` / `<video>.generated.dinov2.npz`); clip_vit2 is accepted only with --clip DIR
   --t5-engine hip    run --t5 on the HIP FLAN-T5 encoder (t5.py) of this rank's GPU instead of transformers on the CPU
   --piano            V2P (src/inference_v2p.py): the grey frames `<video>.generated_frames_raw.2.npz` (features.py; made on the GPU
                      by piano_frames.py from a moviepy decode when the cache is missing) go
@@ -216,8 +217,18 @@ def validate_batch(model, video_paths, extras, frames=None, wav: bool = False) -
                 **{k: float(v) for k, v in zip(("precision", "recall", "f1", "acc"), r.loss_breakdown)})
 
 
+class _Parser(argparse.ArgumentParser):
+    """`--video-encoder clip_vit2` is an error without `--clip DIR`: the choice stands for the pair."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, "video_encoder", None) == "clip_vit2" and ns.clip is None:
+            self.error("--video-encoder clip_vit2 needs --clip DIR (a local openai clip-vit-large-patch14-336 directory)")
+        return ns, rest
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = _Parser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("ckpt")
     ap.add_argument("drop_prompt", type=int)
     ap.add_argument("test_scp")
@@ -239,8 +250,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="what runs --t5: stock transformers on the CPU (torch) or the HIP T5Encoder on this rank's GPU (hip)")
     ap.add_argument("--clip", default=None, help="local CLIP image encoder directory (IP-Adapter sdxl_models/image_encoder): videos "
                     "without <video>.generated.npz are decoded with moviepy and encoded on this rank's GPU, and the cache is written")
-    ap.add_argument("--video-encoder", default="clip_vit", choices=["clip_vit", "dinov2"],
-                    help="the frame encoder of the checkpoint: which class --clip DIR loads (CLIP ViT-bigG or DINOv2) and which feature cache is used")
+    ap.add_argument("--video-encoder", default="clip_vit", choices=["clip_vit", "clip_vit2", "dinov2"],
+                    help="the frame encoder of the checkpoint: which class --clip DIR loads (CLIP ViT-bigG, CLIP ViT-L/14-336 or DINOv2) and which "
+                         "feature cache is used")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the piano frames through the Video2Roll encoder; a video without "

@@ -147,6 +147,11 @@ int dispatch_epi(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
     case V2A_EPI_GELU:
       if (out_f32) return launch<T, A_F32, V2A_EPI_GELU, float, BM, BN>(p, to);
       break;
+    case V2A_EPI_QUICK_GELU:   // exact-fp32 compute only (gemm_prepare refuses plain bf16 compute)
+      if constexpr (sizeof(T) == 4) {
+        if (out_f32) return launch<T, A_F32, V2A_EPI_QUICK_GELU, float, BM, BN>(p, to);
+      }
+      break;
     case V2A_EPI_GEGLU:
       if (out_f32) {
         if constexpr (sizeof(T) == 4) return launch<T, A_F32, V2A_EPI_GEGLU, float, BM, BN>(p, to);
@@ -611,6 +616,10 @@ int dispatch_s3(const v2a_gemm_args* a, const GemmParams& p, GemmTarget to) {
       if (out_f32) return launch_dma<V2A_EPI_GELU, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_GELU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       break;
+    case V2A_EPI_QUICK_GELU:
+      if (out_f32) return launch_dma<V2A_EPI_QUICK_GELU, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
+      if (a->out_dtype == V2A_BF16_SPLIT) return launch_dma<V2A_EPI_QUICK_GELU, bf16_t, BM, BN, WGM, WGN, NST, true, BK>(p, to);
+      break;
     case V2A_EPI_RESID:
       if (out_f32) return launch_dma<V2A_EPI_RESID, float, BM, BN, WGM, WGN, NST, true, BK>(p, to);
       break;
@@ -831,14 +840,19 @@ static int gemm_prepare(const v2a_gemm_args* a, GemmParams& p) {
   p.out_split = a->out_dtype == V2A_BF16_SPLIT ? 1 : 0;
   if (p.out_split)
     V2A_REQUIRE((a->epilogue == V2A_EPI_GEGLU && a->ldo >= a->N) || (a->epilogue == V2A_EPI_SWIGLU && split_in && a->ldo >= a->N) ||
-                    (a->epilogue == V2A_EPI_GELU && split_in && a->ldo >= 2 * (int64_t)a->N),
-                "v2a_gemm: out_dtype V2A_BF16_SPLIT goes with the GEGLU epilogue and ldo >= N, SWIGLU on split operands and ldo >= N, or GELU on split "
-                "operands and ldo >= 2N");
+                    (is_act(a->epilogue) && split_in && a->ldo >= 2 * (int64_t)a->N),
+                "v2a_gemm: out_dtype V2A_BF16_SPLIT goes with the GEGLU epilogue and ldo >= N, SWIGLU on split operands and ldo >= N, or GELU / QUICK_GELU "
+                "on split operands and ldo >= 2N");
   // GELU (CLIP's MLP): the exact-fp32 kernel and the split-operand kernels carry it; plain bf16 compute has no GELU instantiation
   if (a->epilogue == V2A_EPI_GELU)
     V2A_REQUIRE((a->compute_dtype == V2A_F32 || split_in) && !a->out_bf16 && !a->relu && !a->rope_table && !a->a_row_offset && !a->out_row_offset &&
                     !a->norm_gamma && !a->norm_ssq && !a->row_ssq,
                 "v2a_gemm: the GELU epilogue needs fp32 compute or split operands, dense rows, and none of out_bf16 / relu / rope / norm folding");
+  // QUICK_GELU (the ViT-L/14-336 CLIP's MLP): exactly as GELU
+  if (a->epilogue == V2A_EPI_QUICK_GELU)
+    V2A_REQUIRE((a->compute_dtype == V2A_F32 || split_in) && !a->out_bf16 && !a->relu && !a->rope_table && !a->a_row_offset && !a->out_row_offset &&
+                    !a->norm_gamma && !a->norm_ssq && !a->row_ssq,
+                "v2a_gemm: the QUICK_GELU epilogue needs fp32 compute or split operands, dense rows, and none of out_bf16 / relu / rope / norm folding");
   // SWIGLU (DINOv2's feed-forward): as GELU, built for the exact-fp32 kernel and the split-operand kernels only
   if (a->epilogue == V2A_EPI_SWIGLU)
     V2A_REQUIRE((a->compute_dtype == V2A_F32 || split_in) && !a->relu && !a->rope_table && !a->a_row_offset && !a->out_row_offset && !a->norm_gamma &&

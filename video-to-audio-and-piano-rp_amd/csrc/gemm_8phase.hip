@@ -321,8 +321,8 @@ int launch_8ph(const GemmParams& p_in, GemmTarget to) {
   if (p.s3_kl != 0) {
     if (mode == 2) return go(gemm_bf16_8ph_kernel<EPI, OutT, 2, true>, true);
     return go(gemm_bf16_8ph_kernel<EPI, OutT, 1, true>, true);
-  } else if constexpr (EPI == V2A_EPI_GELU || EPI == V2A_EPI_SWIGLU) {
-    return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): GELU / SWIGLU need split operands");
+  } else if constexpr (is_act(EPI) || EPI == V2A_EPI_SWIGLU) {
+    return v2a_fail(V2A_ERR_ARG, "v2a_gemm(8-phase): GELU / QUICK_GELU / SWIGLU need split operands");
   } else {
     if (mode == 2) return go(gemm_bf16_8ph_kernel<EPI, OutT, 2, false>, false);
     return go(gemm_bf16_8ph_kernel<EPI, OutT, 1, false>, false);
@@ -340,6 +340,9 @@ int v2a_detail::launch_gemm_8phase(const GemmParams& p, int epilogue, int out_dt
       return out_f32 ? launch_8ph<V2A_EPI_GEGLU, float>(p, to) : launch_8ph<V2A_EPI_GEGLU, bf16_t>(p, to);
     case V2A_EPI_GELU:     // v2a_gemm admits it here with split operands only (fp32 output, or hi | lo planes through bf16_t + out_split)
       if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_GELU, float>(p, to) : launch_8ph<V2A_EPI_GELU, bf16_t>(p, to);
+      break;
+    case V2A_EPI_QUICK_GELU:   // as GELU
+      if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_QUICK_GELU, float>(p, to) : launch_8ph<V2A_EPI_QUICK_GELU, bf16_t>(p, to);
       break;
     case V2A_EPI_SWIGLU:   // likewise: split operands only
       if (p.s3_kl) return out_f32 ? launch_8ph<V2A_EPI_SWIGLU, float>(p, to) : launch_8ph<V2A_EPI_SWIGLU, bf16_t>(p, to);

@@ -206,6 +206,14 @@ template <int EPI, bool FAST> __device__ __forceinline__ float glu_act(float g) 
   else return FAST ? gelu_fast_f(g) : gelu_erf_f(g);
 }
 
+// the pointwise activation epilogues (CLIP's MLPs): out = act(acc + bias) on all N columns; they share every dispatch path, restriction and store form
+__host__ __device__ constexpr bool is_act(int epi) { return epi == V2A_EPI_GELU || epi == V2A_EPI_QUICK_GELU; }
+// FAST: as for glu_act (Abramowitz-Stegun erf; v_exp / v_rcp based QuickGELU)
+template <int EPI, bool FAST> __device__ __forceinline__ float pointwise_act(float v) {
+  if constexpr (EPI == V2A_EPI_QUICK_GELU) return FAST ? quick_gelu_fast_f(v) : quick_gelu_exact_f(v);
+  else return FAST ? gelu_fast_f(v) : gelu_erf_f(v);
+}
+
 template <typename T> struct TileCfg;
 template <> struct TileCfg<bf16_t> {
   static constexpr int BK = 64;
@@ -314,7 +322,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
           float v = acc[i][j][jj];
           if (p.bias) v += p.bias[n];
           if constexpr (EPI == V2A_EPI_SIGMOID) v = sigmoid_f(v);
-          if constexpr (EPI == V2A_EPI_GELU) v = gelu_erf_f(v);
+          if constexpr (is_act(EPI)) v = pointwise_act<EPI, false>(v);
           if constexpr (EPI == V2A_EPI_RESID) v += p.resid[(int64_t)m * p.ldr + n];
           if constexpr (EPI == V2A_EPI_GATE_RESID) v = p.resid[(int64_t)m * p.ldr + n] + gvec[n] * v;
           if (p.relu) v = fmaxf(v, 0.f);
@@ -757,11 +765,11 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmParams& p, f32x
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = sigmoid_f(v[e]);
           }
-          if constexpr (EPI == V2A_EPI_GELU) {
-            // fp32 output: exact erff (fp32 parity of CLIPMLP); hi | lo planes: Abramowitz-Stegun erf (|error| <= 1.5e-7, below the
-            // 2^-17 the planes keep), as the GEGLU epilogue's split form
+          if constexpr (is_act(EPI)) {
+            // fp32 output: exact erff / expf and division (fp32 parity of CLIPMLP); hi | lo planes: Abramowitz-Stegun erf (|error| <= 1.5e-7,
+            // below the 2^-17 the planes keep), as the GEGLU epilogue's split form; QuickGELU on v_exp / v_rcp
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = sizeof(OutT) == 2 ? gelu_fast_f(v[e]) : gelu_erf_f(v[e]);
+            for (int e = 0; e < 4; ++e) v[e] = pointwise_act<EPI, sizeof(OutT) == 2>(v[e]);
           }
           if constexpr (EPI == V2A_EPI_STORE) {
             // interleaved RoPE (A6): columns (n, n+1) and (n+2, n+3) are pairs (n & 63) / 2 and +1 of this head
@@ -800,7 +808,7 @@ __device__ __forceinline__ void gemm_epilogue_lds_impl(const GemmParams& p, f32x
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (bf16_t)v[e];
             *reinterpret_cast<bf16x4*>(out + o_out + n) = o;
-            if constexpr (EPI == V2A_EPI_GELU) {
+            if constexpr (is_act(EPI)) {
               if (p.out_split) {       // bf16x3 mode: the lo plane, N columns after the hi plane (the next GEMM's split operand)
                 bf16x4 lo;
 #pragma unroll

@@ -79,6 +79,23 @@ __device__ __forceinline__ float gelu_fast_f(float x) {
   return 0.5f * x * (1.0f + copysignf(erfz, x));
 }
 
+// QuickGELU, x sigmoid(1.702 x), finite for every finite x (x << 0 gives -0, x >> 0 gives x).
+// The fp32 parity form: with e = exp(-|1.702 x|) = 2^(-|x| 1.702 log2(e)) in (0, 1] (it underflows to 0, never overflows) sigmoid is
+// 1 / (1 + e) for x >= 0 and e / (1 + e) for x < 0; the denominator lies in (1, 2], so v_rcp_f32 and one Newton step (no inf, no NaN on the
+// way) give its reciprocal to half an ulp.  The exponent is one rounded product and v_exp_f32 (1 ulp): its error, |t| 2^-24 relative in e, is
+// that of the fp32 product 1.702 x every fp32 evaluation of the module starts from, and it reaches the result only where x < 0.  libm's expf
+// and an IEEE division cost some twenty instructions more per output and made the exact-fp32 fc1 GEMM 0.9 % slower than with erff.
+__device__ __forceinline__ float quick_gelu_exact_f(float x) {
+  const float e = __builtin_amdgcn_exp2f(fabsf(x) * -2.4554669595930156f);
+  const float d = 1.0f + e;
+  float r = __builtin_amdgcn_rcpf(d);
+  r = fmaf(fmaf(-d, r, 1.0f), r, r);
+  return x * (x < 0.0f ? e : 1.0f) * r;
+}
+// The fast form, x / (1 + exp(-1.702 x)) on v_exp + v_rcp (1 ulp each), used where the result is rounded to bf16 planes anyway: for x << 0
+// the exponential overflows to +inf, rcp(inf) = 0 and the product is -0; for x >> 0 it underflows to 0 and the product is x.
+__device__ __forceinline__ float quick_gelu_fast_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)); }
+
 // Sum over the 8 lanes of an aligned lane octet, left in every lane of it: three DPP adds (swap neighbours, swap pairs, mirror the
 // half row), no LDS traffic (a __shfl_xor is a ds_bpermute).
 __device__ __forceinline__ float octet_sum(float v) {

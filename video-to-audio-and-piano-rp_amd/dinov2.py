@@ -12,8 +12,8 @@ Prepared on the host at load time: the position table interpolated to the crop's
 patch rows, LayerScale folded into the `dense` / `weights_out` (`fc2`) weights and biases in float64 before rounding or
 splitting, and `weights_in` regrouped [16 value | 16 gate] for the SWIGLU epilogue of v2a_gemm (gate = x1, value = x2).
 
-Attention runs on the MFMA kernels of v2a_attention (64-wide heads, no gate, no clamp; in `"bf16x3"` its products are on hi | lo
-bf16 planes as well), reading the fused qkv buffer in place.
+Attention runs on the MFMA kernels of v2a_attention (the engine's `mfma_attention`: 64-wide heads, no gate, no clamp; in `"bf16x3"`
+its products are on hi | lo bf16 planes as well), reading the fused qkv buffer in place.
 """
 from __future__ import annotations
 
@@ -32,9 +32,6 @@ _PREFIXES = ("image_encoder.",)
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 PIL_BICUBIC = 3
-# v2a_attention picks the key-split form of its split-operand kernel while a launch has fewer workgroups than this and more than
-# 128 keys; that form sums a row's keys in another order (see DINOv2ImageEncoder._attn_frames)
-_ATTN_KEY_SPLIT_BELOW = 200
 
 
 def infer_config(sd: dict[str, torch.Tensor]) -> dict:
@@ -85,6 +82,7 @@ class DINOv2ImageEncoder(ViTImageEncoder):
 
     _CFG_KEYS = ("hidden_size", "num_hidden_layers", "num_attention_heads", "image_size", "patch_size", "layer_norm_eps", "use_swiglu_ffn",
                  "num_channels")
+    mfma_attention = True                # 64-wide heads: v2a_attention and the engine's workgroup floor (vit.py)
 
     def __init__(self, state_dict, device, config: dict | None = None, compute: str = "bf16x3", chunk: int = 32, resize: int = 256,
                  crop: int = 224, image_mean=IMAGENET_MEAN, image_std=IMAGENET_STD):
@@ -104,7 +102,6 @@ class DINOv2ImageEncoder(ViTImageEncoder):
             raise ValueError(f"DINOv2ImageEncoder: feed-forward width {dff} must be a multiple of 64")
         super().__init__(cfg, device, compute, chunk, S=crop, resize=resize, kin=cfg["num_channels"] * P * P, dp=d, dff=dff,
                          ffn=(L.EPI_SWIGLU, 2 * dff) if self.swiglu else (L.EPI_GELU, dff), out_dim=d)
-        self.f32_attention = "v2a_attention"         # fp32 mode: "v2a_attention" (MFMA, V2A_F32) or "v2a_clip_attention" (VALU)
         f32 = lambda k: sd[k].detach().to("cpu", torch.float32)
         dev, wmat = self._dev, self._wmat
         E = "embeddings."
@@ -159,27 +156,6 @@ class DINOv2ImageEncoder(ViTImageEncoder):
             if "image_std" in pc:
                 kw.setdefault("image_std", tuple(pc["image_std"]))
         return super().from_pretrained(path, device, **kw)
-
-    # ---- device pieces -----------------------------------------------------------------------------
-    def _attn_frames(self, F: int) -> int:
-        """Frames one attention launch covers.  v2a_attention chooses between two forms of its split-operand kernel by the launch's
-        workgroup count, and they sum a row's keys in different orders: a launch is never left below that count, so that a frame's
-        result does not depend on its chunk.  The rows behind the chunk are zero, and their outputs are not read."""
-        if not self.split or self.T <= 128:
-            return F
-        per_frame = self.H * ((self.T + 63) // 64)
-        return max(F, (_ATTN_KEY_SPLIT_BELOW + per_frame - 1) // per_frame)
-
-    def attention(self, qkv, out, F: int):
-        """softmax(q k^T / 8) v per frame and head on the fused qkv rows, into the out-projection's operand."""
-        if not self.split and self.f32_attention == "v2a_clip_attention":
-            return super().attention(qkv, out, F)
-        d, T = self.d, self.T
-        B = self._attn_frames(F)
-        ors = out.stride(0)
-        L.attention(qkv.data_ptr(), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, None, out.data_ptr(),
-                    strides=(3 * d, 3 * d, 3 * d, 0, ors, T * 3 * d, T * 3 * d, T * 3 * d, 0, T * ors), B=B, H=self.H, Nq=T, Nk=T,
-                    scale=0.125, softclamp=0.0, dtype=self.ydt, out_split=self.split)
 
     def head(self, bf: dict, F: int) -> torch.Tensor:
         """pooler_output: the final layernorm on the class rows (row stride T * d), fp32; no projection."""

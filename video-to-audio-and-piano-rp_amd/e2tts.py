@@ -25,11 +25,11 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .clip import CLIPImageEncoder
+from .clip import CLIPImageEncoder, CLIPViT2ImageEncoder
 from .dinov2 import DINOv2ImageEncoder
 from .dit import DiTConfig, DiTEngine, NOTES, process_streams
 
-IMAGE_ENCODERS = {"clip_vit": CLIPImageEncoder, "dinov2": DINOv2ImageEncoder}     # video_encoder -> its HIP encoder
+IMAGE_ENCODERS = {"clip_vit": CLIPImageEncoder, "clip_vit2": CLIPViT2ImageEncoder, "dinov2": DINOv2ImageEncoder}     # video_encoder -> its HIP encoder
 
 LossBreakdown = namedtuple("LossBreakdown", ["flow", "velocity_consistency", "a", "b"])                     # x3:132
 E2TTSReturn = namedtuple("E2TTS", ["loss", "cond", "pred_flow", "pred_data", "loss_breakdown"])               # x3:134
@@ -235,7 +235,7 @@ class E2TTS:
         self._engine: DiTEngine | None = None
         self._v2r_sd, self._v2r = None, None      # optional Video2Roll frame encoder (video2roll_net.*, x3:1523)
         self._t5 = None                           # optional FLAN-T5 prompt encoder (load_text_encoder, x3:1412-1413)
-        self._clip = None                         # optional image encoder (load_image_encoder: CLIP x3:1423-1425 or DINOv2 x3:1432-1433)
+        self._clip = None                         # optional image encoder (load_image_encoder: CLIP x3:1423-1428 or DINOv2 x3:1432-1433)
         self._audio_encoder = None                # optional Encodec encoder behind a raw-wave cond (load_audio_encoder, x3:1350)
         self._audio_quantizer = None              # optional Encodec quantizer behind an integer cond of codes (load_audio_quantizer)
         self._wave_front_end = None               # resample + normalize_wav in front of the audio encoder (encode_audio), made on first use
@@ -562,23 +562,31 @@ class E2TTS:
     def load_image_encoder(self, src, **kw):
         """The image encoder behind `video_frames=` and uncached `video_paths`.  video_encoder="clip_vit" (x3:1423-1425, 1714,
         1733-1735): a `CLIPImageEncoder`, a local HF directory (IP-Adapter sdxl_models/image_encoder) or a state dict
-        (CLIPVisionModelWithProjection keys, or a reference checkpoint with `image_encoder.*`).  video_encoder="dinov2"
+        (CLIPVisionModelWithProjection keys, or a reference checkpoint with `image_encoder.*`).  video_encoder="clip_vit2"
+        (x3:1426-1428, 1714, 1736-1738): a `CLIPViT2ImageEncoder` or a local HF directory (openai clip-vit-large-patch14-336); its
+        projection_dim must equal dim_text (768 for that model).  A bare state dict is refused under this choice: it names neither the
+        activation nor the head width, so build the `CLIPViT2ImageEncoder` from it yourself and pass that.  video_encoder="dinov2"
         (x3:1432-1433, 1714, 1742-1744): a `DINOv2ImageEncoder`, a local HF directory (dinov2-giant) or a state dict (Dinov2Model keys,
         or `image_encoder.*`); its hidden_size must equal dim_text.  `kw` go to the encoder's constructor (compute, chunk, config).
         The other choices of the reference have no encoder here."""
         cls = IMAGE_ENCODERS.get(self.video_encoder)
         if cls is None:
-            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit' and 'dinov2' have a HIP encoder)")
+            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit', 'clip_vit2' and 'dinov2' have a HIP encoder)")
         if isinstance(src, cls):
             enc = src
         elif isinstance(src, (str, Path)):
             enc = cls.from_pretrained(str(src), self._device, **kw)
         elif isinstance(src, dict):
+            if self.video_encoder == "clip_vit2":
+                raise NotImplementedError("load_image_encoder: video_encoder='clip_vit2' takes a CLIPViT2ImageEncoder or a directory with config.json, "
+                                          "not a state dict (which names neither quick_gelu nor the head width)")
             enc = cls(src, self._device, **kw)
         else:
             raise TypeError(f"load_image_encoder: a {cls.__name__}, a directory or a state dict, got {type(src).__name__}")
         if self.video_encoder == "dinov2" and enc.d != self.dim_text:
             raise ValueError(f"load_image_encoder: the DINOv2 encoder's hidden_size {enc.d} is not the model's dim_text {self.dim_text}")
+        if self.video_encoder == "clip_vit2" and enc.out_dim != self.dim_text:
+            raise ValueError(f"load_image_encoder: the CLIP encoder's projection_dim {enc.out_dim} is not the model's dim_text {self.dim_text}")
         self._clip = enc
         return enc
 

@@ -340,6 +340,9 @@ def random_t5_encoder_state_dict(config: dict, seed: int = 0, amplify: float = 1
 # OpenCLIP ViT-bigG/14 as CLIPVisionModelWithProjection: IP-Adapter sdxl_models/image_encoder, the reference's "clip_vit" (x3:1423-1425)
 VIT_BIGG_14 = dict(hidden_size=1664, intermediate_size=8192, num_hidden_layers=48, num_attention_heads=16, image_size=224, patch_size=14,
                    projection_dim=1280, layer_norm_eps=1e-5, hidden_act="gelu", num_channels=3)
+# openai/clip-vit-large-patch14-336 as CLIPVisionModelWithProjection (ViT-L/14 at 336 px, 577 tokens): the reference's "clip_vit2" (x3:1426-1428)
+VIT_L_14_336 = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, image_size=336, patch_size=14,
+                    projection_dim=768, layer_norm_eps=1e-5, hidden_act="quick_gelu", num_channels=3)
 
 
 def random_clip_vision_state_dict(config: dict, seed: int = 0, outlier: float = 0.0) -> dict[str, torch.Tensor]:

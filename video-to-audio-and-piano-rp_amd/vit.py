@@ -12,7 +12,8 @@ products per fp32 product, fp32 accumulate).  LayerNorm, softmax and the residua
 
 A model states what is its own: the geometry and feed-forward epilogue it hands to `__init__`, its prepared weights (`patch_w`,
 `cls`, `pos`, `lut`, optionally `pre_ln`, and `layers`: one dict `ln1, qkv, qkv_b, o, o_b, ln2, fc1, fc1_b, fc2, fc2_b` per
-layer), `head`, and -- where it does not use the VALU kernel `v2a_clip_attention` -- `attention` and `_attn_frames`.
+layer), `head`, and its attention: the VALU kernel `v2a_clip_attention` (any head width up to 112), or -- `mfma_attention = True`, 64-wide
+heads only -- the MFMA kernels of `v2a_attention` together with the floor on the workgroups of a launch (`_attn_frames`).
 """
 from __future__ import annotations
 
@@ -28,6 +29,9 @@ from .weights import read_hf_dir
 # bf16x3 tile of every GEMM pinned (the 256x256 8-phase kernel, three products per 32-wide K stage): the summation order of a split GEMM depends on
 # the kernel, and a by-shape choice would make a frame's result depend on how many frames share its chunk
 _SPLIT_TILE = 5
+# v2a_attention picks the key-split form of its split-operand kernel while a launch has fewer workgroups than this and more than
+# 128 keys; that form sums a row's keys in another order (see ViTImageEncoder._attn_frames)
+_ATTN_KEY_SPLIT_BELOW = 200
 
 
 class ViTImageEncoder:
@@ -36,6 +40,8 @@ class ViTImageEncoder:
 
     _CFG_KEYS: tuple[str, ...] = ()      # the config.json fields from_pretrained hands to the constructor
     pre_ln = None                        # (weight, bias) of a LayerNorm between the embeddings and the first layer, if the model has one
+    mfma_attention = False               # True: v2a_attention (MFMA, 64-wide heads; bf16x3: its products on hi | lo planes too), False: v2a_clip_attention
+    f32_attention = "v2a_attention"      # with mfma_attention, the fp32 mode's kernel: "v2a_attention" (MFMA, V2A_F32) or "v2a_clip_attention" (VALU)
 
     def __init__(self, cfg: dict, device, compute: str, chunk: int, *, S: int, resize: int, kin: int, dp: int, dff: int, ffn: tuple[int, int],
                  out_dim: int):
@@ -115,8 +121,14 @@ class ViTImageEncoder:
         return pl
 
     def _attn_frames(self, F: int) -> int:
-        """Frames one attention launch covers (the qkv / ao buffers hold that many); the rows behind the chunk stay zero."""
-        return F
+        """Frames one attention launch covers (the qkv / ao buffers hold that many); the rows behind the chunk stay zero, and their
+        outputs are not read.  v2a_attention chooses between two forms of its split-operand kernel by the launch's workgroup count, and
+        they sum a row's keys in different orders: a launch is never left below that count, so that a frame's result does not depend
+        on its chunk."""
+        if not self.mfma_attention or not self.split or self.T <= 128:
+            return F
+        per_frame = self.H * ((self.T + 63) // 64)
+        return max(F, (_ATTN_KEY_SPLIT_BELOW + per_frame - 1) // per_frame)
 
     def _head_buffers(self, F: int) -> dict:
         return {}
@@ -161,9 +173,15 @@ class ViTImageEncoder:
                                            rows, self.d, ln[0].data_ptr(), ln[1].data_ptr(), self.eps, L.stream_ptr()))
 
     def attention(self, qkv, out, F: int):
-        """softmax(q k^T / sqrt(dh)) v per frame and head on the fused qkv rows, into the out-projection's operand (VALU kernel)."""
+        """softmax(q k^T / sqrt(dh)) v per frame and head on the fused qkv rows (read in place), into the out-projection's operand."""
+        d, T = self.d, self.T
+        if self.mfma_attention and (self.split or self.f32_attention != "v2a_clip_attention"):
+            ors = out.stride(0)
+            L.attention(qkv.data_ptr(), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, None, out.data_ptr(),
+                        strides=(3 * d, 3 * d, 3 * d, 0, ors, T * 3 * d, T * 3 * d, T * 3 * d, 0, T * ors), B=self._attn_frames(F), H=self.H,
+                        Nq=T, Nk=T, scale=self.dh ** -0.5, softclamp=0.0, dtype=self.ydt, out_split=self.split)
+            return
         a = L.ClipAttnArgs()
-        d = self.d
         a.q, a.k, a.v, a.out = qkv.data_ptr(), qkv.data_ptr() + 4 * d, qkv.data_ptr() + 8 * d, out.data_ptr()
         a.row_stride, a.batch_stride = 3 * d, self.T * 3 * d
         a.out_row_stride, a.out_batch_stride = out.stride(0), self.T * out.stride(0)
