@@ -1023,6 +1023,28 @@ int v2a_vocos_spectrum(const float* logits, int64_t ld_logits, int64_t rows, int
 int v2a_vocos_overlap_add(const float* frames, int64_t ld_frames, int64_t rows_per_clip, const float* wsq, int32_t B, int32_t T, int32_t n_fft,
                           int32_t hop, const int32_t* lens, float* out, int64_t out_batch_stride, v2a_stream_t stream);
 
+/* =======================================================================================
+ * N3: CLIP ConvNeXt image encoder, `video_encoder="clip_convnext"` of the reference (and the third part of "mixed"):
+ * open_clip's `image_encoder.encode_image` = TimmModel.forward = head(trunk(x)) around timm's ConvNeXt (x3:1429-1431, 1716-1720,
+ * 1739-1741).  convnext.py runs it as: v2a_clip_resize_h / _v (patches of 4), v2a_gemm (stem.0), v2a_clip_layernorm (stem.1), per stage
+ * v2a_clip_layernorm + v2a_im2col + v2a_gemm (downsample), per block v2a_convnext_dwconv + v2a_clip_layernorm + v2a_gemm (mlp.fc1,
+ * V2A_EPI_GELU) + v2a_gemm (mlp.fc2 with gamma folded in, V2A_EPI_RESID), then v2a_convnext_pool_ln + v2a_gemm (head.proj).  Maps are
+ * fp32 NHWC, (F, H, W, C) dense.  No atomics.  Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+/* out[f][y][x][c] = bias[c] + sum_{ky, kx < 7} wt[(ky * 7 + kx) * C + c] * x[f][y + ky - 3][x + kx - 3][c], x = 0 outside the map:
+ * per output ONE fp32 chain acc = bias, acc = fma(w, x, acc) in ascending (ky, kx) order, so a pixel's bits depend neither on the
+ * tiling nor on F nor on the frame's position.  wt is tap-major, (49, C): wt[(ky * 7 + kx) * C + c] = conv_dw.weight[c][0][ky][kx].
+ * Any H, W >= 1 (maps smaller than the kernel included); C a multiple of 4; x != out; F <= 65535.
+ * Replaces: ConvNeXtBlock.conv_dw (nn.Conv2d(C, C, 7, padding=3, groups=C)) of timm's ConvNeXt. */
+int v2a_convnext_dwconv(const float* x, float* out, const float* wt, const float* bias, int32_t F, int32_t H, int32_t W, int32_t C,
+                        v2a_stream_t stream);
+/* out[f][c] = LayerNorm_c(mean_p x[f * frame_stride + p * C + c]), p < pixels: the pixel sum of a channel is one fp32 chain in ascending
+ * p, divided once; the LayerNorm is v2a_clip_layernorm's (biased variance, centred two-pass).  C <= 4096; one fp32 row of ldo >= C per
+ * frame.  Replaces: the head of timm's ConvNeXt behind open_clip's TimmModel (global average pool, head.norm), pool = 'avg'. */
+int v2a_convnext_pool_ln(const float* x, int64_t frame_stride, int32_t F, int32_t pixels, int32_t C, const float* gamma, const float* beta,
+                         float eps, float* out, int64_t ldo, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
 `vocos.decode` (src/inference_v2a.py / predict.py:277-278).
 
   --clip DIR         encode the videos that have no CLIP feature cache (moviepy decode, HIP CLIP encoder of this rank's GPU)
-  --video-encoder {clip_vit,clip_vit2,dinov2}   which frame encoder the checkpoint was trained on: selects the class --clip DIR loads (the
+  --video-encoder {clip_vit,clip_vit2,clip_convnext,dinov2,mixed}   which frame encoder the checkpoint was trained on: selects the class --clip DIR loads (the
                      HIP CLIP ViT-bigG, CLIP ViT-L/14-336 or DINOv2 encoder) and the cache name (`<video>.generated.npz` /
                      `<video>.generated.clip_vit2.npz` / `<video>.generated.dinov2.npz`); clip_vit2 is accepted only with --clip DIR
   --t5-engine hip    run --t5 on the HIP FLAN-T5 encoder (t5.py) of this rank's GPU instead of transformers on the CPU
@@ -218,12 +218,16 @@ def validate_batch(model, video_paths, extras, frames=None, wav: bool = False) -
 
 
 class _Parser(argparse.ArgumentParser):
-    """`--video-encoder clip_vit2` is an error without `--clip DIR`: the choice stands for the pair."""
+    """`--video-encoder clip_vit2`, `clip_convnext` and `mixed` are errors without `--clip DIR`: the choice stands for the pair."""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
         if getattr(ns, "video_encoder", None) == "clip_vit2" and ns.clip is None:
             self.error("--video-encoder clip_vit2 needs --clip DIR (a local openai clip-vit-large-patch14-336 directory)")
+        if getattr(ns, "video_encoder", None) == "clip_convnext" and ns.clip is None:
+            self.error("--video-encoder clip_convnext needs --clip DIR (a local open_clip CLIP-convnext_xxlarge directory)")
+        if getattr(ns, "video_encoder", None) == "mixed" and ns.clip is None:
+            self.error("--video-encoder mixed needs --clip DIR (one subdirectory per choice: clip_vit, clip_vit2, clip_convnext, dinov2)")
         return ns, rest
 
 
@@ -250,9 +254,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="what runs --t5: stock transformers on the CPU (torch) or the HIP T5Encoder on this rank's GPU (hip)")
     ap.add_argument("--clip", default=None, help="local CLIP image encoder directory (IP-Adapter sdxl_models/image_encoder): videos "
                     "without <video>.generated.npz are decoded with moviepy and encoded on this rank's GPU, and the cache is written")
-    ap.add_argument("--video-encoder", default="clip_vit", choices=["clip_vit", "clip_vit2", "dinov2"],
-                    help="the frame encoder of the checkpoint: which class --clip DIR loads (CLIP ViT-bigG, CLIP ViT-L/14-336 or DINOv2) and which "
-                         "feature cache is used")
+    ap.add_argument("--video-encoder", default="clip_vit", choices=["clip_vit", "clip_vit2", "clip_convnext", "dinov2", "mixed"],
+                    help="the frame encoder of the checkpoint: which class --clip DIR loads (CLIP ViT-bigG, CLIP ViT-L/14-336, CLIP ConvNeXt-XXLarge, "
+                         "DINOv2, or all four side by side from DIR's subdirectories of those names) and which feature cache is used")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model-config", default=None, help="JSON dict of transformer kwargs (default: predict.py:120-134)")
     ap.add_argument("--piano", action="store_true", help="V2P: condition on the piano frames through the Video2Roll encoder; a video without "
@@ -392,6 +396,9 @@ def main(argv=None):
                 frames, duration = decode(vp)
             except ImportError as e:
                 raise FileNotFoundError(f"{vp}: no cached CLIP features and moviepy is not installed to decode it for --clip") from e
+            if a.video_encoder == "mixed":                          # the parts' own caches are read and written too (x3:1745-1788)
+                from .features import encode_mixed_cached
+                return encode_mixed_cached(vp, frames, duration, cenc), duration
             return cenc(frames).cpu(), duration
     if a.audio_prompt_seconds > 0 or a.wav:                          # a checkpoint without cond_proj_in.* was refused above
         model.load_audio_encoder(torch.load(a.encodec, map_location="cpu"))

@@ -26,10 +26,12 @@ import torch
 
 from . import _lib as L
 from .clip import CLIPImageEncoder, CLIPViT2ImageEncoder
+from .convnext import CLIPConvNeXtImageEncoder, MixedImageEncoder, MIXED_ORDER, is_convnext_state_dict
 from .dinov2 import DINOv2ImageEncoder
 from .dit import DiTConfig, DiTEngine, NOTES, process_streams
 
-IMAGE_ENCODERS = {"clip_vit": CLIPImageEncoder, "clip_vit2": CLIPViT2ImageEncoder, "dinov2": DINOv2ImageEncoder}     # video_encoder -> its HIP encoder
+IMAGE_ENCODERS = {"clip_vit": CLIPImageEncoder, "clip_vit2": CLIPViT2ImageEncoder, "clip_convnext": CLIPConvNeXtImageEncoder,
+                  "dinov2": DINOv2ImageEncoder, "mixed": MixedImageEncoder}     # video_encoder -> its HIP encoder
 
 LossBreakdown = namedtuple("LossBreakdown", ["flow", "velocity_consistency", "a", "b"])                     # x3:132
 E2TTSReturn = namedtuple("E2TTS", ["loss", "cond", "pred_flow", "pred_data", "loss_breakdown"])               # x3:134
@@ -567,11 +569,23 @@ class E2TTS:
         projection_dim must equal dim_text (768 for that model).  A bare state dict is refused under this choice: it names neither the
         activation nor the head width, so build the `CLIPViT2ImageEncoder` from it yourself and pass that.  video_encoder="dinov2"
         (x3:1432-1433, 1714, 1742-1744): a `DINOv2ImageEncoder`, a local HF directory (dinov2-giant) or a state dict (Dinov2Model keys,
-        or `image_encoder.*`); its hidden_size must equal dim_text.  `kw` go to the encoder's constructor (compute, chunk, config).
-        The other choices of the reference have no encoder here."""
+        or `image_encoder.*`); its hidden_size must equal dim_text.  video_encoder="clip_convnext" (x3:1429-1431, 1716-1720,
+        1739-1741): a `CLIPConvNeXtImageEncoder`, a local open_clip directory or a state dict (`visual.trunk.*` / `visual.head.*`,
+        `image_encoder.*` or bare `trunk.*` / `head.*`); its embed_dim must equal dim_text.  video_encoder="mixed" (x3:1745-1788): a
+        `MixedImageEncoder`, a directory with one subdirectory per choice, or a dict with one entry per choice (an encoder, a
+        directory or a state dict each); the widths must add up to dim_text.  `kw` go to the encoder's constructor (compute, chunk,
+        config)."""
         cls = IMAGE_ENCODERS.get(self.video_encoder)
         if cls is None:
-            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} (only 'clip_vit', 'clip_vit2' and 'dinov2' have a HIP encoder)")
+            raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} has no HIP encoder (built: {', '.join(IMAGE_ENCODERS)})")
+        if isinstance(src, dict) and self.video_encoder in ("clip_convnext", "mixed"):
+            if self.video_encoder == "mixed" and set(src) == set(MIXED_ORDER):
+                src = MixedImageEncoder({k: self._part_encoder(k, src[k], kw) for k in MIXED_ORDER})
+            elif not is_convnext_state_dict(src) or self.video_encoder == "mixed":
+                raise NotImplementedError(f"load_image_encoder: video_encoder={self.video_encoder!r} " +
+                                          ("takes a MixedImageEncoder, a directory or a dict with one entry per choice " + str(list(MIXED_ORDER))
+                                           if self.video_encoder == "mixed" else "takes ConvNeXt weights (trunk.stem.0.weight ...)") +
+                                          "; a state dict without trunk.stem.0.weight holds the weights of 'clip_vit', 'clip_vit2' or 'dinov2'")
         if isinstance(src, cls):
             enc = src
         elif isinstance(src, (str, Path)):
@@ -587,13 +601,33 @@ class E2TTS:
             raise ValueError(f"load_image_encoder: the DINOv2 encoder's hidden_size {enc.d} is not the model's dim_text {self.dim_text}")
         if self.video_encoder == "clip_vit2" and enc.out_dim != self.dim_text:
             raise ValueError(f"load_image_encoder: the CLIP encoder's projection_dim {enc.out_dim} is not the model's dim_text {self.dim_text}")
+        if self.video_encoder == "clip_convnext" and enc.out_dim != self.dim_text:
+            raise ValueError(f"load_image_encoder: the ConvNeXt encoder's embed_dim {enc.out_dim} is not the model's dim_text {self.dim_text}")
+        if self.video_encoder == "mixed" and enc.out_dim != self.dim_text:
+            raise ValueError(f"load_image_encoder: the mixed encoders' widths add up to {enc.out_dim}, not the model's dim_text {self.dim_text}")
         self._clip = enc
         return enc
 
-    def _encode_video_frames(self, clips) -> list:
+    def _part_encoder(self, choice: str, src, kw: dict):
+        """One part of a mixed encoder: an encoder as it is, a directory through from_pretrained, a state dict through the class."""
+        cls = IMAGE_ENCODERS[choice]
+        if isinstance(src, (str, Path)):
+            return cls.from_pretrained(str(src), self._device, **kw)
+        if isinstance(src, dict):
+            return cls(src, self._device, **kw)
+        return src
+
+    def _encode_video_frames(self, clips, paths=None) -> list:
         """[(frames uint8 (F, H, W, 3), duration) or None] -> [(image_embeds (F, dim) float32 on the CPU, duration) or None]; the
-        frames of all clips of one frame size go through the encoder in one batched pass."""
+        frames of all clips of one frame size go through the encoder in one batched pass.  Under "mixed" with `paths` (the videos
+        the clips belong to) each clip goes through `encode_mixed_cached`: its parts' own caches are read and written (x3:1745-1788)."""
         out = [None] * len(clips)
+        if paths is not None and isinstance(self._clip, MixedImageEncoder):
+            from .features import encode_mixed_cached
+            for i, c in enumerate(clips):
+                if c is not None:
+                    out[i] = (encode_mixed_cached(paths[i], c[0], float(c[1]), self._clip), float(c[1]))
+            return out
         groups: dict[tuple, list[int]] = {}
         arrs = {}
         for i, c in enumerate(clips):
@@ -648,7 +682,7 @@ class E2TTS:
                 plain = [vp[0] if isinstance(vp, tuple) else vp for vp in video_paths]
                 todo = [fr if vp is not None and fr is not None and not os.path.exists(feature_cache_path(vp, self.video_encoder)) else None
                         for vp, fr in zip(plain, video_frames)]
-                done = {vp: e for vp, e in zip(plain, self._encode_video_frames(todo)) if e is not None}
+                done = {vp: e for vp, e in zip(plain, self._encode_video_frames(todo, plain)) if e is not None}
                 def encoder_fn(vp):
                     if vp not in done:
                         raise FileNotFoundError(f"{feature_cache_path(vp, self.video_encoder)}: no cached CLIP features and no frames for {vp}")

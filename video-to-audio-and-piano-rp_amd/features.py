@@ -128,6 +128,23 @@ def encode_video_cached(video_paths, l: int, dim: int = 1280, video_encoder: str
     return torch.stack(rows, 0)
 
 
+def encode_mixed_cached(video_path: str, frames, duration: float, mixed) -> torch.Tensor:
+    """The `mixed` branch of encode_video for one uncached video (x3:1745-1788): every part (`clip_vit`, `clip_vit2`, `clip_convnext`,
+    `dinov2`) is read from its own cache next to the video when that exists, else computed by `mixed.encoders[part]` and written
+    there -- the reference leaves the write of the clip_vit part commented out; here all four are written, under the names their own
+    choices use -- and the parts are joined per frame, cut to the shortest: (F, sum of widths) float32 on the CPU.  The caller
+    writes the `.generated.mixed.npz` cache."""
+    parts = {}
+    for k, enc in mixed.encoders.items():
+        fp = feature_cache_path(video_path, k)
+        if os.path.exists(fp):
+            parts[k] = load_clip_cache(fp)[0].float()
+        else:
+            parts[k] = enc(frames).cpu()
+            save_clip_cache(fp, parts[k], duration)
+    return mixed.concat(parts)
+
+
 # ---- piano-frame cache of the V2P path (the `piano` branch of E2TTS.encode_video_frames, x3:1829-1991) ------------------
 def piano_frames_cache_path(video_path: str) -> str:
     """x3:1876: the grey 100x900 frames of a video are cached next to it."""

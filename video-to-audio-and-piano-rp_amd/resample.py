@@ -72,16 +72,23 @@ def resize_output_size(h: int, w: int, size: int) -> tuple[int, int]:
 class ResizePlan:
     """Host tables of one input size: the crop columns of the horizontal pass, the input rows it covers and the crop rows of the
     vertical pass (bounds relative to the first covered row).  `resize`: the shortest-edge target when it differs from the crop S
-    (DINOv2's processor resizes to 256 and crops 224; CLIP's resizes to the crop size, the default)."""
+    (DINOv2's processor resizes to 256 and crops 224; CLIP's resizes to the crop size, the default).  `crop_offset`: "floor", the
+    transformers processors' (h - S) // 2, or "torchvision", CenterCrop's int(round((h - S) / 2.0)) with Python's rounding (half to
+    even), which differs where h - S is odd: 199 / 2 = 99.5 -> 100, not 99."""
 
-    def __init__(self, H: int, W: int, S: int, resize: int | None = None):
+    def __init__(self, H: int, W: int, S: int, resize: int | None = None, crop_offset: str = "floor"):
+        if crop_offset not in ("floor", "torchvision"):
+            raise ValueError(f"ResizePlan: crop_offset {crop_offset!r} (floor or torchvision)")
         self.H, self.W, self.S = H, W, S
         self.resize = S if resize is None else int(resize)
         if self.resize < S:
             raise ValueError(f"ResizePlan: resize {self.resize} below the crop {S} (the processor would pad)")
         oh, ow = resize_output_size(H, W, self.resize)
         self.out_hw = (oh, ow)
-        self.top, self.left = (oh - S) // 2, (ow - S) // 2
+        if crop_offset == "torchvision":
+            self.top, self.left = int(round((oh - S) / 2.0)), int(round((ow - S) / 2.0))
+        else:
+            self.top, self.left = (oh - S) // 2, (ow - S) // 2
         hb, hk = resample_coeffs(W, ow)
         vb, vk = resample_coeffs(H, oh)
         self.hb, self.hk = hb[self.left:self.left + S].copy(), hk[self.left:self.left + S].copy()
@@ -107,10 +114,16 @@ class ResizePlan:
         return np.clip(out, 0, 255).astype(np.uint8)
 
 
-def normalize_table(mean=OPENAI_CLIP_MEAN, std=OPENAI_CLIP_STD) -> np.ndarray:
+def normalize_table(mean=OPENAI_CLIP_MEAN, std=OPENAI_CLIP_STD, formula: str = "transformers") -> np.ndarray:
     """(3, 256) float32: the processor's value of byte u in channel c -- rescale in float64 then cast (transformers `rescale`),
-    normalise in float32 (`normalize`)."""
+    normalise in float32 (`normalize`).  formula="torchvision": ToTensor's float32 division u / 255 followed by Normalize's
+    (t - mean) / std in float32 (open_clip's image_transform)."""
+    if formula not in ("transformers", "torchvision"):
+        raise ValueError(f"normalize_table: formula {formula!r} (transformers or torchvision)")
     u = np.arange(256, dtype=np.uint8)[:, None].repeat(3, 1)
-    x = (u.astype(np.float64) * (1 / 255)).astype(np.float32)
+    if formula == "torchvision":
+        x = u.astype(np.float32) / np.float32(255)
+    else:
+        x = (u.astype(np.float64) * (1 / 255)).astype(np.float32)
     y = (x - np.array(mean, dtype=np.float32)) / np.array(std, dtype=np.float32)
     return np.ascontiguousarray(y.T.astype(np.float32))

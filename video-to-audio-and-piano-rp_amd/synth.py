@@ -444,6 +444,48 @@ def random_dinov2_state_dict(config: dict, seed: int = 0, outlier: float = 0.0) 
     return sd
 
 
+# open_clip CLIP-convnext_xxlarge-laion2B-s34B-b82K-augreg-soup, the vision tower: the reference's "clip_convnext" (x3:1429-1431)
+CONVNEXT_XXLARGE = dict(depths=(3, 4, 30, 3), dims=(384, 768, 1536, 3072), embed_dim=1024)
+
+
+def random_convnext_state_dict(config: dict, seed: int = 0, outlier: float = 0.0) -> dict[str, torch.Tensor]:
+    """Seeded weights in open_clip's key layout of a TimmModel around timm's ConvNeXt (`visual.trunk.*`, `visual.head.proj.weight`;
+    the real checkpoint is not reachable offline), `config` = dict(depths, dims, embed_dim), by the rules of
+    random_clip_vision_state_dict: numpy PCG64 float32 normals, matrices and convolutions ~ N(0, 1/fan_in), biases and LayerNorm beta
+    ~ 0.1 N, LayerNorm gamma ~ 1 + 0.1 N.  The layer scale `gamma` is drawn uniformly from 0.1 .. 1 (trained values of a size at
+    which the blocks matter, not the init value 1e-6).  `outlier > 0` scales the `mlp.fc2` rows (and biases) of four channels per stage
+    by `outlier`, which drives those channels of the map far above the rest."""
+    import numpy as np
+
+    depths, dims, E = tuple(config["depths"]), tuple(config["dims"]), int(config["embed_dim"])
+    rng = np.random.default_rng(seed)
+    nrm = lambda shp, s: torch.from_numpy(rng.standard_normal(shp, dtype=np.float32) * np.float32(s))
+    T = "visual.trunk."
+    sd = {T + "stem.0.weight": nrm((dims[0], 3, 4, 4), 1.0 / math.sqrt(48)), T + "stem.0.bias": nrm((dims[0],), 0.1),
+          T + "stem.1.weight": 1.0 + nrm((dims[0],), 0.1), T + "stem.1.bias": nrm((dims[0],), 0.1)}
+    for s, (n, C) in enumerate(zip(depths, dims)):
+        p = T + f"stages.{s}."
+        hot = torch.from_numpy(rng.choice(C, size=4, replace=False)) if outlier > 0 else None
+        if s:
+            Cp = dims[s - 1]
+            sd[p + "downsample.0.weight"], sd[p + "downsample.0.bias"] = 1.0 + nrm((Cp,), 0.1), nrm((Cp,), 0.1)
+            sd[p + "downsample.1.weight"], sd[p + "downsample.1.bias"] = nrm((C, Cp, 2, 2), 1.0 / math.sqrt(4 * Cp)), nrm((C,), 0.1)
+        for j in range(n):
+            b = p + f"blocks.{j}."
+            sd[b + "conv_dw.weight"], sd[b + "conv_dw.bias"] = nrm((C, 1, 7, 7), 1.0 / 7.0), nrm((C,), 0.1)
+            sd[b + "norm.weight"], sd[b + "norm.bias"] = 1.0 + nrm((C,), 0.1), nrm((C,), 0.1)
+            sd[b + "mlp.fc1.weight"], sd[b + "mlp.fc1.bias"] = nrm((4 * C, C), 1.0 / math.sqrt(C)), nrm((4 * C,), 0.1)
+            w2, b2 = nrm((C, 4 * C), 1.0 / math.sqrt(4 * C)), nrm((C,), 0.1)
+            if hot is not None:
+                w2[hot] *= outlier
+                b2[hot] *= outlier
+            sd[b + "mlp.fc2.weight"], sd[b + "mlp.fc2.bias"] = w2, b2
+            sd[b + "gamma"] = torch.from_numpy(rng.uniform(0.1, 1.0, C).astype(np.float32))
+    sd[T + "head.norm.weight"], sd[T + "head.norm.bias"] = 1.0 + nrm((dims[-1],), 0.1), nrm((dims[-1],), 0.1)
+    sd["visual.head.proj.weight"] = nrm((E, dims[-1]), 1.0 / math.sqrt(dims[-1]))
+    return sd
+
+
 def synthetic_video_frames(n: int, h: int, w: int, seed: int = 0) -> "np.ndarray":
     """(n, h, w, 3) uint8 RGB test frames: smooth per-frame colour gradients plus noise, so the resize filters really average."""
     import numpy as np

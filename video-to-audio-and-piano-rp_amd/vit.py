@@ -42,6 +42,7 @@ class ViTImageEncoder:
     pre_ln = None                        # (weight, bias) of a LayerNorm between the embeddings and the first layer, if the model has one
     mfma_attention = False               # True: v2a_attention (MFMA, 64-wide heads; bf16x3: its products on hi | lo planes too), False: v2a_clip_attention
     f32_attention = "v2a_attention"      # with mfma_attention, the fp32 mode's kernel: "v2a_attention" (MFMA, V2A_F32) or "v2a_clip_attention" (VALU)
+    crop_offset = "floor"                # ResizePlan's: the transformers processors' (h - S) // 2, or "torchvision" (convnext.py)
 
     def __init__(self, cfg: dict, device, compute: str, chunk: int, *, S: int, resize: int, kin: int, dp: int, dff: int, ffn: tuple[int, int],
                  out_dim: int):
@@ -114,7 +115,7 @@ class ViTImageEncoder:
         key = (H, W)
         pl = self._plans.get(key)
         if pl is None:
-            rp = ResizePlan(H, W, self.S, self.resize)
+            rp = ResizePlan(H, W, self.S, self.resize, crop_offset=self.crop_offset)
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
             pl = (rp, t(rp.hb), t(rp.hk), t(rp.vb), t(rp.vk))
             self._plans[key] = pl
