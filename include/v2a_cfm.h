@@ -1045,6 +1045,52 @@ int v2a_convnext_dwconv(const float* x, float* out, const float* wt, const float
 int v2a_convnext_pool_ln(const float* x, int64_t frame_stride, int32_t F, int32_t pixels, int32_t C, const float* gamma, const float* beta,
                          float eps, float* out, int64_t ldo, v2a_stream_t stream);
 
+/* =======================================================================================
+ * HiFi-GAN vocoder (AudioLDM's 16 kHz / 64-mel generator): mel frames -> wave, the `decode_to_waveform` half of `VaeWrapper.decode`
+ * (x3:470-490, self.vocos = 'vae' at x3:1404-1409): `vocoder_infer` (src/audioldm/hifigan/utilities.py:76-86) around `Generator.forward`
+ * (src/audioldm/hifigan/models.py:163-180).  hifigan.py runs it as: v2a_hifigan_act_pad + v2a_gemm (conv_pre), per stage
+ * v2a_hifigan_act_pad + v2a_gemm (the transposed convolution in polyphase form), per ResBlock round either v2a_hifigan_act_pad + v2a_gemm
+ * chains (tap segments, K chunks chained by V2A_EPI_RESID) or two v2a_hifigan_conv launches, v2a_hifigan_act_pad (the MRF mean), and
+ * v2a_hifigan_post.  Activations are fp32 rows of C floats, frame t of clip b at row b * rows_per_clip + t.  `lens` (device int32[B] or
+ * NULL = T everywhere): clip b has lens[b] frames at this stage and is decoded as if it were alone; the kernels clamp lens[b] to 0 .. T.
+ * No atomics.  Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+#define V2A_HIFIGAN_TILE 128                    /* frames of a workgroup of v2a_hifigan_conv */
+#define V2A_HIFIGAN_MAX_ROWS (1 << 28)
+#define V2A_HIFIGAN_POST_MAX_C 512              /* 16 samples + 6 halo rows of C + 1 floats fit 64 KB of LDS */
+
+/* out: B clips of out_rows_per_clip rows of C floats (dense, row stride C); row halo + t of clip b, 0 <= t < lens[b], is
+ *   leaky_relu(((s0 + s1) + s2) / divisor, slope)       of row b * src_rows_per_clip + t of the sources (row stride ld_src),
+ * s1 and s2 optional (NULL), the sums and the IEEE division in fp32 in that order, the division skipped for divisor == 1,
+ * leaky_relu(v) = v > 0 ? v : v * slope (slope 1: a copy).  Every other row of out -- the halo in front, everything behind the clip's own
+ * length -- is zero; every element of out is written.  out_rows_per_clip >= T + 2 halo; C a multiple of 4.
+ * Replaces: F.leaky_relu(x, LRELU_SLOPE) in front of every convolution (models.py:97-100, 165), `xs / self.num_kernels` (models.py:173),
+ * F.leaky_relu(x) in front of conv_post (models.py:174, the default slope 0.01) and the zero padding of the convolutions behind them. */
+int v2a_hifigan_act_pad(const float* s0, const float* s1, const float* s2, int64_t src_rows_per_clip, int64_t ld_src, int32_t B, int32_t T,
+                        int32_t C, const int32_t* lens, float divisor, float slope, float* out, int64_t out_rows_per_clip, int32_t halo,
+                        v2a_stream_t stream);
+/* a: activated rows of C floats (dense), frame t of clip b at row b * rows_per_clip + t; frames outside [0, lens[b]) are taken as zero
+ * whatever the buffer holds.  For t < lens[b]:
+ *   pre = fma(w[6 C + C - 1], a[t + 3][C - 1], ... fma(w[1], a[t - 3][1], fma(w[0], a[t - 3][0], bias[0])))      w tap-major (7, C)
+ *   wave[b * out_batch_stride + t] = tanhf(pre);  pcm[...] = (int16) trunc(wave * 32768) saturated to -32768 .. 32767;  pre[...] = pre
+ * wave, pcm, pre optional, one of wave and pcm required; nothing else is written.  C <= V2A_HIFIGAN_POST_MAX_C.
+ * Replaces: conv_post and torch.tanh (models.py:175-176) and `(wavs.cpu().numpy() * 32768).astype("int16")` (utilities.py:81). */
+int v2a_hifigan_post(const float* a, int64_t rows_per_clip, int32_t B, int32_t T, int32_t C, const int32_t* lens, const float* w,
+                     const float* bias, float* wave, int16_t* pcm, float* pre, int64_t out_batch_stride, v2a_stream_t stream);
+/* Direct dilated Conv1d(C, C, k, dilation d, padding (k - 1) d / 2) with the leaky ReLU in front of it, on v_mfma_f32_16x16x4_f32.
+ * For t < lens[b], row r = b * rows_per_clip + t:
+ *   out[r][co] = sum_j (sum_ci W[co][ci][j] * leaky_relu(x[t + (j - (k - 1) / 2) d][ci], slope)) + bias[co] (+ resid[r][co])
+ * x = 0 outside [0, lens[b]).  Per tap j one fp32 chain from zero over ci ascending, the taps' sums added in ascending j, then the bias,
+ * then the residual: the bits of an output depend on (k, C) alone, not on the tile, the batch or the other clips.  wp holds W in
+ * fragment order, k C C floats: float 4 i + e of wp, i = ((j * C / 16 + kq) * C / 16 + n) * 64 + lane, is
+ * W[16 n + (lane & 15)][16 kq + 4 e + (lane >> 4)][j].  Rows t >= lens[b] of out are not written.  C = 32, 64 or 128; k odd;
+ * (V2A_HIFIGAN_TILE + (k - 1) d) rows of C + 4 floats fit 160 KB of LDS; out != x, out may be resid; 16-byte aligned rows.
+ * Replaces: one `c(F.leaky_relu(x, LRELU_SLOPE))` of ResBlock.forward, and for convs2 the `xt + x` behind it (models.py:96-102). */
+int v2a_hifigan_conv(const float* x, int64_t ldx, int64_t rows_per_clip, int32_t B, int32_t T, int32_t C, const int32_t* lens,
+                     const float* wp, const float* bias, int32_t k, int32_t d, float slope, const float* resid, int64_t ldr, float* out,
+                     int64_t ldo, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,7 @@ EXPORTS = [
     "v2a_mel_pad", "v2a_mel_from_dft",
     "v2a_vocos_stage_in", "v2a_vocos_dwconv_ln", "v2a_vocos_gelu", "v2a_vocos_scale_residual", "v2a_vocos_spectrum", "v2a_vocos_overlap_add",
     "v2a_convnext_dwconv", "v2a_convnext_pool_ln",
+    "v2a_hifigan_act_pad", "v2a_hifigan_post", "v2a_hifigan_conv",
 ]
 
 
@@ -262,6 +263,9 @@ def _declare(lib):
     lib.v2a_vocos_overlap_add.argtypes = [vp, i64, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp]
     lib.v2a_convnext_dwconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.v2a_convnext_pool_ln.argtypes = [vp, i64, i32, i32, i32, vp, vp, f32, vp, i64, vp]
+    lib.v2a_hifigan_act_pad.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, vp, f32, f32, vp, i64, i32, vp]
+    lib.v2a_hifigan_post.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.v2a_hifigan_conv.argtypes = [vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, i64, vp, i64, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int

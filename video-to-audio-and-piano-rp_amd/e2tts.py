@@ -488,11 +488,14 @@ class E2TTS:
     def load_vocoder(self, src, **kw):
         """The Vocos vocoder behind `sample(return_raw_output=False)` of a model whose latents are mel frames (x3:2275-2287; the
         reference's `Vocos.from_pretrained(pretrained_vocos_path)`, e2_tts_crossatt.py:1324): a `Vocos`, its state dict, or a local
-        directory with config.yaml and pytorch_model.bin.  Sets `self.vocos` and returns it.  `kw` go to the Vocos constructor."""
+        directory with config.yaml and pytorch_model.bin.  Sets `self.vocos` and returns it.  `kw` go to the Vocos constructor.
+        A `HiFiGAN` instance (the vocoder of the reference's `self.vocos = 'vae'`, x3:1404-1409) is taken as it is; a state dict or a
+        directory always means Vocos."""
+        from .hifigan import HiFiGAN
         from .vocos import Vocos
-        if isinstance(src, Vocos):
+        if isinstance(src, (Vocos, HiFiGAN)):
             if kw:
-                raise TypeError("load_vocoder: keywords go with a state dict or a directory, not with a Vocos")
+                raise TypeError(f"load_vocoder: keywords go with a state dict or a directory, not with a {type(src).__name__}")
             voc = src
         elif isinstance(src, dict):
             voc = Vocos(src, self._device, **kw)

@@ -525,3 +525,33 @@ def synthetic_edge_frames(n: int, h: int, w: int, seed: int = 0) -> "np.ndarray"
         grey = np.where(use_fine, fine, coarse[..., 0])
         out[f] = (grey * 255).astype(np.uint8)[..., None]
     return out
+
+
+def random_hifigan_state_dict(config: dict, seed: int = 0) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of `Generator(h).state_dict()` after `remove_weight_norm()` (src/audioldm/hifigan/models.py; the
+    real checkpoint is not reachable offline), `config` as `hifigan.HIFIGAN_16K_64`, in the order of `hifigan.expected_state_dict_shapes`
+    from one numpy `RandomState(seed)`: weights ~ N(0, g^2 / fan_in) with fan_in = C_in k for a convolution and C_in k / u for a transposed
+    one (each output frame meets k / u of its taps), g = 0.5 for the ResBlock convolutions (eighteen of them add to a stage's signal) and 1
+    elsewhere; biases ~ 0.1 N(0, 1).  The module's own `init_weights` (std 0.01) gives waves of 1e-1 that test nothing."""
+    import numpy as np
+    from .hifigan import expected_state_dict_shapes as shapes
+
+    rng = np.random.RandomState(seed)
+    rates = tuple(config["upsample_rates"])
+    sd = {}
+    for key, shape in shapes(config).items():
+        if key.endswith(".bias"):
+            std = 0.1
+        elif key.startswith("ups."):
+            std = 1.0 / math.sqrt(shape[0] * shape[2] / rates[int(key.split(".")[1])])
+        else:
+            std = (0.5 if key.startswith("resblocks.") else 1.0) / math.sqrt(shape[1] * shape[2])
+        sd[key] = torch.from_numpy((rng.standard_normal(shape) * std).astype(np.float32))
+    return sd
+
+
+def synthetic_log_mel(b: int, T: int, C: int = 64, seed: int = 0) -> torch.Tensor:
+    """(b, C, T) fp32 log-mel-like frames, 2 N(0, 1) - 3 from numpy `RandomState(seed)`: the range of AudioLDM's log-mel images."""
+    import numpy as np
+
+    return torch.from_numpy((2.0 * np.random.RandomState(seed).standard_normal((b, C, T)) - 3.0).astype(np.float32))
