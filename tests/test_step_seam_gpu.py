@@ -100,3 +100,36 @@ def test_apg_keeps_the_three_launches(L, model):
     assert plain == dict(fused=1, cfg_euler=0, gemm=off["gemm"]), (plain, off)
     assert apg == off == dict(fused=0, cfg_euler=1, gemm=off["gemm"]), (apg, off)
     assert int(p["step"].item()) == 3 and int(p["arrive"].item()) == 0
+
+
+def test_fused_seam_graph_equals_eager(L):
+    """Depth-2 engine at the SMALL widths of tests/test_fold_embed_gpu.py with the fused seam: the captured armed evaluation replayed S = 4 times
+    against the eager loop -- y, the planes of both halves, the predictions, the step and the arrival counter, bit for bit (as
+    test_graph_equals_eager there does for the three launches)."""
+    from test_fold_embed_gpu import SMALL
+    cfg = O.DiTConfig(**SMALL)
+    P = O.init_params(cfg, 11)
+    y0, text, roll, ctx, cm = O.synthetic_inputs(cfg, 2, 37, nc=NC, seed=3, piano=True)
+    kw = dict(y0=y0, text_embed=text, context=ctx, context_mask=cm, frames_embed=roll, steps=S + 1, cfg_strength=2.0,
+              remove_parallel_component=False, return_raw_output=True)
+    models = [make_model(cfg, P, "bf16x3"), make_model(cfg, P, "bf16x3", use_graph=False)]
+    got, fused = [], []
+    try:
+        for m, eager in zip(models, (False, True)):
+            m.engine().fuse_step_seam = True
+            run = lambda: got.append((m.sample(torch.zeros(2, 37, cfg.num_channels), **kw).float().cpu(),))      # noqa: E731
+            fused.append(_launches(L, run)["fused"] if eager else run())        # launches are counted on the eager loop only
+            torch.cuda.synchronize()
+            p = m.engine().plan
+            assert p["armed"]
+            got[-1] += (dict(y=p["y"].clone(), ybuf=p["ybuf"].t.clone(), pred=p["pred"].clone(), step=p["step"].clone(), arrive=p["arrive"].clone()),)
+    finally:
+        for m in models:
+            m.engine().fuse_step_seam = False
+    (ya, a), (yb, b) = got
+    assert models[0].graph_captures == 1 and models[1].graph_captures == 0
+    assert fused[1] == S, "the eager loop issues the one-launch seam in every evaluation"
+    assert torch.isfinite(ya).all() and torch.equal(ya, yb) and not torch.equal(ya, y0)
+    for name in ("y", "ybuf", "pred", "step", "arrive"):
+        assert torch.equal(a[name], b[name]), (name, float((a[name].float() - b[name].float()).abs().max()))
+    assert int(a["step"].item()) == S and int(a["arrive"].item()) == 0
