@@ -1091,6 +1091,78 @@ int v2a_hifigan_conv(const float* x, int64_t ldx, int64_t rows_per_clip, int32_t
                      const float* wp, const float* bias, int32_t k, int32_t d, float slope, const float* resid, int64_t ldr, float* out,
                      int64_t ldo, v2a_stream_t stream);
 
+/* =======================================================================================
+ * AudioLDM VAE decoder: latents -> the 64-bin mel image, the `decode_first_stage` half of `VaeWrapper.decode` (x3:470-490): `z / scale_factor`,
+ * `post_quant_conv` and `Decoder.forward` (src/audioldm/variational_autoencoder/modules.py:650-683; ResnetBlock :155-175, AttnBlock :204-230,
+ * Upsample :53-57, Normalize :38-41 = GroupNorm(32, eps 1e-6), nonlinearity :33-35 = x sigmoid(x)).  audioldm_vae.py runs it as:
+ * v2a_vae_stage_in, then per GroupNorm v2a_vae_gn_stats + v2a_vae_gn_act_pad, per 3x3 convolution a chain of exact-fp32 v2a_gemm launches
+ * (one A segment per kernel row over the flat padded grid, K in launches chained by V2A_EPI_RESID), the attention as v2a_gemm launches
+ * around v2a_vae_softmax, v2a_vae_upsample_pad in front of an Upsample's convolution, and v2a_vae_conv_out.
+ * Activations are channels-last fp32: time on H, frequency bins on W, C floats per pixel; Wp = W + 2.  Pixel (y, x) of clip b lies at row
+ *   bordered:  b * rows_per_clip + (y + 1) Wp + (x + 1)      a one-pixel border around the clip, rows_per_clip >= (H + 2) Wp
+ *   flat:      b * rows_per_clip + y * src_wp + x            what a GEMM over the bordered grid writes (src_wp = Wp), or dense (src_wp = W);
+ *                                                            rows with x >= W or y >= lens[b] are never read
+ * `lens` (device int32[B] or NULL = H everywhere): clip b has lens[b] rows of pixels at this stage and is decoded as if it were alone; the
+ * kernels clamp lens[b] to 0 .. H.  No atomics; no sum's order depends on the batch.  Additive: the ABI version does not change.
+ * ===================================================================================== */
+
+#define V2A_VAE_GROUPS 32                       /* GroupNorm groups (modules.py:38) */
+#define V2A_VAE_GN_TILE 512                     /* pixels of one partial sum of v2a_vae_gn_stats */
+#define V2A_VAE_MAX_H (1 << 20)
+#define V2A_VAE_MAX_W 4096
+#define V2A_VAE_MAX_C 4096
+#define V2A_VAE_MAX_Z 64
+#define V2A_VAE_MAX_ROWS (1 << 28)
+
+/* The latent z[b][c][t][w] is read at src + b * batch_stride + c * chan_stride + t * time_stride + w * bin_stride: emb (b, 16 zc, l) of
+ * `VaeWrapper.decode`, whose z[b][c][t][w] = emb[b][16 c + w][t], has strides (16 zc l, 16 l, 1, l); z (b, zc, l, 16) has (16 zc l, 16 l, 16, 1).
+ * out: the bordered map of c_pad channels, for t < lens[b]:
+ *   out[..][co] = fma(w[co][zc - 1], z[zc - 1], ... fma(w[co][0], z[0], bias[co]))    co < zc, w (zc, zc) row-major;   0 for zc <= co < c_pad
+ * The border and the rows at or behind lens[b] are zero; every element of out (B clips of out_rows_per_clip rows) is written.
+ * zc <= c_pad <= V2A_VAE_MAX_Z, c_pad a multiple of 16 (the K granule of the GEMM behind it).
+ * Replaces: the transposes and the reshape of VaeWrapper.decode (x3:478-481), `z = 1.0 / self.scale_factor * z` and `post_quant_conv` (the
+ * host folds 1 / scale_factor into w in float64). */
+int v2a_vae_stage_in(const float* src, int64_t batch_stride, int64_t chan_stride, int64_t time_stride, int64_t bin_stride, int32_t B, int32_t H,
+                     int32_t W, int32_t zc, const int32_t* lens, const float* w, const float* bias, float* out, int32_t c_pad,
+                     int64_t out_rows_per_clip, v2a_stream_t stream);
+/* partials[((b * tiles + j) * 32 + g) * 2 + {0, 1}] = the sum and the sum of squares, in double, of group g (channels g C / 32 ..) over the
+ * pixels j * V2A_VAE_GN_TILE <= p < (j + 1) * V2A_VAE_GN_TILE of clip b, p = y W + x counted from the clip's own first pixel, p < lens[b] W.
+ * Order: thread s of 8 adds pixels p = s, s + 8, ... of the tile, a pixel's channels ascending, in one chain (squares by fma); the 8 chains
+ * are added in ascending s.  Every entry of partials (B * tiles * 64 doubles) is written, zero where the tile holds no pixel of the clip.
+ * x is a flat map (src_wp >= W).  C a multiple of 32 up to V2A_VAE_MAX_C; tiles >= ceil(H W / V2A_VAE_GN_TILE).
+ * Replaces: the statistics of torch.nn.GroupNorm (modules.py:38-41). */
+int v2a_vae_gn_stats(const float* x, int64_t src_rows_per_clip, int32_t src_wp, int32_t B, int32_t H, int32_t W, int32_t C, const int32_t* lens,
+                     double* partials, int32_t tiles, v2a_stream_t stream);
+/* Per (clip, group): S, SS = the partials of tiles 0 .. ceil(lens[b] W / V2A_VAE_GN_TILE) - 1 added in ascending order; n = lens[b] W C / 32;
+ * mean = S / n, var = max(SS / n - mean^2, 0), rstd = 1 / sqrt(var + eps), all in double, mean and rstd then rounded to fp32 once.  Per element
+ *   y = ((x - mean) * rstd) * gamma[c] + beta[c]          four separately rounded fp32 operations
+ *   out = swish ? y / (1 + expf(-y)) : y                  libm expf, IEEE division
+ * border 1: out is the bordered map (the operand of a convolution); border 0: dense rows b * out_rows_per_clip + y W + x (the attention's
+ * norm).  Border pixels and rows at or behind lens[b] are zero; every element of out (B clips of out_rows_per_clip rows) is written:
+ * this is the zero padding of the next convolution, per clip of a ragged batch.  out != x; 16-byte aligned rows.
+ * Replaces: torch.nn.GroupNorm and `nonlinearity` (modules.py:157-158, 164-165, 206, 678-679). */
+int v2a_vae_gn_act_pad(const float* x, int64_t src_rows_per_clip, int32_t src_wp, int32_t B, int32_t H, int32_t W, int32_t C, const int32_t* lens,
+                       const double* partials, int32_t tiles, const float* gamma, const float* beta, double eps, int32_t swish, float* out,
+                       int64_t out_rows_per_clip, int32_t border, v2a_stream_t stream);
+/* out: the bordered map of 2 H x 2 W pixels (pitch 2 W + 2): pixel (Y, X), Y < 2 lens[b], is a bit copy of pixel (Y / 2, X / 2) of the flat
+ * map x; the border and everything at or behind row 2 lens[b] are zero; every element of out is written.  C a multiple of 4.
+ * Replaces: F.interpolate(scale_factor=2.0, mode="nearest") and the padding of the convolution behind it (modules.py:54-56). */
+int v2a_vae_upsample_pad(const float* x, int64_t src_rows_per_clip, int32_t src_wp, int32_t B, int32_t H, int32_t W, int32_t C, const int32_t* lens,
+                         float* out, int64_t out_rows_per_clip, v2a_stream_t stream);
+/* In place over `rows` rows of ld floats: with v[j] = scale * s[j] (one rounded product), m = max_j v[j] over j < n,
+ *   e[j] = expf(v[j] - m),   s[j] = e[j] / sum,   s[j] = 0 for n <= j < ld       (a PV GEMM may read K padded to its granule)
+ * sum: thread t of 256 adds e[t], e[t + 256], ... in ascending order; a wave adds its 64 lanes by the xor butterfly (32, 16, .. 1); the four
+ * waves' sums are added as (w0 + w1) + (w2 + w3).  scale > 0.
+ * Replaces: `w_ * c ** -0.5` and softmax(dim=2) of AttnBlock.forward (modules.py:217-218). */
+int v2a_vae_softmax(float* s, int64_t ld, int32_t rows, int32_t n, float scale, v2a_stream_t stream);
+/* a: an activated bordered map of C channels (v2a_vae_gn_act_pad's).  For y < lens[b]:
+ *   out[(b * H + y) * W + x] = fma chain from bias[0] over ky, then kx, then c ascending of w[(ky * 3 + kx) * C + c] * a[(y + ky, x + kx)][c]
+ * ((y + ky, x + kx) in bordered coordinates), and 0 for y >= lens[b]: every element of out (B, H, W) is written -- time-major mel rows, the
+ * row layout of hifigan.py.  C a multiple of 4.
+ * Replaces: conv_out (modules.py:680) for out_ch = 1. */
+int v2a_vae_conv_out(const float* a, int64_t rows_per_clip, int32_t B, int32_t H, int32_t W, int32_t C, const int32_t* lens, const float* w,
+                     const float* bias, float* out, v2a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ from .wave import WaveFrontEnd, sinc_resample_table  # noqa: F401
 from .mel import MelSpec, mel_filterbank, stft_basis  # noqa: F401
 from .vocos import Vocos, istft_basis  # noqa: F401
 from .hifigan import HiFiGAN  # noqa: F401
+from .audioldm_vae import AudioLDMVaeDecoder, VaeVocoder  # noqa: F401
 from .midi import roll_to_notes, notes_to_roll, write_midi, read_midi  # noqa: F401
 from . import midi  # noqa: F401
 from . import _lib  # noqa: F401
@@ -30,4 +31,4 @@ from . import _lib  # noqa: F401
 __all__ = ["E2TTS", "DiTConfig", "DiTEngine", "PackedWeights", "collate_clips", "ClipRequest",
            "shard_range", "gather_latents", "sway_grid", "lens_to_mask", "val_span_mask", "E2TTSReturn", "LossBreakdown", "load_midi_ground_truth", "expected_state_dict_shapes", "NOTES",
            "Video2RollEngine", "Roll2MidiEngine", "Roll2MidiEnhanceEngine", "EncodecDecoder", "EncodecEncoder", "EncodecQuantizer", "T5Encoder", "CLIPImageEncoder", "CLIPViT2ImageEncoder", "DINOv2ImageEncoder", "CLIPConvNeXtImageEncoder", "MixedImageEncoder", "PianoFramePlan", "PianoFramePreprocessor",
-           "WaveFrontEnd", "sinc_resample_table", "MelSpec", "mel_filterbank", "stft_basis", "Vocos", "istft_basis", "HiFiGAN", "roll_to_notes", "notes_to_roll", "write_midi", "read_midi", "PianoConfig", "PIANO_51", "PIANO_88", "piano_config"]
+           "WaveFrontEnd", "sinc_resample_table", "MelSpec", "mel_filterbank", "stft_basis", "Vocos", "istft_basis", "HiFiGAN", "AudioLDMVaeDecoder", "VaeVocoder", "roll_to_notes", "notes_to_roll", "write_midi", "read_midi", "PianoConfig", "PIANO_51", "PIANO_88", "piano_config"]

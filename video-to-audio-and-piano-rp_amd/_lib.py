@@ -170,6 +170,7 @@ EXPORTS = [
     "v2a_vocos_stage_in", "v2a_vocos_dwconv_ln", "v2a_vocos_gelu", "v2a_vocos_scale_residual", "v2a_vocos_spectrum", "v2a_vocos_overlap_add",
     "v2a_convnext_dwconv", "v2a_convnext_pool_ln",
     "v2a_hifigan_act_pad", "v2a_hifigan_post", "v2a_hifigan_conv",
+    "v2a_vae_stage_in", "v2a_vae_gn_stats", "v2a_vae_gn_act_pad", "v2a_vae_upsample_pad", "v2a_vae_softmax", "v2a_vae_conv_out",
 ]
 
 
@@ -266,6 +267,12 @@ def _declare(lib):
     lib.v2a_hifigan_act_pad.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, vp, f32, f32, vp, i64, i32, vp]
     lib.v2a_hifigan_post.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.v2a_hifigan_conv.argtypes = [vp, i64, i64, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, i64, vp, i64, vp]
+    lib.v2a_vae_stage_in.argtypes = [vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, i32, i64, vp]
+    lib.v2a_vae_gn_stats.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp]
+    lib.v2a_vae_gn_act_pad.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, C.c_double, i32, vp, i64, i32, vp]
+    lib.v2a_vae_upsample_pad.argtypes = [vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, vp]
+    lib.v2a_vae_softmax.argtypes = [vp, i64, i32, i32, f32, vp]
+    lib.v2a_vae_conv_out.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("v2a_abi_version", "v2a_last_error", "v2a_gemm_args_size"):
             getattr(lib, name).restype = C.c_int

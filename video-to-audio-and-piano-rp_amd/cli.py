@@ -30,6 +30,11 @@ local T5 weights.  Output: `<out_dir>/<name>.latent.npy`, the (n, 128) Encodec l
                      e2_tts_crossatt.py:1324; nothing is fetched).  Each clip's valid frames are decoded by the HIP Vocos (vocos.py) and
                      written as `<name>.wav`; a clip has 24000 / hop frames per second, hop from the vocoder's config (256), not 320.
                      As the vocoder it is exclusive with --encodec.
+  --audioldm CKPT    the vocoder of a checkpoint whose latents are the AudioLDM VAE's (the reference's `self.vocos = 'vae'`, x3:1404-1409):
+                     a local torch checkpoint file, the state dict itself or a dict that holds it under `state_dict`
+                     (`first_stage_model.decoder.*`, `first_stage_model.post_quant_conv.*`, `first_stage_model.vocoder.*`, `scale_factor`).
+                     Each clip's valid frames go through the HIP VAE decoder and HiFi-GAN (audioldm_vae.py, hifigan.py) and are written as
+                     `<name>.wav` at 16 kHz; a clip has 16000 / 640 = 25 frames per second.  Exclusive with --vocos and --encodec.
   --audio-prompt-seconds S   (with --encodec, checkpoint built with if_cond_proj_in) the first S seconds of `<video>.wav` (24 kHz) are
                      encoded by the HIP Encodec encoder and given to the sampler as the audio prompt: `cond` = the raw waves,
                      `lens` = ceil(24000 S / 320) frames, which come back unchanged in front of the generated ones (x3:2196-2231).
@@ -147,10 +152,26 @@ def validation_sources(video_paths, wav: bool = False):
     return out
 
 
-def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None, video_encoder: str = "clip_vit", hop: int = 320):
+def load_audioldm_state_dict(path):
+    """The state dict of --audioldm: a torch-saved dict of tensors, or a dict that holds one under `state_dict`.  Loaded with
+    weights_only=True; a file that holds other objects (a trainer's whole checkpoint), or no dict at all, is refused with what to do."""
+    import pickle
+    try:
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+    except pickle.UnpicklingError as e:
+        raise ValueError(f"--audioldm {path}: the file holds objects other than tensors ({e}); save its state dict alone: "
+                         f"torch.save(ckpt['state_dict'], ...)") from e
+    sd = ck.get("state_dict", ck) if isinstance(ck, dict) else None
+    if not isinstance(sd, dict) or not all(isinstance(k, str) for k in sd):
+        raise ValueError(f"--audioldm {path}: expected a state dict, or a dict with one under 'state_dict', got {type(ck).__name__}")
+    return sd
+
+
+def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip_encode=None, video_encoder: str = "clip_vit", hop: int = 320,
+                   rate: int = 24000):
     """clip_encode: optional `video_path -> (image_embeds, duration)` that makes a missing `<video>.generated.npz` (--clip);
     video_encoder: which cache name is read and written (--video-encoder); hop: samples per latent frame (320: Encodec; --vocos: the
-    vocoder's hop)."""
+    vocoder's hop; --audioldm: 640) at `rate` samples per second (--audioldm: 16000)."""
     from .collate import ClipRequest
     from .features import feature_cache_path, load_clip_cache, resample_clip_features, save_clip_cache
     reqs = []
@@ -161,7 +182,7 @@ def build_requests(items, drop_prompt: bool, n_frames: int, t5_encode=None, clip
                 raise FileNotFoundError(f"{fp}: no cached CLIP features for {vp}; pass --clip DIR (with moviepy installed) to encode it")
             save_clip_cache(fp, *clip_encode(vp))                                # x3:1706-1793
         emb, duration = load_clip_cache(fp)
-        n = min(n_frames, int(duration * 24000) // hop) if n_frames > 0 else int(duration * 24000) // hop
+        n = min(n_frames, int(duration * rate) // hop) if n_frames > 0 else int(duration * rate) // hop
         clip = resample_clip_features(emb.float(), duration, n)
         prompt = "" if drop_prompt else cap
         t5p = vp.replace(".mp4", ".t5.npz")
@@ -272,6 +293,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--encodec", default=None, help="state dict (.pt) of the Encodec model / decoder: also write <name>.wav")
     ap.add_argument("--vocos", default=None, metavar="DIR", help="local Vocos directory (config.yaml, pytorch_model.bin) of a checkpoint whose latents "
                     "are mel frames: also write <name>.wav through the HIP Vocos; exclusive with --encodec")
+    ap.add_argument("--audioldm", default=None, metavar="CKPT", help="local torch checkpoint of the AudioLDM VAE (a state dict, or a dict with one "
+                    "under state_dict) of a checkpoint whose latents are its 128-channel latents: also write <name>.wav at 16 kHz through the HIP "
+                    "VAE decoder and HiFi-GAN; exclusive with --vocos and --encodec")
     ap.add_argument("--audio-prompt-seconds", type=float, default=0.0, help="with --encodec and a checkpoint built with if_cond_proj_in: "
                     "prompt every clip with the first S seconds of <video>.wav, encoded by the HIP Encodec encoder")
     ap.add_argument("--codes", type=float, default=None, choices=[1.5, 3.0, 6.0, 12.0, 24.0], metavar="KBPS",
@@ -326,6 +350,10 @@ def main(argv=None):
 
     if a.vocos and a.encodec:
         ap.error("--vocos and --encodec are exclusive: each is the vocoder of its own latents (mel frames / Encodec latents)")
+
+    if a.audioldm and (a.vocos or a.encodec):
+        ap.error("--audioldm is exclusive with --vocos and --encodec: each is the vocoder of its own latents (VAE latents / mel frames / "
+                 "Encodec latents)")
 
     if a.codes is not None and not a.encodec:
         ap.error("--codes needs --encodec (the state dict that holds the quantizer's codebooks)")
@@ -414,6 +442,12 @@ def main(argv=None):
         voc = model.load_vocoder(a.vocos)                            # refuses a vocoder whose channels are not the model's
         hop = voc.hop
         vocoder = voc if rank == 0 else None
+    rate = 24000
+    if a.audioldm:                                                   # x3:1404-1409: the 'vae' vocoder, 16 kHz, 640 samples per latent frame
+        from .audioldm_vae import VaeVocoder
+        voc = model.load_vocoder(VaeVocoder.from_state_dict(load_audioldm_state_dict(a.audioldm), torch.device("cuda", local)))
+        hop, rate = voc.hop, 16000
+        vocoder = voc if rank == 0 else None
     items = read_scp(a.test_scp, a.start, a.end)
     os.makedirs(a.out_dir, exist_ok=True)
     gen = torch.Generator().manual_seed(a.seed)
@@ -423,7 +457,7 @@ def main(argv=None):
         s, e, per = shard_range(len(chunk), rank, world)
         mine = chunk[s:e]
         if mine:
-            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder, hop), channels, gen, notes=model.cfg.notes)
+            batch8, extras = collate_clips(build_requests(mine, bool(a.drop_prompt), a.frames, t5_encode, clip_encode, a.video_encoder, hop, rate), channels, gen, notes=model.cfg.notes)
             frames = None
             if a.piano:
                 # x3:1829, predict.py:231; a clip without a frame cache is decoded and resized on this rank's GPU, its cache written
@@ -464,9 +498,9 @@ def main(argv=None):
                 if vocoder is not None:
                     from scipy.io import wavfile
                     from .features import load_clip_cache, feature_cache_path
-                    n = min(a.frames, int(load_clip_cache(feature_cache_path(vp, a.video_encoder))[1] * 24000) // hop) if a.frames > 0 else one.shape[0]
+                    n = min(a.frames, int(load_clip_cache(feature_cache_path(vp, a.video_encoder))[1] * rate) // hop) if a.frames > 0 else one.shape[0]
                     wav = vocoder.decode(one[:n].t()[None].float())[0]                     # predict.py:277-278
-                    wavfile.write(os.path.join(a.out_dir, name + ".wav"), 24000, wav.cpu().numpy())
+                    wavfile.write(os.path.join(a.out_dir, name + ".wav"), rate, wav.cpu().numpy())
                     if a.codes is not None:
                         codes = model.latents_to_codes(one[None, :n].float(), a.codes)[0]          # (n_q, n)
                         np.save(os.path.join(a.out_dir, name + ".codes.npy"), codes.cpu().numpy().astype(np.int16))

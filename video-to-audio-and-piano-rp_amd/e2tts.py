@@ -490,10 +490,12 @@ class E2TTS:
         reference's `Vocos.from_pretrained(pretrained_vocos_path)`, e2_tts_crossatt.py:1324): a `Vocos`, its state dict, or a local
         directory with config.yaml and pytorch_model.bin.  Sets `self.vocos` and returns it.  `kw` go to the Vocos constructor.
         A `HiFiGAN` instance (the vocoder of the reference's `self.vocos = 'vae'`, x3:1404-1409) is taken as it is; a state dict or a
-        directory always means Vocos."""
+        directory always means Vocos.  So is a `VaeVocoder` (the whole of `VaeWrapper.decode`: the AudioLDM VAE decoder in front of the
+        HiFiGAN), which reads the 128-channel latents of a 'vae' model."""
+        from .audioldm_vae import VaeVocoder
         from .hifigan import HiFiGAN
         from .vocos import Vocos
-        if isinstance(src, (Vocos, HiFiGAN)):
+        if isinstance(src, (Vocos, HiFiGAN, VaeVocoder)):
             if kw:
                 raise TypeError(f"load_vocoder: keywords go with a state dict or a directory, not with a {type(src).__name__}")
             voc = src

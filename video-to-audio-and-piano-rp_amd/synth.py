@@ -555,3 +555,33 @@ def synthetic_log_mel(b: int, T: int, C: int = 64, seed: int = 0) -> torch.Tenso
     import numpy as np
 
     return torch.from_numpy((2.0 * np.random.RandomState(seed).standard_normal((b, C, T)) - 3.0).astype(np.float32))
+
+
+def random_audioldm_vae_state_dict(config: dict, seed: int = 0, bias_std: float = 0.1) -> dict[str, torch.Tensor]:
+    """Seeded weights in the key layout of the AudioLDM `AutoencoderKL`'s decoder half (`decoder.*` of
+    src/audioldm/variational_autoencoder/modules.py `Decoder`, and `post_quant_conv.*`): seeded weights, not AudioLDM's;
+    `config` as `audioldm_vae.AUDIOLDM_VAE`, in the order of `audioldm_vae.expected_state_dict_shapes` from one numpy `RandomState(seed)`:
+    convolution weights ~ N(0, 1 / fan_in), norm weights 1 + 0.1 N(0, 1), every bias (the norms' included) ~ bias_std N(0, 1).
+    bias_std = 3 is the "offset" regime: group means that dwarf the deviations and attention logits of tens.  torch's default
+    initialisation gives an output that tests nothing."""
+    import numpy as np
+    from .audioldm_vae import expected_state_dict_shapes as shapes
+
+    rng = np.random.RandomState(seed)
+    sd = {}
+    for key, shape in shapes(config).items():
+        if key.endswith(".bias"):
+            v = rng.standard_normal(shape) * bias_std
+        elif len(shape) == 1:
+            v = 1.0 + 0.1 * rng.standard_normal(shape)
+        else:
+            v = rng.standard_normal(shape) / math.sqrt(shape[1] * shape[2] * shape[3])
+        sd[key] = torch.from_numpy(v.astype(np.float32))
+    return sd
+
+
+def synthetic_vae_latents(b: int, l: int, channels: int = 128, seed: int = 0) -> torch.Tensor:
+    """(b, channels, l) fp32 latents ~ N(0, 1) from numpy `RandomState(seed)`: the `emb` of `VaeWrapper.decode`."""
+    import numpy as np
+
+    return torch.from_numpy(np.random.RandomState(seed).standard_normal((b, channels, l)).astype(np.float32))
